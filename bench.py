@@ -14,7 +14,12 @@ activations) and run concurrently — the serving engine's steady state, where
 the next batch's kernels fill the gaps of this one's launch chain.  K steps
 are timed between barriers + device synchronisation; value = frames / time.
 
-Also measured in the same run (rank 0):
+A plain run does only that: set up, warm up, time the K steps, write the last
+timed step's masks if `--dump-outputs DIR` is given (DIR/masks.npy, float32,
+what a caller of the step receives), and print the result line.
+
+With `--full`, also measured in the same run (rank 0):
+  * median_step_ms: a second pass of the same K steps with an event per step;
   * roofline: the dominant kernel's algorithmic bytes per launch / its mean
     duration from HIP events recorded by the kernel launches themselves
     (hipExtLaunchKernelGGL on the stream the kernels run on, one batch at a
@@ -432,6 +437,13 @@ def main():
     # windows"; the per-step work is the same)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg (per-step events, kernel timing and roofline, "
+                         "oracle parity, CPU baseline, latency, post, host and TypeScript paths, batch sweep); the "
+                         "--no-* options below choose among these legs and mean nothing without --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the masks the last timed step computed to DIR/masks.npy "
+                         "(float32, [frames, model_h * model_w], what the step's caller receives)")
     ap.add_argument("--batch", type=int, default=8, help="frames per GPU per step")
     ap.add_argument("--frame", default="480x640")
     ap.add_argument("--model", default="144x256")
@@ -493,7 +505,7 @@ def main():
     B = args.batch
 
     ts = None
-    if rank == 0 and world == 1 and not args.no_ts and not args.dry_run_dist:
+    if args.full and rank == 0 and world == 1 and not args.no_ts and not args.dry_run_dist:
         # (a fixed 600 batches per timed loop, whatever --steps: at the driver's
         # --steps 20 the legs ran 100 batches, ~15 ms windows that read 36-57k
         # on one box, profiles/r06c)
@@ -614,9 +626,61 @@ def main():
     wd.beat("barrier after the timed steps")
     if world > 1:
         dist.barrier()
-    wd.beat("event pass")
     timed_builds, timed_patches = sess.graph_builds - builds0, sess.graph_patches - patches0
     last = (k - 1) % S
+    if args.dump_outputs and rank == 0:
+        # the last timed step's output buffer as its caller holds it (N > 1: the gathered batch)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "masks.npy"), outs[last].cpu().numpy())
+    n_ranks = sess.comm_ranks if gather else world
+    t = torch.tensor([el], dtype=torch.float64)
+    if world > 1:
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    el_max = float(t.item())
+    value = world * B * args.steps / el_max
+    out = {
+        "metric": METRIC,
+        "value": round(value, 1),
+        "unit": "frames/s",
+        "n_gpus": n_ranks,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(el_max * 1e3 / args.steps, 5),
+        "graph_builds_in_timed_region": timed_builds,
+        "settle_ms_before_window": args.settle_ms,
+        "warmup_steps_after_settle": tail,
+        "graph_patches_in_timed_region": timed_patches,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "bf16" if args.dtype == "bf16x2" else "f32",
+        "data": "synthetic",
+        "config": {
+            "workload": f"{B} synthetic {fw}x{fh} RGB u8 frames per GPU per step (resident in HBM) -> "
+                        f"{wm}x{hm} f32 masks, {S} steps in flight (one handle, {S} slots, {S} streams)"
+                        + (", RCCL all-gather of masks in the C ABI (vss_segment_gather_device)"
+                           if world > 1 else ""),
+            "global_batch": world * B,
+            "frame": f"{fw}x{fh}x3",
+            "model_res": f"{wm}x{hm}",
+            "pw_gemm": "v_mfma_f32_16x16x32_bf16, f32 activations split hi+lo" if args.dtype == "bf16x2"
+                       else "v_mfma_f32_16x16x4_f32",
+            "graph": not args.no_graph,
+            "inflight": S,
+            "parallelism": f"dp{world}",
+            "gather_form": sess.gather_form if gather else None,
+        },
+    }
+    if not args.full:  # a plain run ends here: the headline alone
+        wd.disarm()
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        sess.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return out if rank == 0 else None
+
+    wd.beat("event pass")
     # per-step completion times (a second pass of the same K steps, events on
     # each step's stream; kept out of the headline window): the median interval
     ends = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps)]
@@ -636,16 +700,10 @@ def main():
     done_ms = np.sort(np.array([e0.elapsed_time(e) for e in ends]))
     iv = (done_ms[S:] - done_ms[:-S]) / S if len(done_ms) > S else np.diff(done_ms)
     median_step_ms = float(np.median(iv)) if len(iv) else None
-    n_ranks = sess.comm_ranks if gather else world
     d_masks = outs[last][rank * B:(rank + 1) * B] if world > 1 else outs[last][:B]
     if gather:  # the gathered batch holds every rank's masks in frame order
         assert all(torch.equal(outs[last], o) for o in outs), "every step gathers the same masks"
-    t = torch.tensor([el], dtype=torch.float64)
-    if world > 1:
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    el_max = float(t.item())
     wd.beat("profile pass")
-    value = world * B * args.steps / el_max
 
     # ---- kernel timing pass (events recorded by the launches, one batch at a time) ----
     sess.set_option(pkg.VSS_OPT_PROFILE, 1)
@@ -694,7 +752,6 @@ def main():
     if rank == 0 and world == 1 and not args.no_sweep:
         batch_sweep = sweep(pkg, torch, dev, fh, fw, args.dtype, S, args.steps)
 
-    out = None
     if rank == 0:
         masks = d_masks.cpu().numpy()
         err = None
@@ -706,40 +763,9 @@ def main():
             err = float(np.abs(masks - ref).max())
             if world == 1:
                 cpu = cpu_baseline(blob, frames, hm, wm, args.cpu_budget_s)
-        out = {
-            "metric": METRIC,
-            "value": round(value, 1),
-            "unit": "frames/s",
-            "n_gpus": n_ranks,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(el_max * 1e3 / args.steps, 5),
+        out.update({
             "median_step_ms": round(median_step_ms, 5) if median_step_ms else None,
             "value_at_median_step": round(world * B / (median_step_ms * 1e-3), 1) if median_step_ms else None,
-            "graph_builds_in_timed_region": timed_builds,
-            "settle_ms_before_window": args.settle_ms,
-            "warmup_steps_after_settle": tail,
-            "graph_patches_in_timed_region": timed_patches,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "bf16" if args.dtype == "bf16x2" else "f32",
-            "data": "synthetic",
-            "config": {
-                "workload": f"{B} synthetic {fw}x{fh} RGB u8 frames per GPU per step (resident in HBM) -> "
-                            f"{wm}x{hm} f32 masks, {S} steps in flight (one handle, {S} slots, {S} streams)"
-                            + (", RCCL all-gather of masks in the C ABI (vss_segment_gather_device)"
-                               if world > 1 else ""),
-                "global_batch": world * B,
-                "frame": f"{fw}x{fh}x3",
-                "model_res": f"{wm}x{hm}",
-                "pw_gemm": "v_mfma_f32_16x16x32_bf16, f32 activations split hi+lo" if args.dtype == "bf16x2"
-                           else "v_mfma_f32_16x16x4_f32",
-                "graph": not args.no_graph,
-                "inflight": S,
-                "parallelism": f"dp{world}",
-                "gather_form": sess.gather_form if gather else None,
-            },
             "mask_max_abs_err": err,
             "roofline": {
                 "bound": "hbm",
@@ -766,12 +792,12 @@ def main():
             "post": post,
             "host_path": host,
             "ts_path": ts,
-        }
+        })
         print(json.dumps(out), flush=True)
     sess.close()
     if world > 1:
         dist.destroy_process_group()
-    return out
+    return out if rank == 0 else None
 
 
 if __name__ == "__main__":

@@ -28,6 +28,14 @@ def test_world_size_must_match_gpus():
     assert "WORLD_SIZE=2" in r.stderr
 
 
+def test_full_and_dump_outputs_are_options():
+    """The legs beside the headline sit behind --full (off by default), and
+    --dump-outputs takes the directory the last timed step's masks go to."""
+    r = _run(["--help"])
+    assert r.returncode == 0
+    assert "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+
+
 def test_gpus_2_dry_run_reaches_the_clique_id_broadcast():
     """the whole multi-rank launch path of `bench.py --gpus 2`
     — launch_ranks -> torch.distributed.run -> gloo init -> rank 0's clique-id

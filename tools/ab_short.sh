@@ -4,13 +4,13 @@
 # flight) and the one-call-at-a-time latency leg, per setting and round.
 #   bash tools/ab_short.sh N "VAR=a" "VAR=b" ...   ("-" = no setting)
 N=$1; shift
-mkdir -p gpurun_out
+mkdir -p bench_out
 for r in $(seq 1 $N); do
   for e in "$@"; do
     ev=$e; [ "$e" = "-" ] && ev="VSS_AB_NONE=1"
-    env $ev timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-cpu --no-host --no-ts --no-post \
-      > gpurun_out/abs.log 2>&1 || { tail -5 gpurun_out/abs.log; exit 1; }
-    tail -1 gpurun_out/abs.log | python -c "
+    env $ev timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-cpu --no-host --no-ts --no-post \
+      > bench_out/abs.log 2>&1 || { tail -5 bench_out/abs.log; exit 1; }
+    tail -1 bench_out/abs.log | python -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 sw = {(s['batch'], s['inflight']): s['value'] for s in d['batch_sweep']}

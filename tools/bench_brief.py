@@ -1,5 +1,5 @@
-"""One-line digest of a bench.py JSON line: headline, median step, roofline,
-batch sweep, the latency legs and the host / TS legs when present.
+"""One-line digest of a bench.py JSON line: headline and, from a `--full` run,
+median step, roofline, batch sweep, the latency legs and the host / TS legs.
     python tools/bench_brief.py BENCH.json"""
 import json
 import sys

@@ -1,11 +1,11 @@
 #!/bin/bash
 # headline (400 steps, 4 in flight) under HIP runtime knobs, one run each:
 #   bash tools/env_probe.sh
-mkdir -p gpurun_out
+mkdir -p bench_out
 run() {
-  env "$@" timeout -k 10 150 python bench.py --no-cpu --no-host --no-ts --no-post --no-sweep --steps 400 \
-    > gpurun_out/envp.log 2>&1 || { tail -5 gpurun_out/envp.log; exit 1; }
-  tail -1 gpurun_out/envp.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$*', d['value'], d['value_at_median_step'])"
+  env "$@" timeout -k 10 150 python bench.py --full --no-cpu --no-host --no-ts --no-post --no-sweep --steps 400 \
+    > bench_out/envp.log 2>&1 || { tail -5 bench_out/envp.log; exit 1; }
+  tail -1 bench_out/envp.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('$*', d['value'], d['value_at_median_step'])"
 }
 run X=0
 run DEBUG_CLR_GRAPH_PACKET_CAPTURE=0

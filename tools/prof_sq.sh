@@ -11,6 +11,6 @@ cd /tmp
 export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_MFMA SQ_LDS_BANK_CONFLICT SQ_WAVES GRBM_GUI_ACTIVE \
   --output-format csv -d "$OUT/mfma" -o run -- \
-  python3 "$R/bench.py" --no-cpu --no-host --no-ts --no-sweep --no-post --steps 20 --warmup 5 > "$OUT/mfma.log" 2>&1
+  python3 "$R/bench.py" --full --no-cpu --no-host --no-ts --no-sweep --no-post --steps 20 --warmup 5 > "$OUT/mfma.log" 2>&1
 cd "$R"
 python3 tools/sq_table.py "$OUT/mfma/run_counter_collection.csv"

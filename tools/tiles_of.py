@@ -1,4 +1,4 @@
-"""The VSS_TILE spec ("layer:THxTW,...") of the kernels a bench.py JSON line
+"""The VSS_TILE spec ("layer:THxTW,...") of the kernels a `bench.py --full` JSON line
 timed (its per-layer `kernels` entries): python tools/tiles_of.py bench.json"""
 import json
 import re
