@@ -477,6 +477,71 @@ int vss_composite_device(vss_handle* h, const uint8_t* d_frames, int n, int heig
 int vss_segment_composite(vss_handle* h, vss_post_state* st, const uint8_t* frames, int n, int height, int width,
                           int channels, size_t row_stride, uint8_t* out_rgba);
 
+/* ---- virtual backgrounds (csrc/vss_background.hip) ---------------------------
+ * The person over a background as one opaque RGBA frame, so that only finished
+ * frames leave the GPU: a solid colour (composeMatteOnCanvas,
+ * client/src/core/u2FrameProc.ts:78-148), a user image drawn to the canvas
+ * size (client/customization.ts:41), or the frame itself blurred.
+ * Per colour channel, with A = vss_composite_device's alpha at frame size:
+ *   out = (fg*A + bg*(255-A) + 127) / 255   (integer division), out alpha = 255
+ * which equals u2FrameProc's Math.round((a*s/255 + (1-a)*b/255)*255), a = A/255,
+ * for every (A, fg, bg).
+ *   VSS_BG_COLOR: bg = a constant (r, g, b); (32, 32, 32) after create (:89).
+ *   VSS_BG_IMAGE: bg = the user's image scaled to the frame size with the
+ *     alpha's half-pixel bilinear (f32 lerps, rounded half up) per channel —
+ *     a definition, for up- and downscaling alike, no antialiasing; the
+ *     image's own alpha is dropped.  The scaled copy is cached on the GPU per
+ *     frame size and rebuilt only when the image or the frame size changes.
+ *   VSS_BG_BLUR: bg = the frame blurred by a separable Gaussian, edges
+ *     replicated, in 16-bit fixed point (vss_blur_weights): a horizontal pass
+ *     h = (sum w[k]*p[x+k] + 32768) >> 16 stored as u8, then the same
+ *     vertically over h.
+ * One call in flight per background object, as for vss_post_state; a setter or
+ * destroy waits for the object's latest composite before it frees or overwrites
+ * device memory, and takes effect from the next composite call.  The object's
+ * device buffers count into vss_info.device_bytes.  Destroy backgrounds before
+ * their handle. */
+enum { VSS_BG_COLOR = 0, VSS_BG_IMAGE = 1, VSS_BG_BLUR = 2 };
+typedef struct vss_background vss_background;
+int vss_background_create(vss_handle* h, vss_background** out);
+void vss_background_destroy(vss_background* bg);
+/* Each setter also selects its mode.  r, g, b in 0..255. */
+int vss_background_set_color(vss_background* bg, int r, int g, int b);
+/* pixels: host memory [height][width][channels] u8, channels 3 or 4, row_stride
+ * bytes per row; copied to the GPU before the call returns. */
+int vss_background_set_image(vss_background* bg, const uint8_t* pixels, int height, int width, int channels,
+                             size_t row_stride);
+/* radius in 1..32, sigma > 0 (and large enough for one off-centre weight >= 1). */
+int vss_background_set_blur(vss_background* bg, int radius, double sigma);
+/* Back to a mode with the colour, image or blur it was last given (a user
+ * toggling between them: the image is not uploaded again).  A composite in
+ * image or blur mode that was never given an image or a blur fails with
+ * VSS_E_INVALID_ARG. */
+int vss_background_set_mode(vss_background* bg, int mode);
+
+/* The blur's weights w[0 .. 2*radius] (centre at w[radius]); host-only, no GPU
+ * needed.  With g_k = exp(-k^2 / (2 sigma^2)): w[k] = floor(65536 g_k / sum(g)
+ * + 0.5) off the centre, and the centre takes 65536 - the rest, so the table
+ * sums to 65536 exactly.  Where the rounding errors would leave the centre
+ * below its neighbours (wide sigmas: radius 32, sigma 40), the innermost tap
+ * pairs give one unit each to the centre, as few pairs as make the table
+ * non-increasing from the centre outwards.  VSS_E_INVALID_ARG for a radius outside 1..32, a sigma
+ * that is <= 0, NaN or infinite, or one so small that every off-centre weight
+ * rounds to 0 (the centre would not fit 16 bits). */
+int vss_blur_weights(int radius, double sigma, uint16_t* w);
+
+/* As vss_composite_device, over bg.  VSS_E_INVALID_ARG when bg belongs to
+ * another handle or is in image mode with no image set. */
+int vss_background_composite_device(vss_handle* h, vss_background* bg, const uint8_t* d_frames, int n, int height,
+                                    int width, int channels, size_t row_stride, size_t frame_stride,
+                                    const uint8_t* d_alpha_u8, uint8_t* d_out_rgba, size_t out_row_stride,
+                                    size_t out_frame_stride, void* stream);
+
+/* Host-memory convenience: seam + post chain + background compositing for n
+ * consecutive frames of the state's stream -> out_rgba [n][height][width][4]. */
+int vss_segment_background(vss_handle* h, vss_post_state* st, vss_background* bg, const uint8_t* frames, int n,
+                           int height, int width, int channels, size_t row_stride, uint8_t* out_rgba);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,132 @@
+#!/usr/bin/env python3
+"""Time the virtual-background kernels against the parent's k_composite.
+
+For 8 x 640x480 and 8 x 1080p RGB frames resident in HBM: the HIP-event median
+per call of vss_composite_device (the yardstick) and of
+vss_background_composite_device in colour, image and blur mode, the calls of
+the four interleaved round by round so that drift hits all alike; the spread
+of the yardstick's per-round medians; each mode's algorithmic bytes and the
+share of 8 TB/s they imply at the measured time.  Prints one JSON line.
+
+    python tools/bench_background.py [--radius 7 --sigma 2.5 --rounds 5 --calls 8]
+
+Needs a GPU: there is no fall-back.
+"""
+import argparse
+import importlib.util
+import json
+import os
+import statistics
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG_DIR = os.path.join(ROOT, "video-stream-segmenetation_amd")
+HBM_BYTES_PER_S = 8e12
+
+
+def load_pkg():
+    spec = importlib.util.spec_from_file_location("vss_amd", os.path.join(PKG_DIR, "__init__.py"),
+                                                  submodule_search_locations=[PKG_DIR])
+    mod = importlib.util.module_from_spec(spec)
+    sys.modules["vss_amd"] = mod
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def algorithmic_bytes(mode, n, fh, fw, fc, H, W):
+    """Bytes each mode must move per call: every input read once, every output written once."""
+    px = n * fh * fw
+    alpha = n * H * W
+    base = px * (fc + 4) + alpha           # frame in, RGBA out, mask alpha
+    if mode in ("composite", "colour"):
+        return base
+    if mode == "image":
+        return base + px * 3               # the cached scaled image, RGB
+    return base + px * (fc + 4) + px * 4   # blur: the horizontal pass (frame in, RGBX out), RGBX back in
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--radius", type=int, default=7)
+    ap.add_argument("--sigma", type=float, default=2.5)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--calls", type=int, default=8, help="timed calls per mode and round")
+    ap.add_argument("--warmup", type=int, default=5)
+    a = ap.parse_args()
+    if a.rounds * a.calls < 20:
+        ap.error("at least 20 timed calls per mode (rounds * calls)")
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_background: no GPU")
+    pkg = load_pkg()
+    n, fc, H, W = 8, 3, 144, 256
+    rng = np.random.default_rng(0)
+    result = {"bench": "background", "n": n, "radius": a.radius, "sigma": a.sigma,
+              "timed_calls_per_mode": a.rounds * a.calls, "sizes": {}}
+    with pkg.Session(model_h=H, model_w=W, dtype="bf16x2", max_batch=n, autotune=False) as s:
+        # a stream of its own: handle 0 (the null stream) would send the calls to the session's stream,
+        # away from the events
+        st = torch.cuda.Stream()
+        stream = st.cuda_stream
+        for fh, fw in ((480, 640), (1080, 1920)):
+            df = torch.from_numpy(rng.integers(0, 256, (n, fh, fw, fc), dtype=np.uint8)).cuda()
+            da = torch.from_numpy(rng.integers(0, 256, (n, H, W), dtype=np.uint8)).cuda()
+            do = torch.empty((n, fh, fw, 4), dtype=torch.uint8, device="cuda")
+            bgs = {m: pkg.Background(s) for m in ("colour", "image", "blur")}
+            bgs["image"].set_image(rng.integers(0, 256, (720, 1280, 3), dtype=np.uint8))
+            bgs["blur"].set_blur(a.radius, a.sigma)
+            geo = (n, fh, fw, fc, fw * fc, fh * fw * fc)
+
+            def call(mode):
+                if mode == "composite":
+                    pkg.composite_device(s, df.data_ptr(), *geo, da.data_ptr(), do.data_ptr(), stream=stream)
+                else:
+                    pkg.background_composite_device(s, bgs[mode], df.data_ptr(), *geo, da.data_ptr(), do.data_ptr(),
+                                                    stream=stream)
+
+            modes = ("composite", "colour", "image", "blur")
+            for m in modes:
+                for _ in range(a.warmup):
+                    call(m)
+            torch.cuda.synchronize()
+            check = do.clone()  # blur ran last in the warm-up
+            times = {m: [[] for _ in range(a.rounds)] for m in modes}
+            for r in range(a.rounds):
+                pairs = []
+                for _ in range(a.calls):
+                    for m in modes:
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record(st)
+                        call(m)
+                        e1.record(st)
+                        pairs.append((m, e0, e1))
+                torch.cuda.synchronize()
+                for m, e0, e1 in pairs:
+                    times[m][r].append(e0.elapsed_time(e1) * 1e3)  # us
+            call("blur")
+            torch.cuda.synchronize()
+            if not torch.equal(check, do):
+                raise SystemExit("bench_background: the output changed between two runs of the same call")
+            out = {}
+            for m in modes:
+                flat = [t for rr in times[m] for t in rr]
+                med = statistics.median(flat)
+                by = algorithmic_bytes(m, n, fh, fw, fc, H, W)
+                rounds = [statistics.median(rr) for rr in times[m]]
+                out[m] = {"median_us": round(med, 2), "round_medians_us": [round(v, 2) for v in rounds],
+                          "bytes": by, "bytes_per_px": round(by / (n * fh * fw), 3),
+                          "hbm_fraction": round(by / (med * 1e-6) / HBM_BYTES_PER_S, 4)}
+            base = out["composite"]
+            base["spread"] = round(max(base["round_medians_us"]) / min(base["round_medians_us"]) - 1, 4)
+            for m in modes[1:]:
+                out[m]["ratio_to_composite"] = round(out[m]["median_us"] / base["median_us"], 3)
+            result["sizes"][f"{fw}x{fh}"] = out
+            for b in bgs.values():
+                b.close()
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()

@@ -173,6 +173,15 @@ def lib() -> ctypes.CDLL:
                 "vss_segment_post": ([P, P, P, I, I, I, I, S, P, P], I),
                 "vss_composite_device": ([P, P, I, I, I, I, S, S, P, P, S, S, P], I),
                 "vss_segment_composite": ([P, P, P, I, I, I, I, S, P], I),
+                "vss_background_create": ([P, ctypes.POINTER(P)], I),
+                "vss_background_destroy": ([P], None),
+                "vss_background_set_color": ([P, I, I, I], I),
+                "vss_background_set_image": ([P, P, I, I, I, S], I),
+                "vss_background_set_blur": ([P, I, ctypes.c_double], I),
+                "vss_background_set_mode": ([P, I], I),
+                "vss_blur_weights": ([I, ctypes.c_double, P], I),
+                "vss_background_composite_device": ([P, P, P, I, I, I, I, S, S, P, P, S, S, P], I),
+                "vss_segment_background": ([P, P, P, P, I, I, I, I, S, P], I),
             }
             for name, (args, res) in sig.items():
                 fn = getattr(L, name)
@@ -233,10 +242,11 @@ class Session:
         self._pending = []
         self._tickets = {}
         self._posts = []
+        self._backgrounds = []
 
     # -- lifecycle --------------------------------------------------------
     def close(self):
-        for p in getattr(self, "_posts", []):
+        for p in getattr(self, "_posts", []) + getattr(self, "_backgrounds", []):
             p.close()
         if getattr(self, "_h", None):
             lib().vss_destroy(self._h)
@@ -580,6 +590,17 @@ class PostChain:
                s._h)
         return out
 
+    def replace_background(self, frames: np.ndarray, bg: "Background") -> np.ndarray:
+        """Consecutive frames [N,H,W,3|4] u8 -> the person over `bg` (a colour, an image
+        or the blurred frame): opaque RGBA u8 [N,H,W,4], blended on the GPU."""
+        s = self.session
+        f = _as_frames(frames)
+        n, hh, ww, c = f.shape
+        out = np.empty((n, hh, ww, 4), np.uint8)
+        _check(lib().vss_segment_background(s._h, self._st, bg._bg, f.ctypes.data, n, hh, ww, c, ww * c,
+                                            out.ctypes.data), s._h)
+        return out
+
     def set_faces(self, faces):
         """The face inputs (a list of FaceFrame, one per frame) of the NEXT call."""
         arr = (FaceFrame * len(faces))(*faces)
@@ -603,6 +624,67 @@ def composite_device(session: Session, frames_ptr: int, n: int, h: int, w: int, 
     ors = out_row_stride or w * 4
     _check(lib().vss_composite_device(session._h, frames_ptr, n, h, w, c, row_stride, frame_stride, alpha_u8_ptr,
                                       out_ptr, ors, out_frame_stride or ors * h, stream or None), session._h)
+
+
+VSS_BG_COLOR, VSS_BG_IMAGE, VSS_BG_BLUR = 0, 1, 2
+
+
+class Background:
+    """What goes behind the person (include/vss.h, virtual backgrounds): a solid
+    colour (u2FrameProc.ts:78-148; (32, 32, 32) until set), an image drawn to the
+    frame size (customization.ts:41) or the blurred frame.  Each setter selects
+    its mode and takes effect from the next composite call."""
+
+    def __init__(self, session: Session):
+        self.session = session
+        bg = ctypes.c_void_p()
+        _check(lib().vss_background_create(session._h, ctypes.byref(bg)), session._h)
+        self._bg = bg
+        session._backgrounds.append(self)
+
+    def close(self):
+        if getattr(self, "_bg", None):
+            lib().vss_background_destroy(self._bg)
+            self._bg = None
+
+    def set_color(self, r: int, g: int, b: int):
+        _check(lib().vss_background_set_color(self._bg, int(r), int(g), int(b)), self.session._h)
+
+    def set_image(self, image: np.ndarray):
+        """image [h,w,3|4] uint8; rows may be strided (a view of a wider array)."""
+        a = np.asarray(image)
+        if a.dtype != np.uint8 or a.ndim != 3:
+            raise VssError(VSS_E_INVALID_ARG, "image must be uint8 [h,w,3|4]")
+        hh, ww, c = a.shape
+        if a.size and (a.strides[2] != 1 or a.strides[1] != c or a.strides[0] < ww * c):
+            a = np.ascontiguousarray(a)
+        _check(lib().vss_background_set_image(self._bg, a.ctypes.data, hh, ww, c, a.strides[0] if a.size else 0),
+               self.session._h)
+
+    def set_blur(self, radius: int, sigma: float):
+        _check(lib().vss_background_set_blur(self._bg, int(radius), float(sigma)), self.session._h)
+
+    def set_mode(self, mode: int):
+        """Back to VSS_BG_COLOR / _IMAGE / _BLUR with what that mode was last given."""
+        _check(lib().vss_background_set_mode(self._bg, int(mode)), self.session._h)
+
+
+def background_composite_device(session: Session, bg: Background, frames_ptr: int, n: int, h: int, w: int, c: int,
+                                row_stride: int, frame_stride: int, alpha_u8_ptr: int, out_ptr: int,
+                                out_row_stride: int = 0, out_frame_stride: int = 0, stream: int = 0):
+    """HBM in/out: frames + mask alpha bytes -> opaque RGBA frames, the person over `bg`."""
+    ors = out_row_stride or w * 4
+    _check(lib().vss_background_composite_device(session._h, bg._bg, frames_ptr, n, h, w, c, row_stride,
+                                                 frame_stride, alpha_u8_ptr, out_ptr, ors,
+                                                 out_frame_stride or ors * h, stream or None), session._h)
+
+
+def blur_weights(radius: int, sigma: float) -> np.ndarray:
+    """The blur's 16-bit fixed-point taps, uint16 [2*radius+1] summing to 65536
+    (vss_blur_weights).  Host-only: no GPU needed."""
+    w = np.zeros(2 * max(int(radius), 0) + 1, np.uint16)
+    _check(lib().vss_blur_weights(int(radius), float(sigma), w.ctypes.data))
+    return w
 
 
 class _PinnedBlock:

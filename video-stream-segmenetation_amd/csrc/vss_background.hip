@@ -1,0 +1,202 @@
+// vss_background.hip — virtual backgrounds: the person over a solid colour, a
+// user image or the blurred frame, as one opaque RGBA frame.
+//
+// The reference shows the person over a colour (composeMatteOnCanvas,
+// client/src/core/u2FrameProc.ts:78-148) or over a background image drawn to
+// the canvas size (client/customization.ts:41).  Here, per colour channel,
+//   out = (fg*A + bg*(255-A) + 127) / 255        (integer division)
+// with A = k_composite's alpha (the half-pixel bilinear of the mask's u8 alpha,
+// rounded half up) and the output alpha byte 255; for a = A/255 this equals
+// composeMatteOnCanvas's Math.round((a*s/255 + (1-a)*b/255)*255) for all 256^3
+// (A, fg, bg) (tests/test_background_ref.py).
+//
+//   k_bg_resize          : the user image scaled to the frame size with the
+//                          alpha's half-pixel bilinear, per channel (once per
+//                          image and frame geometry).
+//   k_bg_composite<mode> : COLOR / IMAGE: k_composite's thread shape (4
+//                          consecutive pixels, one 16-B store) plus the blend.
+//   k_blur_h             : BLUR's horizontal pass, 16-bit fixed-point weights,
+//                          h = (sum w*p + 32768) >> 16, packed RGBX u8.
+//   k_bg_composite<BLUR> : the vertical pass over an LDS tile of k_blur_h's
+//                          output (radius halo rows above and below), fused
+//                          with the alpha upscale and the blend: the blurred
+//                          frame never goes to HBM.
+// Edges replicate.  The sums stay below 2^32 (65536 * 255 + 32768).
+#include <hip/hip_runtime.h>
+
+#include "vss_kernels.h"
+
+namespace vss {
+
+namespace {
+
+// 4 consecutive pixels x0.. of row y of frame t over bg[4] (r | g<<8 | b<<16)
+__device__ __forceinline__ void blend_quad(const CompositeParams& p, int t, int y, int x0, const uint32_t (&bg)[4]) {
+#pragma clang fp contract(off)
+  int ya, yb;
+  float ly;
+  up_coord(y, p.sy, p.H, ya, yb, ly);
+  const uint8_t* a = p.alpha + (long)t * p.H * p.W;
+  const uint8_t* ra = a + (long)ya * p.W;
+  const uint8_t* rb = a + (long)yb * p.W;
+  const uint8_t* f = p.frames + (long)t * p.frame_stride + (long)y * p.row_stride;
+  uint32_t px[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int x = min(x0 + k, p.fw - 1);
+    int xa, xb;
+    float lx;
+    up_coord(x, p.sx, p.W, xa, xb, lx);
+    const float a00 = ra[xa], a01 = ra[xb], a10 = rb[xa], a11 = rb[xb];
+    const float top = __builtin_fmaf(a01 - a00, lx, a00), bot = __builtin_fmaf(a11 - a10, lx, a10);
+    const uint32_t A = (uint32_t)floorf(__builtin_fmaf(bot - top, ly, top) + 0.5f);
+    const uint8_t* q = f + (long)x * p.fc;
+    uint32_t o = 0xFF000000u;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const uint32_t b = (bg[k] >> (8 * c)) & 255u;
+      o |= (((uint32_t)q[c] * A + b * (255u - A) + 127u) / 255u) << (8 * c);
+    }
+    px[k] = o;
+  }
+  uint8_t* o = p.out + (long)t * p.out_frame_stride + (long)y * p.out_row_stride + (long)x0 * 4;
+  if (x0 + 4 <= p.fw && (reinterpret_cast<uintptr_t>(o) & 15) == 0) {
+    *reinterpret_cast<uint4*>(o) = make_uint4(px[0], px[1], px[2], px[3]);
+  } else {
+    for (int k = 0; k < 4 && x0 + k < p.fw; ++k) reinterpret_cast<uint32_t*>(o)[k] = px[k];
+  }
+}
+
+constexpr int kBlurTW = 64, kBlurTH = 32;  // k_bg_composite<BLUR>'s tile: 16 x 16 threads, 4 x 2 pixels each
+
+}  // namespace
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_bg_composite(BgCompositeParams p) {
+  const CompositeParams& c = p.c;
+  const int t = blockIdx.z;
+  if constexpr (MODE != kBgBlur) {
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const int x0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
+    if (y >= c.fh || x0 >= c.fw) return;
+    uint32_t bg[4];
+    if constexpr (MODE == kBgColor) {
+      bg[0] = bg[1] = bg[2] = bg[3] = p.color;
+    } else {
+      // 4 RGB pixels = 3 dwords (rows padded to whole quads, bg_image_stride)
+      const uint32_t* q = reinterpret_cast<const uint32_t*>(p.image + (long)y * bg_image_stride(c.fw) + (long)x0 * 3);
+      const uint32_t d0 = q[0], d1 = q[1], d2 = q[2];
+      bg[0] = d0 & 0xFFFFFFu;
+      bg[1] = (d0 >> 24) | ((d1 & 0xFFFFu) << 8);
+      bg[2] = (d1 >> 16) | ((d2 & 0xFFu) << 16);
+      bg[3] = d2 >> 8;
+    }
+    blend_quad(c, t, y, x0, bg);
+  } else {
+    extern __shared__ __align__(16) uint32_t tile[];  // [kBlurTH + 2r][kBlurTW] RGBX, then the r + 1 weights
+    const int r = p.radius, rows = kBlurTH + 2 * r;
+    uint32_t* wl = tile + rows * kBlurTW;
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int X0 = blockIdx.x * kBlurTW, Y0 = blockIdx.y * kBlurTH;
+    const uint32_t* h = p.hblur + (long)t * c.fh * c.fw;
+    for (int i = tid; i < rows * kBlurTW; i += 256) {
+      const int yy = min(max(Y0 - r + i / kBlurTW, 0), c.fh - 1), xx = min(X0 + i % kBlurTW, c.fw - 1);
+      tile[i] = h[(long)yy * c.fw + xx];
+    }
+    if (tid <= r) wl[tid] = p.w[tid];
+    __syncthreads();
+    const int x0 = X0 + tx * 4;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int ly = ty + 16 * j, y = Y0 + ly;
+      if (y >= c.fh || x0 >= c.fw) continue;
+      uint32_t acc[4][3];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) acc[k][0] = acc[k][1] = acc[k][2] = 32768u;
+      for (int d = 0; d <= 2 * r; ++d) {
+        const uint4 v = *reinterpret_cast<const uint4*>(tile + (ly + d) * kBlurTW + tx * 4);
+        const uint32_t w = wl[d < r ? r - d : d - r];
+        const uint32_t q[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          acc[k][0] += w * (q[k] & 255u);
+          acc[k][1] += w * ((q[k] >> 8) & 255u);
+          acc[k][2] += w * ((q[k] >> 16) & 255u);
+        }
+      }
+      uint32_t bg[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) bg[k] = (acc[k][0] >> 16) | ((acc[k][1] >> 16) << 8) | ((acc[k][2] >> 16) << 16);
+      blend_quad(c, t, y, x0, bg);
+    }
+  }
+}
+
+// One workgroup = 256 consecutive pixels of one row; the row segment and its
+// radius halo (replicated at the frame's edges) packed RGBX in LDS.
+__global__ __launch_bounds__(256) void k_blur_h(BlurHParams p) {
+  __shared__ uint32_t row[256 + 2 * kBlurMaxRadius];
+  __shared__ uint32_t wl[kBlurMaxRadius + 1];
+  const int tid = threadIdx.x, r = p.radius;
+  const int X0 = blockIdx.x * 256, y = blockIdx.y, t = blockIdx.z;
+  const uint8_t* f = p.frames + (long)t * p.frame_stride + (long)y * p.row_stride;
+  for (int i = tid; i < 256 + 2 * r; i += 256) {
+    const uint8_t* q = f + (long)min(max(X0 - r + i, 0), p.fw - 1) * p.fc;
+    row[i] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
+  }
+  if (tid <= r) wl[tid] = p.w[tid];
+  __syncthreads();
+  const int x = X0 + tid;
+  if (x >= p.fw) return;
+  uint32_t a0 = 32768u, a1 = 32768u, a2 = 32768u;
+  for (int d = 0; d <= 2 * r; ++d) {
+    const uint32_t v = row[tid + d], w = wl[d < r ? r - d : d - r];
+    a0 += w * (v & 255u);
+    a1 += w * ((v >> 8) & 255u);
+    a2 += w * ((v >> 16) & 255u);
+  }
+  p.out[((long)t * p.fh + y) * p.fw + x] = (a0 >> 16) | ((a1 >> 16) << 8) | ((a2 >> 16) << 16);
+}
+
+// One thread per pixel of the scaled image (runs once per image and geometry).
+__global__ __launch_bounds__(256) void k_bg_resize(BgResizeParams p) {
+#pragma clang fp contract(off)
+  const int y = blockIdx.y * 4 + (threadIdx.x >> 6), x = blockIdx.x * 64 + (threadIdx.x & 63);
+  if (y >= p.fh || x >= p.fw) return;
+  int ya, yb, xa, xb;
+  float ly, lx;
+  up_coord(y, p.sy, p.sh, ya, yb, ly);
+  up_coord(x, p.sx, p.sw, xa, xb, lx);
+  const uint8_t* ra = p.src + (long)ya * p.sw * p.sc;
+  const uint8_t* rb = p.src + (long)yb * p.sw * p.sc;
+  uint8_t* o = p.out + (long)y * bg_image_stride(p.fw) + (long)x * 3;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float a00 = ra[xa * p.sc + c], a01 = ra[xb * p.sc + c], a10 = rb[xa * p.sc + c], a11 = rb[xb * p.sc + c];
+    const float top = __builtin_fmaf(a01 - a00, lx, a00), bot = __builtin_fmaf(a11 - a10, lx, a10);
+    o[c] = (uint8_t)floorf(__builtin_fmaf(bot - top, ly, top) + 0.5f);
+  }
+}
+
+void launch_bg_resize(const BgResizeParams& p, hipStream_t s) {
+  hipLaunchKernelGGL(k_bg_resize, dim3((p.fw + 63) / 64, (p.fh + 3) / 4), dim3(256), 0, s, p);
+}
+
+void launch_blur_h(const BlurHParams& p, int n, hipStream_t s) {
+  hipLaunchKernelGGL(k_blur_h, dim3((p.fw + 255) / 256, p.fh, n), dim3(256), 0, s, p);
+}
+
+void launch_bg_composite(const BgCompositeParams& p, int mode, int n, hipStream_t s) {
+  const dim3 grid((p.c.fw + 255) / 256, (p.c.fh + 3) / 4, n);
+  if (mode == kBgColor) {
+    hipLaunchKernelGGL(k_bg_composite<kBgColor>, grid, dim3(256), 0, s, p);
+  } else if (mode == kBgImage) {
+    hipLaunchKernelGGL(k_bg_composite<kBgImage>, grid, dim3(256), 0, s, p);
+  } else {
+    const size_t lds = ((size_t)(kBlurTH + 2 * p.radius) * kBlurTW + p.radius + 1) * 4;
+    hipLaunchKernelGGL(k_bg_composite<kBgBlur>, dim3((p.c.fw + kBlurTW - 1) / kBlurTW, (p.c.fh + kBlurTH - 1) / kBlurTH, n),
+                       dim3(256), lds, s, p);
+  }
+}
+
+}  // namespace vss

@@ -352,7 +352,8 @@ struct vss_handle {
 #ifdef VSS_TRACE
   std::vector<int> trace_wgs;              // workgroups of the layer's last launch
 #endif
-  uint8_t* d_comp = nullptr;      // vss_segment_composite output, allocated on first use
+  uint8_t* d_comp = nullptr;      // vss_segment_composite / _background output, allocated on first use
+  std::atomic<size_t> bg_bytes{0};  // device buffers of the handle's vss_background objects
   float* d_post_alpha = nullptr;  // vss_segment_post outputs [max_batch][P]
   uint8_t* d_post_u8 = nullptr;
   int use_graph = 1;
@@ -2149,7 +2150,7 @@ int vss_get_info(const vss_handle* h, vss_info* info) {
   info->mask_w = h->cfg.model_w;
   info->n_layers = (int)h->L.size();
   info->dtype = h->cfg.dtype;
-  info->device_bytes = h->dev_bytes;
+  info->device_bytes = h->dev_bytes + h->bg_bytes.load();
   for (const vss_handle* p : h->peers) info->device_bytes += p->dev_bytes;
   info->n_gpus = 1 + (int)h->peers.size();
   info->queue_depth = (int)h->slots.size();
@@ -3120,6 +3121,324 @@ int vss_segment_composite(vss_handle* h, vss_post_state* st, const uint8_t* fram
   if (!rc)
     rc = composite_enqueue(h, s.d_frames, n, height, width, channels, row_stride, fs, h->d_post_u8, h->d_comp, ors,
                            ofs, h->stream);
+  if (!rc) {
+    const hipError_t e = hipMemcpyAsync(out_rgba, h->d_comp, (size_t)n * ofs, hipMemcpyDeviceToHost, h->stream);
+    if (e != hipSuccess) rc = fail(h, VSS_E_HIP, std::string("D2H: ") + hipGetErrorString(e));
+  }
+  return finish_seam(h, lk, k, rc);
+}
+
+}  // extern "C"
+
+// ---- virtual backgrounds (vss_background.hip) --------------------------------
+struct vss_background {
+  vss_handle* h = nullptr;
+  std::mutex mu;                 // setters and composites of one object are serialised
+  int mode = VSS_BG_COLOR;
+  uint32_t color = 32u | (32u << 8) | (32u << 16);  // u2FrameProc.ts:89
+  uint8_t* d_src = nullptr;      // IMAGE: the user's image [sh][sw][sc], tight rows
+  int sh = 0, sw = 0, sc = 0;
+  size_t src_bytes = 0;
+  uint8_t* d_img = nullptr;      // IMAGE: d_src scaled to img_fh x img_fw (0: not built)
+  int img_fh = 0, img_fw = 0;
+  size_t img_bytes = 0;
+  uint32_t* d_hblur = nullptr;   // BLUR: the horizontal pass's output, grown on demand
+  size_t hblur_bytes = 0;
+  int radius = 0;
+  uint16_t w[kBlurMaxRadius + 1] = {};  // taps 0 (centre) .. radius
+  hipEvent_t last = nullptr;     // recorded after every composite
+  hipStream_t last_stream = nullptr;
+  bool used = false;
+};
+
+namespace {
+
+// w[0..2r]: 16-bit fixed-point Gaussian taps that sum to 65536 exactly
+int blur_weights(int radius, double sigma, uint16_t* w, std::string* why) {
+  if (radius < 1 || radius > kBlurMaxRadius) {
+    *why = "blur radius must be in [1, 32]";
+    return VSS_E_INVALID_ARG;
+  }
+  if (!(sigma > 0.0) || std::isinf(sigma)) {
+    *why = "blur sigma must be a finite number > 0";
+    return VSS_E_INVALID_ARG;
+  }
+  double g[2 * kBlurMaxRadius + 1], sum = 0.0;
+  for (int k = -radius; k <= radius; ++k) sum += g[k + radius] = std::exp(-(double)(k * k) / (2.0 * sigma * sigma));
+  long rest = 0;
+  for (int k = 0; k <= 2 * radius; ++k) {
+    if (k == radius) continue;
+    const long v = (long)std::floor(65536.0 * g[k] / sum + 0.5);
+    w[k] = (uint16_t)v;
+    rest += v;
+  }
+  if (rest == 0) {  // the centre tap would be 65536: no u16, and no blur
+    *why = "blur sigma too small: every off-centre 16-bit weight rounds to 0";
+    return VSS_E_INVALID_ARG;
+  }
+  // The centre takes what the rounded taps leave.  With a wide sigma the 2r
+  // rounding errors can add up to more than the table's own slope at the
+  // centre (radius 32, sigma 40: 1116 left between two taps of 1120), and the
+  // kernel would dip at its peak.  Then the m innermost tap pairs give one
+  // unit each to the centre, m the smallest count that leaves the table
+  // non-increasing from the centre outwards; no tap moves by more than 1.
+  long centre = 65536 - rest;
+  if (centre < w[radius + 1]) {
+    const long first = w[radius + 1];
+    int m = 0;
+    for (int k = 1; k <= radius && !m; ++k)
+      if (centre + 2 * k >= first - 1 && (k == radius || w[radius + k] - 1 >= w[radius + k + 1])) m = k;
+    for (int k = 1; k <= m; ++k) {
+      --w[radius + k];
+      --w[radius - k];
+    }
+    centre += 2 * m;
+  }
+  w[radius] = (uint16_t)centre;
+  return VSS_OK;
+}
+
+// the device buffers of a background count into vss_info.device_bytes
+template <class T>
+int bg_alloc(vss_background* bg, T** p, size_t* have, size_t bytes) {
+  vss_handle* h = bg->h;
+  if (*p) {
+    (void)hipFree(*p);
+    h->bg_bytes -= *have;
+    *p = nullptr;
+    *have = 0;
+  }
+  if (!bytes) return VSS_OK;
+  void* q = nullptr;
+  if (hipMalloc(&q, bytes) != hipSuccess) return fail(h, VSS_E_OOM, "hipMalloc(" + std::to_string(bytes) + ") failed");
+  *p = static_cast<T*>(q);
+  *have = bytes;
+  h->bg_bytes += bytes;
+  return VSS_OK;
+}
+
+// before a device buffer of bg is freed or overwritten: its latest composite has ended
+int bg_quiesce(vss_background* bg) {
+  HIP_TRY(bg->h, hipSetDevice(bg->h->device));
+  if (bg->used) HIP_TRY(bg->h, hipEventSynchronize(bg->last));
+  return VSS_OK;
+}
+
+// bg->mu held
+int bg_enqueue(vss_handle* h, vss_background* bg, const uint8_t* d_frames, int n, int fh, int fw, int fc, size_t rs,
+               size_t fs, const uint8_t* d_alpha, uint8_t* d_out, size_t ors, size_t ofs, hipStream_t s) {
+  if (bg->mode == VSS_BG_IMAGE && !bg->d_src)
+    return fail(h, VSS_E_INVALID_ARG, "background is in image mode but no image was set");
+  if (bg->mode == VSS_BG_BLUR && !bg->radius)
+    return fail(h, VSS_E_INVALID_ARG, "background is in blur mode but no blur was set");
+  // the previous composite (and the image it may have scaled) ran on another stream
+  if (bg->used && bg->last_stream != s) HIP_TRY(h, hipStreamWaitEvent(s, bg->last, 0));
+  BgCompositeParams p{};
+  p.c.frames = d_frames;
+  p.c.row_stride = (long)rs;
+  p.c.frame_stride = (long)fs;
+  p.c.fh = fh; p.c.fw = fw; p.c.fc = fc;
+  p.c.alpha = d_alpha;
+  p.c.H = h->cfg.model_h; p.c.W = h->cfg.model_w;
+  p.c.sy = (float)p.c.H / (float)fh;
+  p.c.sx = (float)p.c.W / (float)fw;
+  p.c.out = d_out;
+  p.c.out_row_stride = (long)ors;
+  p.c.out_frame_stride = (long)ofs;
+  p.color = bg->color;
+  if (bg->mode == VSS_BG_IMAGE) {
+    if (bg->img_fh != fh || bg->img_fw != fw) {  // (re)build the cached scaled image
+      const size_t need = (size_t)bg_image_stride(fw) * fh;
+      if (need > bg->img_bytes) {
+        int rc = bg_quiesce(bg);
+        if (!rc) rc = bg_alloc(bg, &bg->d_img, &bg->img_bytes, need);
+        if (rc) return rc;
+      }
+      BgResizeParams r{};
+      r.src = bg->d_src;
+      r.sh = bg->sh; r.sw = bg->sw; r.sc = bg->sc;
+      r.sy = (float)bg->sh / (float)fh;
+      r.sx = (float)bg->sw / (float)fw;
+      r.out = bg->d_img;
+      r.fh = fh; r.fw = fw;
+      launch_bg_resize(r, s);
+      bg->img_fh = fh;
+      bg->img_fw = fw;
+    }
+    p.image = bg->d_img;
+  } else if (bg->mode == VSS_BG_BLUR) {
+    const size_t need = (size_t)n * fh * fw * 4;
+    if (need > bg->hblur_bytes) {
+      int rc = bg_quiesce(bg);
+      if (!rc) rc = bg_alloc(bg, &bg->d_hblur, &bg->hblur_bytes, need);
+      if (rc) return rc;
+    }
+    BlurHParams b{};
+    b.frames = d_frames;
+    b.row_stride = (long)rs;
+    b.frame_stride = (long)fs;
+    b.fh = fh; b.fw = fw; b.fc = fc;
+    b.out = bg->d_hblur;
+    b.radius = bg->radius;
+    std::copy(bg->w, bg->w + kBlurMaxRadius + 1, b.w);
+    launch_blur_h(b, n, s);
+    p.hblur = bg->d_hblur;
+    p.radius = bg->radius;
+    std::copy(bg->w, bg->w + kBlurMaxRadius + 1, p.w);
+  }
+  launch_bg_composite(p, bg->mode, n, s);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, VSS_E_HIP, std::string("background launch: ") + hipGetErrorString(e));
+  HIP_TRY(h, hipEventRecord(bg->last, s));
+  bg->last_stream = s;
+  bg->used = true;
+  return VSS_OK;
+}
+
+}  // namespace
+
+static_assert(VSS_BG_COLOR == kBgColor && VSS_BG_IMAGE == kBgImage && VSS_BG_BLUR == kBgBlur, "modes mirror vss.h");
+
+extern "C" {
+
+int vss_blur_weights(int radius, double sigma, uint16_t* w) {
+  if (!w) return fail(nullptr, VSS_E_INVALID_ARG, "null weights");
+  std::string why;
+  const int rc = blur_weights(radius, sigma, w, &why);
+  return rc ? fail(nullptr, rc, why) : VSS_OK;
+}
+
+int vss_background_create(vss_handle* h, vss_background** out) {
+  if (!h || !out) return fail(h, VSS_E_INVALID_ARG, "null handle/out");
+  *out = nullptr;
+  HIP_TRY(h, hipSetDevice(h->device));
+  vss_background* bg = new vss_background();
+  bg->h = h;
+  const hipError_t e = hipEventCreateWithFlags(&bg->last, hipEventDisableTiming);
+  if (e != hipSuccess) {
+    delete bg;
+    return fail(h, VSS_E_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
+  }
+  *out = bg;
+  return VSS_OK;
+}
+
+void vss_background_destroy(vss_background* bg) {
+  if (!bg) return;
+  (void)bg_quiesce(bg);
+  (void)bg_alloc(bg, &bg->d_src, &bg->src_bytes, 0);
+  (void)bg_alloc(bg, &bg->d_img, &bg->img_bytes, 0);
+  (void)bg_alloc(bg, &bg->d_hblur, &bg->hblur_bytes, 0);
+  if (bg->last) (void)hipEventDestroy(bg->last);
+  delete bg;
+}
+
+int vss_background_set_color(vss_background* bg, int r, int g, int b) {
+  if (!bg) return fail(nullptr, VSS_E_INVALID_ARG, "null background");
+  if (r < 0 || r > 255 || g < 0 || g > 255 || b < 0 || b > 255)
+    return fail(bg->h, VSS_E_INVALID_ARG, "colour components must be in [0, 255]");
+  std::lock_guard<std::mutex> lk(bg->mu);
+  bg->color = (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16);
+  bg->mode = VSS_BG_COLOR;
+  return VSS_OK;
+}
+
+int vss_background_set_image(vss_background* bg, const uint8_t* pixels, int height, int width, int channels,
+                             size_t row_stride) {
+  if (!bg) return fail(nullptr, VSS_E_INVALID_ARG, "null background");
+  vss_handle* h = bg->h;
+  if (!pixels) return fail(h, VSS_E_INVALID_ARG, "null image");
+  if (height < 1 || width < 1) return fail(h, VSS_E_INVALID_ARG, "bad image size");
+  if (channels != 3 && channels != 4) return fail(h, VSS_E_INVALID_ARG, "image channels must be 3 or 4");
+  if (row_stride < (size_t)width * channels) return fail(h, VSS_E_INVALID_ARG, "row_stride < width*channels");
+  std::lock_guard<std::mutex> lk(bg->mu);
+  int rc = bg_quiesce(bg);  // a composite may still read the old image
+  if (rc) return rc;
+  const size_t rb = (size_t)width * channels;
+  if ((rc = bg_alloc(bg, &bg->d_src, &bg->src_bytes, rb * height))) {
+    bg->sh = bg->sw = bg->sc = 0;
+    return rc;
+  }
+  bg->img_fh = bg->img_fw = 0;  // the scaled copy is rebuilt by the next composite
+  const hipError_t e = hipMemcpy2D(bg->d_src, rb, pixels, row_stride, rb, height, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)bg_alloc(bg, &bg->d_src, &bg->src_bytes, 0);
+    return fail(h, VSS_E_HIP, std::string("image upload: ") + hipGetErrorString(e));
+  }
+  bg->sh = height; bg->sw = width; bg->sc = channels;
+  bg->mode = VSS_BG_IMAGE;
+  return VSS_OK;
+}
+
+int vss_background_set_mode(vss_background* bg, int mode) {
+  if (!bg) return fail(nullptr, VSS_E_INVALID_ARG, "null background");
+  if (mode != VSS_BG_COLOR && mode != VSS_BG_IMAGE && mode != VSS_BG_BLUR)
+    return fail(bg->h, VSS_E_INVALID_ARG, "mode must be VSS_BG_COLOR, VSS_BG_IMAGE or VSS_BG_BLUR");
+  std::lock_guard<std::mutex> lk(bg->mu);
+  bg->mode = mode;
+  return VSS_OK;
+}
+
+int vss_background_set_blur(vss_background* bg, int radius, double sigma) {
+  if (!bg) return fail(nullptr, VSS_E_INVALID_ARG, "null background");
+  uint16_t w[2 * kBlurMaxRadius + 1];
+  std::string why;
+  const int rc = blur_weights(radius, sigma, w, &why);
+  if (rc) return fail(bg->h, rc, why);
+  std::lock_guard<std::mutex> lk(bg->mu);
+  for (int k = 0; k <= radius; ++k) bg->w[k] = w[radius + k];
+  bg->radius = radius;
+  bg->mode = VSS_BG_BLUR;
+  return VSS_OK;
+}
+
+int vss_background_composite_device(vss_handle* h, vss_background* bg, const uint8_t* d_frames, int n, int height,
+                                    int width, int channels, size_t row_stride, size_t frame_stride,
+                                    const uint8_t* d_alpha_u8, uint8_t* d_out_rgba, size_t out_row_stride,
+                                    size_t out_frame_stride, void* stream) {
+  if (!h) return fail(nullptr, VSS_E_INVALID_ARG, "null handle");
+  if (!bg || bg->h != h) return fail(h, VSS_E_INVALID_ARG, "handle / background mismatch");
+  if (!d_frames || !d_alpha_u8 || !d_out_rgba) return fail(h, VSS_E_INVALID_ARG, "null device pointer");
+  int rc = check_frames(h, n, height, width, channels, row_stride, frame_stride,
+                        std::max(h->cfg.max_batch, h->user_max_batch));
+  if (rc) return rc;
+  if (out_row_stride < (size_t)width * 4 || out_row_stride % 4 || out_frame_stride < out_row_stride * height ||
+      (reinterpret_cast<uintptr_t>(d_out_rgba) & 3))
+    return fail(h, VSS_E_INVALID_ARG, "bad RGBA output geometry (row stride >= 4*width, multiple of 4)");
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  std::lock_guard<std::mutex> lk(bg->mu);
+  return bg_enqueue(h, bg, d_frames, n, height, width, channels, row_stride, frame_stride, d_alpha_u8, d_out_rgba,
+                    out_row_stride, out_frame_stride, s);
+}
+
+int vss_segment_background(vss_handle* h, vss_post_state* st, vss_background* bg, const uint8_t* frames, int n,
+                           int height, int width, int channels, size_t row_stride, uint8_t* out_rgba) {
+  if (!h || !st || st->h != h) return fail(h, VSS_E_INVALID_ARG, "handle / post state mismatch");
+  if (!bg || bg->h != h) return fail(h, VSS_E_INVALID_ARG, "handle / background mismatch");
+  if (!out_rgba) return fail(h, VSS_E_INVALID_ARG, "null output");
+  std::lock_guard<std::mutex> pl(h->post_mu);
+  std::unique_lock<std::mutex> lk(h->mu);
+  HIP_TRY(h, hipSetDevice(h->device));
+  const size_t cap = (size_t)h->cfg.max_batch * h->cfg.max_frame_h * h->cfg.max_frame_w * 4;
+  if (!h->d_comp) {
+    int rc = dalloc(h, &h->d_comp, cap);
+    if (rc) return rc;
+  }
+  const size_t fs = row_stride * (size_t)height, ors = (size_t)width * 4, ofs = ors * height;
+  if ((size_t)n * ofs > cap)
+    return fail(h, VSS_E_INVALID_ARG, "RGBA output exceeds the handle's capacity (max_batch, max_frame_h/w)");
+  int k = 0;
+  int rc = seam_on_stream(h, lk, frames, n, height, width, channels, row_stride, &k);
+  if (rc) return rc;
+  Slot& s = h->slots[k];
+  rc = post_enqueue(st, s.d_frames, n, height, width, channels, row_stride, fs, s.d_masks, nullptr, h->d_post_u8,
+                    h->stream);
+  if (!rc) {
+    std::lock_guard<std::mutex> bl(bg->mu);
+    rc = bg_enqueue(h, bg, s.d_frames, n, height, width, channels, row_stride, fs, h->d_post_u8, h->d_comp, ors, ofs,
+                    h->stream);
+  }
   if (!rc) {
     const hipError_t e = hipMemcpyAsync(out_rgba, h->d_comp, (size_t)n * ofs, hipMemcpyDeviceToHost, h->stream);
     if (e != hipSuccess) rc = fail(h, VSS_E_HIP, std::string("D2H: ") + hipGetErrorString(e));

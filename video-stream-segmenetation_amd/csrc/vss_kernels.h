@@ -488,6 +488,19 @@ struct PostFilterParams {
   uint8_t* alpha_u8;     // [n][H][W] (may be null)
 };
 
+// Source taps of output index o of the half-pixel bilinear (scale = in / out):
+// shared by the compositing alpha, the frame-resolution masks and the
+// background image's scaling (vss_post.hip, vss_background.hip).
+__device__ __forceinline__ void up_coord(int o, float scale, int in, int& i0, int& i1, float& l) {
+#pragma clang fp contract(off)
+  float s = ((float)o + 0.5f) * scale - 0.5f;
+  s = fmaxf(s, 0.f);
+  const int a = min((int)s, in - 1);
+  i0 = a;
+  i1 = a < in - 1 ? a + 1 : a;
+  l = s - (float)a;
+}
+
 // §8(f) row 3: destination-in compositing of the frame by the upscaled mask alpha
 struct CompositeParams {
   const uint8_t* frames;  // [n] frames, row_stride / frame_stride bytes, fc = 3 or 4
@@ -511,6 +524,43 @@ struct UpmaskParams {
   int fh, fw;
 };
 void launch_upmask(const UpmaskParams& p, int n, hipStream_t s);
+
+// Virtual backgrounds (vss_background.hip): the frame over a background by the
+// upscaled mask alpha, out = (fg*A + bg*(255-A) + 127) / 255 per channel, alpha
+// byte 255.  mode = VSS_BG_COLOR / _IMAGE / _BLUR (include/vss.h).
+constexpr int kBgColor = 0, kBgImage = 1, kBgBlur = 2;
+constexpr int kBlurMaxRadius = 32;
+// the cached scaled image: RGB, 3 B per pixel, rows padded so that every
+// thread's 4 pixels are 3 whole dwords
+__host__ __device__ constexpr long bg_image_stride(int fw) { return (long)((fw + 3) / 4) * 12; }
+struct BgCompositeParams {
+  CompositeParams c;       // frames, alpha, output: as k_composite
+  uint32_t color;          // COLOR: r | g << 8 | b << 16
+  const uint8_t* image;    // IMAGE: [fh][bg_image_stride(fw)] RGB at frame size
+  const uint32_t* hblur;   // BLUR: [n][fh][fw] RGBX, the horizontal pass
+  int radius;              // BLUR
+  uint16_t w[kBlurMaxRadius + 1];  // BLUR: taps 0 (centre) .. radius, 16-bit fixed point
+};
+void launch_bg_composite(const BgCompositeParams& p, int mode, int n, hipStream_t s);
+
+struct BlurHParams {
+  const uint8_t* frames;   // [n] frames, row_stride / frame_stride bytes, fc = 3 or 4
+  long row_stride, frame_stride;
+  int fh, fw, fc;
+  uint32_t* out;           // [n][fh][fw] RGBX
+  int radius;
+  uint16_t w[kBlurMaxRadius + 1];
+};
+void launch_blur_h(const BlurHParams& p, int n, hipStream_t s);
+
+struct BgResizeParams {
+  const uint8_t* src;      // [sh][sw][sc] u8, tight rows, sc = 3 or 4 (alpha dropped)
+  int sh, sw, sc;
+  float sy, sx;            // (float)sh / fh, (float)sw / fw
+  uint8_t* out;            // [fh][bg_image_stride(fw)] RGB
+  int fh, fw;
+};
+void launch_bg_resize(const BgResizeParams& p, hipStream_t s);
 
 // Queued host path: only the frame rows the resize reads, pinned host -> HBM
 // (vss_stage.hip).  rows: device list of the row indices; src / dst = frame 0.

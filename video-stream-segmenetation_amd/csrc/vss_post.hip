@@ -338,17 +338,8 @@ __global__ __launch_bounds__(256) void k_post_filter(PostFilterParams p) {
 // bilinear of the mask's u8 alpha at frame resolution, rounded half up; colour
 // 0 where alpha is 0 (a canvas stores premultiplied colour).  Thread = 4
 // consecutive pixels of a row: one 16-B RGBA store; the alpha taps come from
-// the L2-resident mask.  A tile of 256 x 4 pixels per workgroup.
-__device__ __forceinline__ void up_coord(int o, float scale, int in, int& i0, int& i1, float& l) {
-#pragma clang fp contract(off)
-  float s = ((float)o + 0.5f) * scale - 0.5f;
-  s = fmaxf(s, 0.f);
-  const int a = min((int)s, in - 1);
-  i0 = a;
-  i1 = a < in - 1 ? a + 1 : a;
-  l = s - (float)a;
-}
-
+// the L2-resident mask (up_coord: vss_kernels.h).  A tile of 256 x 4 pixels
+// per workgroup.
 __global__ __launch_bounds__(256) void k_composite(CompositeParams p) {
 #pragma clang fp contract(off)
   const int t = blockIdx.z;

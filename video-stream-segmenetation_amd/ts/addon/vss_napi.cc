@@ -35,6 +35,13 @@
 //       -> Promise<{alpha: Float32Array, alphaU8: Uint8Array}>   (processFrame :78-169)
 //   segmentComposite(handle, post, frames, n, height, width, channels, rowStride)
 //       -> Promise<Uint8Array>   RGBA output canvases, n * height * width * 4 (:78-178)
+//   backgroundCreate(handle) -> background   what goes behind the person (include/vss.h, virtual
+//       backgrounds); the colour (32, 32, 32) until a setter is called (u2FrameProc.ts:89)
+//   backgroundSetColor(background, r, g, b)
+//   backgroundSetImage(background, pixels: Uint8Array, height, width, channels, rowStride)
+//   backgroundSetBlur(background, radius, sigma), backgroundDestroy(background)
+//   segmentBackground(handle, post, frames, n, height, width, channels, rowStride, background)
+//       -> Promise<Uint8Array>   opaque RGBA frames, the person over the background
 //   ortCreate(modelBytes: Uint8Array, inputDims: number[] | null, deviceId, convPrecision) -> session
 //       ONNX sessions (include/vso.h) behind InferenceSession.create (model.ts:14, :38, :61)
 //   ortInfo(session) -> {inputNames, outputNames, inputShapes, outputShapes}
@@ -89,12 +96,14 @@ namespace {
 std::atomic<bool> g_env_closing{false};
 
 struct Post;
+struct Bg;
 struct Submitter;
 
 struct Handle {
   vss_handle* h = nullptr;
   int mask_h = 0, mask_w = 0;
   std::vector<Post*> posts;  // destroyed before the handle, whatever order the GC finalizes in
+  std::vector<Bg*> bgs;      // the same for the backgrounds
   // Queued batches whose libuv work still holds h (JS thread only): destroy()
   // or the GC finalizer while some are pending defers vss_destroy to the last
   // one's completion, so no worker ever waits on a destroyed handle.
@@ -111,6 +120,11 @@ struct Post {
   vss_post_state* st = nullptr;
 };
 
+struct Bg {
+  Handle* hd = nullptr;
+  vss_background* bg = nullptr;
+};
+
 void release_handle(Handle* hd) {
   hd->closing = true;
   if (hd->pending > 0) return;  // work_done() of the last queued batch finishes the release
@@ -120,6 +134,12 @@ void release_handle(Handle* hd) {
     p->hd = nullptr;
   }
   hd->posts.clear();
+  for (Bg* b : hd->bgs) {
+    if (b->bg) vss_background_destroy(b->bg);
+    b->bg = nullptr;
+    b->hd = nullptr;
+  }
+  hd->bgs.clear();
   stop_submitter(hd);
   if (hd->h) vss_destroy(hd->h);
   hd->h = nullptr;
@@ -151,6 +171,19 @@ void finalize_post(napi_env, void* data, void*) {
   Post* p = static_cast<Post*>(data);
   release_post(p);
   delete p;
+}
+
+void release_bg(Bg* b) {
+  if (b->bg) vss_background_destroy(b->bg);
+  b->bg = nullptr;
+  if (b->hd) b->hd->bgs.erase(std::remove(b->hd->bgs.begin(), b->hd->bgs.end(), b), b->hd->bgs.end());
+  b->hd = nullptr;
+}
+
+void finalize_bg(napi_env, void* data, void*) {
+  Bg* b = static_cast<Bg*>(data);
+  release_bg(b);
+  delete b;
 }
 
 Handle* get_handle(napi_env env, napi_value v) {
@@ -461,6 +494,110 @@ napi_value PostDestroy(napi_env env, napi_callback_info info) {
   NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
   void* p = nullptr;
   if (argc >= 1 && napi_get_value_external(env, argv[0], &p) == napi_ok && p) release_post(static_cast<Post*>(p));
+  return nullptr;
+}
+
+// ---- virtual backgrounds -------------------------------------------------------
+Bg* get_bg(napi_env env, napi_value v) {
+  void* p = nullptr;
+  if (napi_get_value_external(env, v, &p) != napi_ok || !p) {
+    napi_throw_type_error(env, nullptr, "expected a vss background");
+    return nullptr;
+  }
+  Bg* b = static_cast<Bg*>(p);
+  if (!b->bg) {
+    napi_throw_error(env, nullptr, "vss background already destroyed");
+    return nullptr;
+  }
+  return b;
+}
+
+napi_value BackgroundCreate(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Handle* hd = argc >= 1 ? get_handle(env, argv[0]) : nullptr;
+  if (!hd) return nullptr;
+  vss_background* bg = nullptr;
+  const int rc = vss_background_create(hd->h, &bg);
+  if (rc != VSS_OK) {
+    throw_vss(env, "vss_background_create", rc, vss_last_error(hd->h));
+    return nullptr;
+  }
+  Bg* b = new Bg();
+  b->hd = hd;
+  b->bg = bg;
+  hd->bgs.push_back(b);
+  napi_value ext;
+  NAPI_OK(env, napi_create_external(env, b, finalize_bg, nullptr, &ext));
+  return ext;
+}
+
+napi_value BackgroundSetColor(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Bg* b = argc >= 4 ? get_bg(env, argv[0]) : nullptr;
+  if (!b) return nullptr;
+  int c[3] = {-1, -1, -1};
+  for (int k = 0; k < 3; ++k) napi_get_value_int32(env, argv[1 + k], &c[k]);
+  const int rc = vss_background_set_color(b->bg, c[0], c[1], c[2]);
+  if (rc != VSS_OK) throw_vss(env, "vss_background_set_color", rc, vss_last_error(b->hd->h));
+  return nullptr;
+}
+
+napi_value BackgroundSetImage(napi_env env, napi_callback_info info) {
+  size_t argc = 6;
+  napi_value argv[6];
+  NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Bg* b = argc >= 6 ? get_bg(env, argv[0]) : nullptr;
+  if (!b) return nullptr;
+  bool is_ta = false;
+  napi_is_typedarray(env, argv[1], &is_ta);
+  napi_typedarray_type tt = napi_int8_array;
+  size_t len = 0, off = 0;
+  void* data = nullptr;
+  napi_value buf;
+  if (is_ta) NAPI_OK(env, napi_get_typedarray_info(env, argv[1], &tt, &len, &data, &buf, &off));
+  if (!is_ta || (tt != napi_uint8_array && tt != napi_uint8_clamped_array)) {
+    napi_throw_type_error(env, nullptr, "pixels must be a Uint8Array or Uint8ClampedArray");
+    return nullptr;
+  }
+  int h = 0, w = 0, c = 0, rs = 0;
+  napi_get_value_int32(env, argv[2], &h);
+  napi_get_value_int32(env, argv[3], &w);
+  napi_get_value_int32(env, argv[4], &c);
+  napi_get_value_int32(env, argv[5], &rs);
+  if (h < 1 || rs < 1 || len < (size_t)h * (size_t)rs) {
+    napi_throw_range_error(env, nullptr, "pixels buffer smaller than height * rowStride");
+    return nullptr;
+  }
+  const int rc = vss_background_set_image(b->bg, static_cast<const uint8_t*>(data), h, w, c, (size_t)rs);
+  if (rc != VSS_OK) throw_vss(env, "vss_background_set_image", rc, vss_last_error(b->hd->h));
+  return nullptr;
+}
+
+napi_value BackgroundSetBlur(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Bg* b = argc >= 3 ? get_bg(env, argv[0]) : nullptr;
+  if (!b) return nullptr;
+  int radius = 0;
+  double sigma = 0.0;
+  napi_get_value_int32(env, argv[1], &radius);
+  napi_get_value_double(env, argv[2], &sigma);
+  const int rc = vss_background_set_blur(b->bg, radius, sigma);
+  if (rc != VSS_OK) throw_vss(env, "vss_background_set_blur", rc, vss_last_error(b->hd->h));
+  return nullptr;
+}
+
+napi_value BackgroundDestroy(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  void* p = nullptr;
+  if (argc >= 1 && napi_get_value_external(env, argv[0], &p) == napi_ok && p) release_bg(static_cast<Bg*>(p));
   return nullptr;
 }
 
@@ -1076,6 +1213,7 @@ struct SegmentWork {
   vss_handle* h = nullptr;
   vss_post_state* post = nullptr;        // segmentPost / segmentComposite
   bool composite = false;                // segmentComposite: out_u8 holds the RGBA canvases
+  vss_background* bg = nullptr;          // segmentBackground: ... composited over this
   const uint8_t* frames = nullptr;
   float* out = nullptr;
   uint8_t* out_u8 = nullptr;
@@ -1087,7 +1225,10 @@ struct SegmentWork {
 
 void SegmentExecute(napi_env, void* data) {  // libuv worker thread: no JS calls here
   SegmentWork* w = static_cast<SegmentWork*>(data);
-  if (w->composite)
+  if (w->bg)
+    w->rc = vss_segment_background(w->h, w->post, w->bg, w->frames, w->n, w->height, w->width, w->channels,
+                                   w->row_stride, w->out_u8);
+  else if (w->composite)
     w->rc = vss_segment_composite(w->h, w->post, w->frames, w->n, w->height, w->width, w->channels, w->row_stride,
                                   w->out_u8);
   else
@@ -1121,7 +1262,8 @@ void SegmentComplete(napi_env env, napi_status, void* data) {
     }
   } else {
     napi_value msg, code, e;
-    const std::string m = std::string(w->composite ? "vss_segment_composite" : "vss_segment_post") + " failed (" +
+    const std::string m = std::string(w->bg ? "vss_segment_background"
+                                            : (w->composite ? "vss_segment_composite" : "vss_segment_post")) + " failed (" +
                           std::to_string(w->rc) + "): " + w->err;
     napi_create_string_utf8(env, m.c_str(), m.size(), &msg);
     napi_create_string_utf8(env, std::to_string(w->rc).c_str(), NAPI_AUTO_LENGTH, &code);
@@ -1137,8 +1279,10 @@ void SegmentComplete(napi_env env, napi_status, void* data) {
   work_done(hd);
 }
 
-// segmentPost(handle, post, frames, ...) and segmentComposite(handle, post, frames, ...)
-napi_value SegmentImpl(napi_env env, napi_callback_info info, bool with_post, bool composite = false) {
+// segmentPost(handle, post, frames, ...), segmentComposite(handle, post, frames, ...) and
+// segmentBackground(handle, post, frames, ..., background)
+napi_value SegmentImpl(napi_env env, napi_callback_info info, bool with_post, bool composite = false,
+                       bool background = false) {
   size_t argc = 9;
   napi_value all[9];
   NAPI_OK(env, napi_get_cb_info(env, info, &argc, all, nullptr, nullptr));
@@ -1157,6 +1301,20 @@ napi_value SegmentImpl(napi_env env, napi_callback_info info, bool with_post, bo
     if (!ps) return nullptr;
     if (ps->hd != hd) {
       napi_throw_error(env, nullptr, "post state belongs to another handle");
+      return nullptr;
+    }
+  }
+  Bg* bgp = nullptr;
+  if (background) {
+    if (argc < 9) {
+      napi_throw_type_error(env, nullptr,
+                            "segmentBackground(handle, post, frames, n, height, width, channels, rowStride, background)");
+      return nullptr;
+    }
+    bgp = get_bg(env, all[8]);
+    if (!bgp) return nullptr;
+    if (bgp->hd != hd) {
+      napi_throw_error(env, nullptr, "background belongs to another handle");
       return nullptr;
     }
   }
@@ -1200,6 +1358,7 @@ napi_value SegmentImpl(napi_env env, napi_callback_info info, bool with_post, bo
   NAPI_OK(env, napi_create_arraybuffer(env, w->out_count * 4, &out, &ab));
   w->out = static_cast<float*>(out);
   w->composite = composite;
+  w->bg = bgp ? bgp->bg : nullptr;
   if (ps) {
     napi_value ab8;
     void* out8 = nullptr;
@@ -1222,6 +1381,7 @@ napi_value SegmentImpl(napi_env env, napi_callback_info info, bool with_post, bo
 
 napi_value SegmentPost(napi_env env, napi_callback_info info) { return SegmentImpl(env, info, true); }
 napi_value SegmentComposite(napi_env env, napi_callback_info info) { return SegmentImpl(env, info, true, true); }
+napi_value SegmentBackground(napi_env env, napi_callback_info info) { return SegmentImpl(env, info, true, true, true); }
 
 // ---- ONNX sessions (include/vso.h) -------------------------------------------
 struct OrtSess {
@@ -1741,6 +1901,12 @@ napi_value Init(napi_env env, napi_value exports) {
       {"postSetFaces", nullptr, PostSetFaces, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"segmentPost", nullptr, SegmentPost, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"segmentComposite", nullptr, SegmentComposite, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"backgroundCreate", nullptr, BackgroundCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"backgroundSetColor", nullptr, BackgroundSetColor, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"backgroundSetImage", nullptr, BackgroundSetImage, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"backgroundSetBlur", nullptr, BackgroundSetBlur, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"backgroundDestroy", nullptr, BackgroundDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"segmentBackground", nullptr, SegmentBackground, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ortCreate", nullptr, OrtCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ortInfo", nullptr, OrtInfo, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ortRun", nullptr, OrtRun, nullptr, nullptr, nullptr, napi_default, nullptr},
