@@ -31,6 +31,44 @@
  * points, bias; dequantised once at create).  Anything else fails vso_create
  * with VSO_E_UNSUPPORTED naming the node.
  *
+ * Attributes (tests/op_cases.py is the table the sessions are held to):
+ *   opset_import          read; it selects Softmax's form and Split's default.
+ *   MaxPool, AveragePool  kernel_shape, strides, dilations, pads (0 or 4
+ *                         values), auto_pad, ceil_mode, count_include_pad: the
+ *                         divisor is the window's taps inside the padded input
+ *                         (a ceil_mode window reaching past the padding is cut
+ *                         there first, as ONNX's reference implementation and
+ *                         PyTorch do).  Refused: storage_order 1, MaxPool's
+ *                         Indices output, any other pads length.
+ *   Resize                mode nearest / linear, the four coordinate
+ *                         transformations above, nearest_mode
+ *                         round_prefer_floor / round_prefer_ceil / floor /
+ *                         ceil, constant scales or sizes on H and W.  Upsample:
+ *                         asymmetric, floor.  Refused: cubic, antialias, axes,
+ *                         keep_aspect_ratio_policy other than stretch, any
+ *                         other nearest_mode or transformation.
+ *   PRelu                 the slope broadcasts to the input as ONNX says (a
+ *                         1-D slope aligns with W); [C,1,1], [1,C,1,1] or one
+ *                         value after a Conv run in its epilogue.  Refused: a
+ *                         slope that does not broadcast to the input.
+ *   Clip                  min / max as attributes or constant inputs, either
+ *                         or both absent.
+ *   Pad                   constant mode; constant pads (negative: crop), value
+ *                         and axes.  Refused: reflect, edge, wrap.
+ *   Slice                 constant starts / ends / axes / steps (inputs, or
+ *                         attributes before opset 10), negative steps and
+ *                         indices, ends clamped.
+ *   Split                 sizes by input or attribute; else equal parts, from
+ *                         opset 18 on ceil-sized with a smaller last part.
+ *                         Refused: an uneven default split below opset 18.
+ *   Gemm                  transA, transB, alpha, beta, C broadcast to [M, N].
+ *   MatMul                B of rank 2, of batch 1, or batched like A.
+ *   Softmax               the last axis; below opset 13 the input flattened to
+ *                         2-D at axis (default 1), every row normalised.
+ *                         Refused: another axis from opset 13 on.
+ *   BatchNormalization    constant parameters, rank >= 2 (inference form).
+ *   InstanceNormalization constant scale and B, rank >= 3.
+ *
  * Errors: int returns are 0 or a negative code, message in vso_last_error
  * (thread-local when the session is NULL), like _OrtGetLastError (:50).
  * One call in flight per session.

@@ -394,6 +394,15 @@ def conv2d(x, w, b, attrs):
 
 
 def _pool(x, attrs, mode):
+    """MaxPool / AveragePool.  count_include_pad=1 divides by the window's taps
+    inside the padded input [-pad_begin, size + pad_end): a ceil_mode window
+    that reaches past it is clipped there first (the ONNX reference
+    implementation and PyTorch agree)."""
+    op = "MaxPool" if mode == "max" else "AveragePool"
+    if attrs.get("storage_order", 0):
+        raise ValueError(f"{op}: storage_order 1 is not supported")
+    if len(attrs.get("pads", [0, 0, 0, 0])) != 4:
+        raise ValueError(f"{op}: pads must have 4 values")
     n, c, h, w = x.shape
     k = attrs["kernel_shape"]
     s = attrs.get("strides", [1, 1])
@@ -414,13 +423,14 @@ def _pool(x, attrs, mode):
         for ox in range(wo):
             ys = [oy * s[0] - pt + i * d[0] for i in range(k[0])]
             xs = [ox * s[1] - pl + j * d[1] for j in range(k[1])]
+            padded = sum(y < h + pb for y in ys) * sum(q < w + pr for q in xs)
             ys = [y for y in ys if 0 <= y < h]
             xs = [q for q in xs if 0 <= q < w]
             win = xx[:, :, ys][:, :, :, xs]
             if mode == "max":
                 out[:, :, oy, ox] = win.max(axis=(2, 3))
             else:
-                cnt = (k[0] * k[1]) if attrs.get("count_include_pad", 0) else len(ys) * len(xs)
+                cnt = padded if attrs.get("count_include_pad", 0) else len(ys) * len(xs)
                 out[:, :, oy, ox] = win.sum(axis=(2, 3)) / cnt
     return out.astype(np.float32)
 
@@ -429,6 +439,14 @@ def _resize(x, scales, sizes, attrs):
     mode = attrs.get("mode", "nearest")
     ctm = attrs.get("coordinate_transformation_mode", "half_pixel")
     nmode = attrs.get("nearest_mode", "round_prefer_floor")
+    if nmode not in ("round_prefer_floor", "round_prefer_ceil", "floor", "ceil"):
+        raise ValueError(f"Resize: nearest_mode {nmode}")
+    if attrs.get("antialias", 0):
+        raise ValueError("Resize: antialias is not supported")
+    if "axes" in attrs:
+        raise ValueError("Resize: axes is not supported")
+    if attrs.get("keep_aspect_ratio_policy", "stretch") != "stretch":
+        raise ValueError(f"Resize: keep_aspect_ratio_policy {attrs['keep_aspect_ratio_policy']} is not supported")
     n, c, h, w = x.shape
     if sizes is not None and len(sizes):
         oh, ow = int(sizes[2]), int(sizes[3])
@@ -446,7 +464,7 @@ def _resize(x, scales, sizes, attrs):
             return o * (ilen - 1) / (olen - 1) if olen > 1 else 0.0
         if ctm == "asymmetric":
             return o / scale
-        raise ValueError(f"coordinate_transformation_mode {ctm}")
+        raise ValueError(f"Resize: coordinate_transformation_mode {ctm}")
     xx = x.astype(np.float64)
     out = np.zeros((n, c, oh, ow), np.float64)
     if mode == "nearest":
@@ -477,7 +495,7 @@ def _resize(x, scales, sizes, attrs):
                 out[:, :, oy, ox] = ((1 - fy) * ((1 - fx) * xx[:, :, y0, x0] + fx * xx[:, :, y0, x1]) +
                                      fy * ((1 - fx) * xx[:, :, y1, x0] + fx * xx[:, :, y1, x1]))
     else:
-        raise ValueError(f"Resize mode {mode}")
+        raise ValueError(f"Resize: mode {mode}")
     return out.astype(np.float32)
 
 
@@ -568,6 +586,9 @@ def run(model: Model, feeds: dict, want=None, conv_operands=None) -> dict:
         elif op == "LeakyRelu":
             y = _f32(np.where(x >= 0, x, x.astype(np.float64) * a.get("alpha", 0.01)))
         elif op == "PRelu":
+            sl = ins[1]  # unidirectional: the slope broadcasts to x
+            if sl.ndim > x.ndim or any(a != 1 and a != b for a, b in zip(sl.shape[::-1], x.shape[::-1])):
+                raise ValueError(f"PRelu: slope {sl.shape} does not broadcast to the input {x.shape}")
             y = _f32(np.where(x >= 0, x, x.astype(np.float64) * ins[1].astype(np.float64)))
         elif op == "Clip":
             lo = ins[1] if len(ins) > 1 and ins[1] is not None else a.get("min", -np.inf)
@@ -586,34 +607,54 @@ def run(model: Model, feeds: dict, want=None, conv_operands=None) -> dict:
             else:
                 y = fn(p, q)
         elif op == "MaxPool":
+            if len(nd["outputs"]) > 1 and nd["outputs"][1]:
+                raise ValueError("MaxPool: the Indices output is not supported")
             y = _pool(x, a, "max")
         elif op == "AveragePool":
             y = _pool(x, a, "avg")
         elif op == "GlobalAveragePool":
-            y = _f32(x.astype(np.float64).mean(axis=(2, 3), keepdims=True))
+            y = _f32(x.astype(np.float64).mean(axis=tuple(range(2, x.ndim)), keepdims=True))
         elif op == "Pad":
             pads = list(ins[1]) if len(ins) > 1 and ins[1] is not None else a["pads"]
             val = float(ins[2]) if len(ins) > 2 and ins[2] is not None and ins[2].size else a.get("value", 0.0)
             r = x.ndim
             mode = a.get("mode", "constant")
-            pw = [(int(pads[i]), int(pads[i + r])) for i in range(r)]
-            y = np.pad(x, pw, mode="constant", constant_values=val) if mode == "constant" else \
-                np.pad(x, pw, mode={"reflect": "reflect", "edge": "edge"}[mode])
+            if mode != "constant":
+                raise ValueError(f"Pad: constant mode only, got {mode}")
+            axes = [int(v) % r for v in ins[3]] if len(ins) > 3 and ins[3] is not None else list(range(r))
+            if len(pads) != 2 * len(axes):
+                raise ValueError("Pad: pads length")
+            pw = [[0, 0] for _ in range(r)]
+            for k, ax in enumerate(axes):
+                pw[ax] = [int(pads[k]), int(pads[k + len(axes)])]
+            # negative pads remove elements: crop first, then pad what is left to add
+            crop = tuple(slice(max(-lo, 0), x.shape[d] - max(-hi, 0)) for d, (lo, hi) in enumerate(pw))
+            y = np.pad(x[crop], [(max(lo, 0), max(hi, 0)) for lo, hi in pw], mode="constant", constant_values=val)
         elif op == "Concat":
             y = np.concatenate([t for t in ins if t is not None], axis=a["axis"])
         elif op == "Split":
             ax = a.get("axis", 0)
             sp = list(ins[1]) if len(ins) > 1 and ins[1] is not None else a.get("split")
             if sp is None:
-                k = len(nd["outputs"])
-                sp = [x.shape[ax] // k] * k
+                # opset 18: ceil-sized parts, the last one smaller; before, even parts only
+                k, length = len(nd["outputs"]), x.shape[ax]
+                if length % k and 0 < model.opset < 18:
+                    raise ValueError("Split: uneven default split needs opset 18")
+                part = -(-length // k)
+                sp = [max(0, min(part, length - q * part)) for q in range(k)]
+            if len(sp) != len(nd["outputs"]) or sum(int(v) for v in sp) != x.shape[ax]:
+                raise ValueError("Split: sizes do not add up to the axis")
             idx = np.cumsum(sp)[:-1]
             parts = np.split(x, idx, axis=ax)
             for o, t in zip(nd["outputs"], parts):
                 env[o] = t
             continue
         elif op == "Slice":
-            starts, ends = list(ins[1]), list(ins[2])
+            if len(ins) >= 3:
+                starts, ends = list(ins[1]), list(ins[2])
+            else:  # before opset 10: attributes
+                starts, ends = a["starts"], a["ends"]
+                ins = ins + [None, None, np.asarray(a["axes"]) if "axes" in a else None]
             axes = list(ins[3]) if len(ins) > 3 and ins[3] is not None else list(range(len(starts)))
             steps = list(ins[4]) if len(ins) > 4 and ins[4] is not None else [1] * len(starts)
             sl = [slice(None)] * x.ndim
@@ -645,19 +686,23 @@ def run(model: Model, feeds: dict, want=None, conv_operands=None) -> dict:
                 y = x.astype(_NP[a["to"]])
         elif op in ("Resize", "Upsample"):
             if op == "Upsample":
-                y = _resize(x, ins[1], None, a)
+                # opset 7-9, neither attribute: y[o] = x[floor(o / scale)] (linear: asymmetric)
+                scales = ins[1] if len(ins) > 1 and ins[1] is not None else a["scales"]
+                y = _resize(x, scales, None, {"coordinate_transformation_mode": "asymmetric", "nearest_mode": "floor", **a})
             else:
                 scales = ins[2] if len(ins) > 2 and ins[2] is not None and ins[2].size else None
                 sizes = ins[3] if len(ins) > 3 and ins[3] is not None else None
                 y = _resize(x, scales, sizes, a)
         elif op == "InstanceNormalization":
             xx = x.astype(np.float64)
-            mu = xx.mean(axis=(2, 3), keepdims=True)
-            var = ((xx - mu) ** 2).mean(axis=(2, 3), keepdims=True)
-            y = _f32((xx - mu) / np.sqrt(var + a.get("epsilon", 1e-5)) * ins[1].astype(np.float64)[None, :, None, None]
-                     + ins[2].astype(np.float64)[None, :, None, None])
+            sp = tuple(range(2, x.ndim))
+            per_c = (1, -1) + (1,) * (x.ndim - 2)
+            mu = xx.mean(axis=sp, keepdims=True)
+            var = ((xx - mu) ** 2).mean(axis=sp, keepdims=True)
+            y = _f32((xx - mu) / np.sqrt(var + a.get("epsilon", 1e-5)) * ins[1].astype(np.float64).reshape(per_c)
+                     + ins[2].astype(np.float64).reshape(per_c))
         elif op == "BatchNormalization":
-            sc, bb, mu, var = (t.astype(np.float64)[None, :, None, None] for t in ins[1:5])
+            sc, bb, mu, var = (t.astype(np.float64).reshape((1, -1) + (1,) * (x.ndim - 2)) for t in ins[1:5])
             y = _f32((x.astype(np.float64) - mu) / np.sqrt(var + a.get("epsilon", 1e-5)) * sc + bb)
         elif op == "MatMul":
             y = _f32(np.matmul(x.astype(np.float64), ins[1].astype(np.float64)))
@@ -681,9 +726,15 @@ def run(model: Model, feeds: dict, want=None, conv_operands=None) -> dict:
                 r = r + ins[5].astype(np.float64)
             y = _f32(r).reshape(tuple(x.shape[:-1]) + (a["N"],))
         elif op == "Softmax":
-            ax = a.get("axis", -1)
-            e = np.exp(x.astype(np.float64) - x.max(axis=ax, keepdims=True))
-            y = _f32(e / e.sum(axis=ax, keepdims=True))
+            # opset 13 on: along `axis` (default -1; the GPU session takes the last
+            # axis only).  Before: the input flattened to 2-D at `axis` (default 1).
+            flat = 0 < model.opset < 13
+            ax = a.get("axis", 1 if flat else -1) % x.ndim
+            if not flat and ax != x.ndim - 1:
+                raise ValueError("Softmax: last axis only")
+            xx = x.astype(np.float64).reshape(int(np.prod(x.shape[:ax])), -1)
+            e = np.exp(xx - xx.max(axis=1, keepdims=True))
+            y = _f32(e / e.sum(axis=1, keepdims=True)).reshape(x.shape)
         elif op == "Shape":
             y = np.array(x.shape, np.int64)
         elif op == "Gather":

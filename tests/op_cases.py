@@ -1,0 +1,425 @@
+"""The operator conformance matrix of the ONNX sessions (test infrastructure):
+one table of named single-operator cases, shared by
+tests/test_op_matrix_oracle.py (the oracle against an independent float64
+evaluation, CPU) and tests/test_gpu_op_matrix.py (the GPU session against the
+oracle).
+
+A case is one operator node: its attributes, its inputs in operator order
+(graph inputs filled from a seeded generator, or constants where the operator
+needs them constant), the model's opset, and whether the session must compute
+it ("value") or refuse it at creation ("refused").  build() packs any number
+of cases into one model with one graph output per case output, so one GPU
+session serves a whole family; every operand that should reach a kernel is a
+graph input (constant folding cannot eat a case).
+"""
+from __future__ import annotations
+
+import zlib
+from dataclasses import dataclass, field
+
+import numpy as np
+
+import onnx_models as M
+import onnx_ref as R
+
+I64 = np.int64
+INT64_MAX, INT64_MIN = np.iinfo(np.int64).max, np.iinfo(np.int64).min
+
+
+@dataclass(frozen=True)
+class Case:
+    name: str
+    family: str
+    op: str
+    # per operator input: ("x", shape) standard normal | ("pos", shape) in [0.5, 1.5) |
+    # ("pm80", shape) +-80 plus a standard normal | ("c", array) a constant | None (omitted)
+    inputs: tuple
+    attrs: dict = field(default_factory=dict)
+    seed: int = 0
+    opset: int = 13
+    expect: str = "value"   # or "refused"
+    exact: bool = False     # data movement / selection: bitwise
+    n_out: int = 1
+    post: tuple = ()        # ("PRelu", slope array): a second node on the output (the fused forms)
+    kernels: tuple = ()     # what a session of this case alone launches (a part of each name, in order)
+
+
+CASES: list[Case] = []
+
+
+def case(name, family, op, inputs, attrs=None, **kw):
+    assert all(c.name != name for c in CASES), name
+    CASES.append(Case(name, family, op, tuple(inputs), dict(attrs or {}), **kw))
+
+
+def x(*shape):
+    return ("x", tuple(shape))
+
+
+def pos(*shape):
+    return ("pos", tuple(shape))
+
+
+def c(arr, dtype=None):
+    return ("c", np.asarray(arr, dtype))
+
+
+def ci(*v):
+    return ("c", np.asarray(v, I64))
+
+
+def cf(shape, seed, lo=None):
+    """A seeded float32 constant: standard normal, or uniform in [lo, lo + 1)."""
+    rng = np.random.default_rng(1000 + seed)
+    a = rng.standard_normal(shape) if lo is None else rng.random(shape) + lo
+    return ("c", a.astype(np.float32))
+
+
+def _tag(v):
+    return "x".join(str(k) for k in v) if isinstance(v, (tuple, list)) else str(v)
+
+
+X = (2, 3, 10, 11)
+
+# ---------------------------------------------------------------------------
+# MaxPool / AveragePool (k_pool)
+for op_ in ("MaxPool", "AveragePool"):
+    for k_ in (2, 3, (2, 3)):
+        for s_ in (1, 2, (2, 1)):
+            for p_ in ((0, 0, 0, 0), (1, 1, 1, 1), (0, 1, 1, 0)):
+                for ceil_ in (0, 1):
+                    for cip_ in ((0, 1) if op_ == "AveragePool" else (None,)):
+                        kk = list(k_) if isinstance(k_, tuple) else [k_, k_]
+                        ss = list(s_) if isinstance(s_, tuple) else [s_, s_]
+                        at = {"kernel_shape": kk, "strides": ss, "pads": list(p_), "ceil_mode": ceil_}
+                        nm = f"{op_}_k{_tag(k_)}_s{_tag(s_)}_p{''.join(map(str, p_))}_ceil{ceil_}"
+                        if cip_ is not None:
+                            at["count_include_pad"] = cip_
+                            nm += f"_cip{cip_}"
+                        case(nm, "pool", op_, [x(*X)], at, exact=op_ == "MaxPool")
+for k_ in (2, 3):
+    for s_ in (1, 2):
+        for p_ in (0, 1):
+            for ceil_ in (0, 1):
+                case(f"MaxPool_dil2_k{k_}_s{s_}_p{p_}_ceil{ceil_}", "pool", "MaxPool", [x(*X)],
+                     {"kernel_shape": [k_, k_], "strides": [s_, s_], "pads": [p_] * 4, "dilations": [2, 2],
+                      "ceil_mode": ceil_}, exact=True)
+for ap_ in ("SAME_UPPER", "SAME_LOWER", "VALID"):
+    case(f"MaxPool_{ap_}", "pool", "MaxPool", [x(*X)], {"kernel_shape": [3, 3], "strides": [2, 2], "auto_pad": ap_},
+         exact=True)
+    for cip_ in (0, 1):
+        case(f"AveragePool_{ap_}_cip{cip_}", "pool", "AveragePool", [x(*X)],
+             {"kernel_shape": [3, 3], "strides": [2, 2], "auto_pad": ap_, "count_include_pad": cip_})
+case("AveragePool_default_strides", "pool", "AveragePool", [x(*X)], {"kernel_shape": [2, 2]})
+
+# ---------------------------------------------------------------------------
+# Resize / Upsample (k_resize<true>: rows of a multiple of 4 outputs; <false>: the rest)
+RX = (2, 3, 10, 12)
+CTMS = ("half_pixel", "pytorch_half_pixel", "align_corners", "asymmetric")
+
+
+def _resize_inputs(scale=None, sizes=None):
+    if sizes is not None:
+        return [x(*RX), None, None, ci(RX[0], RX[1], *sizes)]
+    return [x(*RX), None, c([1, 1, scale, scale], np.float32)]
+
+
+for ctm_ in CTMS:
+    for sc_ in (2.0, 0.5, 1.5):  # 20x24 (float4 rows), 5x6, 15x18
+        case(f"Resize_linear_{ctm_}_x{sc_}", "resize", "Resize", _resize_inputs(scale=sc_),
+             {"mode": "linear", "coordinate_transformation_mode": ctm_},
+             kernels=("k_resize<true>(" if int(RX[3] * sc_) % 4 == 0 else "k_resize<false>(",))
+    for sz_ in ((7, 13), (5, 16), (1, 8), (9, 1)):
+        case(f"Resize_linear_{ctm_}_to{_tag(sz_)}", "resize", "Resize", _resize_inputs(sizes=sz_),
+             {"mode": "linear", "coordinate_transformation_mode": ctm_})
+for nm_ in ("round_prefer_floor", "round_prefer_ceil", "floor", "ceil"):
+    for ctm_ in ("asymmetric", "half_pixel"):
+        for sc_ in (2.0, 0.5, 1.5):
+            case(f"Resize_nearest_{nm_}_{ctm_}_x{sc_}", "resize", "Resize", _resize_inputs(scale=sc_),
+                 {"mode": "nearest", "coordinate_transformation_mode": ctm_, "nearest_mode": nm_}, exact=True)
+        for sz_ in ((7, 13), (25, 16)):
+            case(f"Resize_nearest_{nm_}_{ctm_}_to{_tag(sz_)}", "resize", "Resize", _resize_inputs(sizes=sz_),
+                 {"mode": "nearest", "coordinate_transformation_mode": ctm_, "nearest_mode": nm_}, exact=True)
+case("Resize_nearest_defaults_x2", "resize", "Resize", _resize_inputs(scale=2.0), {}, exact=True)
+case("Upsample_nearest_x2x3", "resize9", "Upsample", [x(*RX), c([1, 1, 2, 3], np.float32)], {"mode": "nearest"},
+     opset=9, exact=True)
+case("Upsample_nearest_x1.5", "resize9", "Upsample", [x(*RX), c([1, 1, 1.5, 1.5], np.float32)], {"mode": "nearest"},
+     opset=9, exact=True)
+case("Upsample_linear_x2", "resize9", "Upsample", [x(*RX), c([1, 1, 2, 2], np.float32)], {"mode": "linear"}, opset=9)
+case("Upsample_linear_x1.5", "resize9", "Upsample", [x(*RX), c([1, 1, 1.5, 1.5], np.float32)], {"mode": "linear"},
+     opset=9)
+
+# ---------------------------------------------------------------------------
+# standalone activations (k_unary; PRelu: k_binary)
+case("Relu", "unary", "Relu", [x(*X)], exact=True)
+case("LeakyRelu_default", "unary", "LeakyRelu", [x(*X)])
+case("LeakyRelu_alpha0.2", "unary", "LeakyRelu", [x(*X)], {"alpha": 0.2})
+case("Sigmoid", "unary", "Sigmoid", [("x4", X)])
+case("Tanh", "unary", "Tanh", [("x4", X)])
+case("Clip_min_max", "unary", "Clip", [x(*X), c(-0.5, np.float32), c(0.75, np.float32)], exact=True)
+case("Clip_min_only", "unary", "Clip", [x(*X), c(-0.25, np.float32)], exact=True)
+case("Clip_max_only", "unary", "Clip", [x(*X), None, c(0.5, np.float32)], exact=True)
+case("Clip_none", "unary", "Clip", [x(*X)], exact=True)
+case("Clip_attr_min_only", "unary6", "Clip", [x(*X)], {"min": -0.25}, opset=6, exact=True)
+case("Clip_attr_max_only", "unary6", "Clip", [x(*X)], {"max": 0.5}, opset=6, exact=True)
+case("PRelu_C11", "unary", "PRelu", [x(*X), cf((3, 1, 1), 1)])
+case("PRelu_1C11", "unary", "PRelu", [x(*X), cf((1, 3, 1, 1), 2)])
+case("PRelu_scalar", "unary", "PRelu", [x(*X), cf((1,), 3)])
+case("PRelu_W_1d", "unary", "PRelu", [x(*X), cf((11,), 4)])
+# a 1-D slope aligns with W, also where C == W (here both 4): not per channel
+case("PRelu_1d_C_equals_W", "unary", "PRelu", [x(2, 4, 5, 4), cf((4,), 5)])
+case("PRelu_runtime_slope", "unary", "PRelu", [x(*X), x(3, 1, 1)])
+# behind a convolution: [C,1,1] in the epilogue, [C] (C == W) aligned with W by its own launch
+case("ConvPRelu_C11", "fused", "Conv", [x(1, 3, 6, 4), cf((4, 3, 3, 3), 6), cf((4,), 7)],
+     {"kernel_shape": [3, 3], "pads": [1, 1, 1, 1]}, post=("PRelu", cf((4, 1, 1), 8)[1]), kernels=("k_conv",))
+case("ConvPRelu_1d_C_equals_W", "fused", "Conv", [x(1, 3, 6, 4), cf((4, 3, 3, 3), 6), cf((4,), 7)],
+     {"kernel_shape": [3, 3], "pads": [1, 1, 1, 1]}, post=("PRelu", cf((4,), 9)[1]), kernels=("k_conv", "k_binary("))
+
+# ---------------------------------------------------------------------------
+# Add / Sub / Mul / Div (k_binary; a per-plane operand on contiguous planes: k_binary_planes)
+for op_ in ("Add", "Sub", "Mul", "Div"):
+    d_ = pos if op_ == "Div" else x
+    case(f"{op_}_same_shape", "binary", op_, [x(*X), d_(*X)])
+    case(f"{op_}_both_broadcast", "binary", op_, [x(2, 1, 10, 1), d_(1, 3, 1, 11)])
+    case(f"{op_}_rank5", "binary", op_, [x(2, 1, 3, 1, 5), d_(1, 4, 1, 2, 5)])
+    case(f"{op_}_rank6", "binary", op_, [x(2, 1, 2, 1, 3, 1), d_(1, 3, 1, 2, 1, 4)])
+    case(f"{op_}_lower_rank", "binary", op_, [x(*X), d_(11)])
+    case(f"{op_}_lower_rank_left", "binary", op_, [x(10, 1), d_(*X)])
+    case(f"{op_}_planes", "binary", op_, [x(2, 3, 4, 6), d_(2, 3, 1, 1)], kernels=("k_binary_planes(",))
+    case(f"{op_}_planes_odd", "binary", op_, [x(2, 3, 3, 5), d_(2, 3, 1, 1)], kernels=("k_binary(",))
+    case(f"{op_}_const_right", "binary", op_, [x(*X), cf((3, 1, 1), 11, lo=0.5)])
+    case(f"{op_}_const_left", "binary", op_, [cf((3, 1, 1), 12, lo=0.5), d_(*X)])
+    case(f"{op_}_scalar_const_left", "binary", op_, [c(1.5, np.float32), d_(*X)])
+
+# ---------------------------------------------------------------------------
+# Slice (k_copy; whole trailing dims: k_copy_rows)
+case("Slice_reverse_W", "slice", "Slice", [x(*X), ci(-1), ci(INT64_MIN), ci(3), ci(-1)], exact=True)
+case("Slice_step-2", "slice", "Slice", [x(*X), ci(8), ci(1), ci(2), ci(-2)], exact=True)
+case("Slice_step-3_past_both_ends", "slice", "Slice", [x(*X), ci(INT64_MAX), ci(INT64_MIN), ci(-1), ci(-3)], exact=True)
+case("Slice_negative_indices", "slice", "Slice", [x(*X), ci(-7), ci(-2), ci(-2)], exact=True)
+case("Slice_end_max", "slice", "Slice", [x(*X), ci(1, 4), ci(INT64_MAX, INT64_MAX), ci(1, 3)], exact=True)
+case("Slice_steps_2_3", "slice", "Slice", [x(*X), ci(1, 0), ci(9, 11), ci(2, 3), ci(2, 3)], exact=True)
+case("Slice_default_axes", "slice", "Slice", [x(*X), ci(0, 1), ci(2, 3)], exact=True)
+case("Slice_steps_without_axes", "slice", "Slice", [x(*X), ci(1, 0), ci(2, 3), None, ci(1, 2)], exact=True)
+case("Slice_channels", "slice", "Slice", [x(2, 4, 10, 12), ci(1), ci(3), ci(1)], exact=True,
+     kernels=("k_copy_rows<true>(",))
+case("Slice_batch_odd", "slice", "Slice", [x(*X), ci(1), ci(2), ci(0)], exact=True,
+     kernels=("k_copy_rows<false>(",))
+case("Slice_attr_form", "slice9", "Slice", [x(*X)], {"starts": [1, -6], "ends": [3, INT64_MAX], "axes": [1, 3]},
+     opset=9, exact=True)
+
+# ---------------------------------------------------------------------------
+# Concat / Split (k_copy_rows<true>: 16-byte moves; <false>; k_copy)
+case("Concat_axis0", "concat", "Concat", [x(1, 3, 10, 11), x(2, 3, 10, 11), x(1, 3, 10, 11)], {"axis": 0}, exact=True,
+     kernels=("k_copy_rows<false>(",) * 3)
+case("Concat_axis1_vec", "concat", "Concat", [x(2, 1, 10, 12), x(2, 2, 10, 12), x(2, 3, 10, 12)], {"axis": 1},
+     exact=True, kernels=("k_copy_rows<true>(",) * 3)
+case("Concat_axis1_odd", "concat", "Concat", [x(2, 1, 10, 11), x(2, 2, 10, 11), x(2, 3, 10, 11)], {"axis": 1},
+     exact=True, kernels=("k_copy_rows<false>(",) * 3)
+case("Concat_axis2", "concat", "Concat", [x(2, 3, 1, 11), x(2, 3, 4, 11), x(2, 3, 2, 11)], {"axis": 2}, exact=True,
+     kernels=("k_copy(",) * 3)
+case("Concat_axis-1", "concat", "Concat", [x(2, 3, 10, 1), x(2, 3, 10, 5), x(2, 3, 10, 3)], {"axis": -1}, exact=True,
+     kernels=("k_copy(",) * 3)
+case("Concat_rank2_axis-1", "concat", "Concat", [x(3, 5), x(3, 1), x(3, 2)], {"axis": -1}, exact=True)
+case("Split_sizes_input", "split", "Split", [x(2, 7, 4, 5), ci(1, 4, 2)], {"axis": 1}, n_out=3, exact=True)
+case("Split_sizes_W", "split", "Split", [x(*X), ci(5, 6)], {"axis": -1}, n_out=2, exact=True)
+case("Split_default_even", "split", "Split", [x(2, 6, 4, 5)], {"axis": 1}, n_out=3, exact=True)
+case("Split_default_axis", "split", "Split", [x(4, 3, 5)], {}, n_out=2, exact=True)
+case("Split_sizes_attr", "split11", "Split", [x(2, 7, 4, 5)], {"axis": 1, "split": [3, 4]}, n_out=2, opset=11,
+     exact=True)
+case("Split_default_uneven", "split18", "Split", [x(2, 7, 4, 5)], {"axis": 1, "num_outputs": 3}, n_out=3, opset=18,
+     exact=True)
+case("Split_default_uneven_W", "split18", "Split", [x(2, 3, 4, 10)], {"axis": 3, "num_outputs": 4}, n_out=4, opset=18,
+     exact=True)
+case("Split_default_even_18", "split18", "Split", [x(2, 6, 4, 5)], {"axis": 1, "num_outputs": 2}, n_out=2, opset=18,
+     exact=True)
+
+# ---------------------------------------------------------------------------
+# Transpose / Pad (k_copy)
+case("Transpose_default_rank4", "move", "Transpose", [x(*X)], exact=True)
+case("Transpose_default_rank3", "move", "Transpose", [x(3, 5, 7)], exact=True)
+case("Transpose_default_rank2", "move", "Transpose", [x(5, 7)], exact=True)
+case("Transpose_nhwc", "move", "Transpose", [x(*X)], {"perm": [0, 2, 3, 1]}, exact=True)
+case("Transpose_rank5", "move", "Transpose", [x(2, 3, 4, 5, 6)], {"perm": [4, 0, 3, 1, 2]}, exact=True)
+case("Pad_value", "move", "Pad", [x(*X), ci(0, 1, 2, 0, 0, 0, 1, 3), c(0.5, np.float32)], exact=True)
+case("Pad_default_value", "move", "Pad", [x(*X), ci(0, 0, 1, 1, 0, 0, 1, 1)], exact=True)
+case("Pad_negative", "move", "Pad", [x(*X), ci(0, 0, -2, -1, 0, -1, -3, 0)], exact=True)
+case("Pad_mixed_sign", "move", "Pad", [x(*X), ci(0, 0, -2, 3, 0, 1, 2, -4), c(-1.0, np.float32)], exact=True)
+case("Pad_axes", "move18", "Pad", [x(*X), ci(1, 2, 3, 0), c(2.0, np.float32), ci(3, 1)], opset=18, exact=True)
+case("Pad_negative_axes", "move18", "Pad", [x(*X), ci(2, -3, -1, 1), None, ci(-1, -2)], opset=18, exact=True)
+case("Pad_attr_form", "move9", "Pad", [x(*X)], {"pads": [0, 0, 1, 2, 0, 1, 0, 0], "value": 0.25}, opset=9, exact=True)
+
+# ---------------------------------------------------------------------------
+# the view ops (no launch: the output is the input's buffer)
+case("Squeeze_axes_input", "view", "Squeeze", [x(2, 1, 5, 1), ci(1, -1)], exact=True)
+case("Squeeze_all", "view", "Squeeze", [x(2, 1, 5, 1)], exact=True)
+case("Unsqueeze_axes_input", "view", "Unsqueeze", [x(2, 5), ci(0, 3)], exact=True)
+case("Unsqueeze_negative_axes", "view", "Unsqueeze", [x(2, 5), ci(-1, 1)], exact=True)
+case("Squeeze_axes_attr", "view11", "Squeeze", [x(2, 1, 5, 1)], {"axes": [1, 3]}, opset=11, exact=True)
+case("Unsqueeze_axes_attr", "view11", "Unsqueeze", [x(2, 5)], {"axes": [0, 3]}, opset=11, exact=True)
+case("Flatten_axis0", "view", "Flatten", [x(*X)], {"axis": 0}, exact=True)
+case("Flatten_axis2", "view", "Flatten", [x(*X)], {"axis": 2}, exact=True)
+case("Flatten_axis-1", "view", "Flatten", [x(*X)], {"axis": -1}, exact=True)
+case("Flatten_default", "view", "Flatten", [x(*X)], exact=True)
+case("Reshape_0_-1", "view", "Reshape", [x(*X), ci(0, -1, 11)], exact=True)
+case("Reshape_-1_first", "view", "Reshape", [x(*X), ci(-1, 0, 5, 2, 11)], exact=True)
+case("Reshape_plain", "view", "Reshape", [x(*X), ci(6, 110)], exact=True)
+
+# ---------------------------------------------------------------------------
+# Gemm / MatMul (k_gemm<true>: both operands contiguous in k, K % 4 == 0; <false>: the rest)
+case("Gemm_plain", "gemm", "Gemm", [x(5, 8), x(8, 7)], kernels=("k_gemm<false>(",))
+case("Gemm_transB_vec", "gemm", "Gemm", [x(5, 8), x(7, 8), x(7)], {"transB": 1}, kernels=("k_gemm<true>(",))
+case("Gemm_transB_K6", "gemm", "Gemm", [x(5, 6), x(7, 6), x(7)], {"transB": 1}, kernels=("k_gemm<false>(",))
+case("Gemm_transA", "gemm", "Gemm", [x(8, 5), x(8, 7), x(5, 7)], {"transA": 1}, kernels=("k_gemm<false>(",))
+case("Gemm_transA_transB", "gemm", "Gemm", [x(8, 5), x(7, 8), x(1, 7)], {"transA": 1, "transB": 1})
+case("Gemm_alpha_beta", "gemm", "Gemm", [x(5, 8), x(8, 7), x(5, 7)], {"alpha": 0.5, "beta": -1.5})
+case("Gemm_alpha_only", "gemm", "Gemm", [x(5, 8), x(8, 7)], {"alpha": 2.5})
+case("Gemm_C_M1", "gemm", "Gemm", [x(5, 8), x(8, 7), x(5, 1)], {"beta": 0.75})
+case("Gemm_C_1N", "gemm", "Gemm", [x(5, 8), x(8, 7), x(1, 7)])
+case("Gemm_C_1", "gemm", "Gemm", [x(5, 8), x(8, 7), x(1)])
+case("Gemm_C_11", "gemm", "Gemm", [x(5, 8), x(8, 7), x(1, 1)])
+case("Gemm_C_const", "gemm", "Gemm", [x(5, 8), x(8, 7), cf((7,), 21)])
+case("Gemm_tiles", "gemm", "Gemm", [x(18, 37), x(37, 33), x(18, 1)], {"alpha": 0.5})
+case("Gemm_tiles_vec", "gemm", "Gemm", [x(18, 68), x(33, 68), x(33)], {"transB": 1},
+     kernels=("k_gemm<true>(",))
+case("MatMul_2d", "gemm", "MatMul", [x(5, 8), x(8, 7)])
+case("MatMul_batch_broadcast_B2d", "gemm", "MatMul", [x(2, 3, 4, 5), x(5, 7)])
+case("MatMul_batch_broadcast_B1", "gemm", "MatMul", [x(2, 4, 8), x(1, 8, 7)])
+case("MatMul_batched_B", "gemm", "MatMul", [x(2, 3, 4, 8), x(2, 3, 8, 7)])
+case("MatMul_const_B", "gemm", "MatMul", [x(2, 4, 8), cf((8, 7), 22)], kernels=("k_gemm<true>(",))
+case("MatMul_const_B_K6", "gemm", "MatMul", [x(2, 4, 6), cf((6, 7), 23)], kernels=("k_gemm<false>(",))
+
+# ---------------------------------------------------------------------------
+# BatchNormalization alone (k_affine), InstanceNormalization, GlobalAveragePool, Softmax
+for shp_ in ((4, 5), (2, 5, 7), (2, 5, 3, 4), (2, 5, 2, 3, 2)):
+    case(f"BatchNormalization_rank{len(shp_)}", "norm", "BatchNormalization",
+         [x(*shp_), cf((5,), 31, lo=0.5), cf((5,), 32), cf((5,), 33), cf((5,), 34, lo=0.5)], {"epsilon": 1e-3},
+         kernels=("k_affine(",))
+case("BatchNormalization_default_eps", "norm", "BatchNormalization",
+     [x(2, 5, 3, 4), cf((5,), 31, lo=0.5), cf((5,), 32), cf((5,), 33), cf((5,), 34, lo=0.5)])
+for shp_ in ((2, 3, 1, 1), (2, 3, 1, 3), (1, 2, 15, 17), (1, 2, 16, 16), (1, 2, 1, 257), (2, 3, 257), (2, 3, 33, 40)):
+    case(f"InstanceNormalization_{_tag(shp_)}", "norm", "InstanceNormalization",
+         [("x3", shp_), cf((shp_[1],), 35, lo=0.5), cf((shp_[1],), 36)], {"epsilon": 1e-5})
+case("GlobalAveragePool_1024", "gap", "GlobalAveragePool", [x(1, 3, 32, 32)], kernels=("k_gap_wave(",))
+case("GlobalAveragePool_1025", "gap", "GlobalAveragePool", [x(1, 5, 25, 41)], kernels=("k_gap(",))
+case("GlobalAveragePool_rows6", "gap", "GlobalAveragePool", [x(*X)], kernels=("k_gap_wave(",))
+case("GlobalAveragePool_1x1", "gap", "GlobalAveragePool", [x(3, 3, 1, 1)])
+case("GlobalAveragePool_rank3", "gap", "GlobalAveragePool", [x(2, 3, 17)])
+for n_ in (1, 255, 256, 257, 1000):
+    case(f"Softmax_{n_}", "softmax", "Softmax", [x(3, n_)])
+    case(f"Softmax_{n_}_pm80", "softmax", "Softmax", [("pm80", (3, n_))])
+case("Softmax_rank3", "softmax", "Softmax", [x(2, 3, 5)], {"axis": -1})
+case("Softmax_rank4_axis3", "softmax", "Softmax", [x(2, 3, 4, 5)], {"axis": 3})
+# before opset 13: flattened to 2-D at `axis` (default 1), each row normalised
+case("Softmax_opset11_default_axis_rank3", "softmax11", "Softmax", [x(2, 3, 5)], opset=11)
+case("Softmax_opset11_axis1_rank4", "softmax11", "Softmax", [x(2, 3, 4, 5)], {"axis": 1}, opset=11)
+case("Softmax_opset11_axis0", "softmax11", "Softmax", [x(3, 5)], {"axis": 0}, opset=11)
+case("Softmax_opset11_axis-1", "softmax11", "Softmax", [x(2, 3, 5)], {"axis": -1}, opset=11)
+
+# ---------------------------------------------------------------------------
+# what the session refuses at creation (and the oracle refuses to evaluate)
+case("refuse_Resize_antialias", "refused", "Resize", _resize_inputs(scale=0.5), {"mode": "linear", "antialias": 1},
+     opset=18, expect="refused")
+case("refuse_Resize_axes", "refused", "Resize", [x(*RX), None, c([2, 2], np.float32)], {"mode": "linear", "axes": [2, 3]},
+     opset=18, expect="refused")
+case("refuse_Resize_keep_aspect_ratio_policy", "refused", "Resize", _resize_inputs(sizes=(7, 13)),
+     {"mode": "linear", "keep_aspect_ratio_policy": "not_larger"}, opset=18, expect="refused")
+case("refuse_Resize_nearest_mode", "refused", "Resize", _resize_inputs(scale=2.0),
+     {"mode": "nearest", "nearest_mode": "round_half_up"}, expect="refused")
+case("refuse_Resize_cubic", "refused", "Resize", _resize_inputs(scale=2.0), {"mode": "cubic"}, expect="refused")
+case("refuse_MaxPool_pads_length", "refused", "MaxPool", [x(*X)], {"kernel_shape": [3, 3], "pads": [1, 1]},
+     expect="refused")
+case("refuse_AveragePool_pads_length", "refused", "AveragePool", [x(*X)], {"kernel_shape": [3, 3], "pads": [1, 1]},
+     expect="refused")
+case("refuse_MaxPool_storage_order", "refused", "MaxPool", [x(*X)], {"kernel_shape": [2, 2], "storage_order": 1},
+     expect="refused")
+case("refuse_MaxPool_Indices", "refused", "MaxPool", [x(*X)], {"kernel_shape": [2, 2]}, n_out=2, expect="refused")
+case("refuse_Pad_reflect", "refused", "Pad", [x(*X), ci(0, 0, 1, 1, 0, 0, 1, 1)], {"mode": "reflect"}, expect="refused")
+case("refuse_Softmax_axis1_rank3", "refused", "Softmax", [x(2, 3, 5)], {"axis": 1}, expect="refused")
+case("refuse_Softmax_axis0_rank2", "refused", "Softmax", [x(3, 5)], {"axis": 0}, expect="refused")
+case("refuse_Split_uneven_opset13", "refused", "Split", [x(2, 7, 4, 5)], {"axis": 1}, n_out=3, expect="refused")
+case("refuse_Split_uneven_opset11", "refused", "Split", [x(2, 7, 4, 5)], {"axis": 1}, n_out=2, opset=11,
+     expect="refused")
+# a 1-D slope aligns with W: [C] with C != W does not broadcast
+case("refuse_PRelu_1d_channels", "refused", "PRelu", [x(*X), cf((3,), 41)], expect="refused")
+case("refuse_ConvPRelu_1d_channels", "refused", "Conv", [x(1, 3, 6, 5), cf((4, 3, 3, 3), 6), cf((4,), 7)],
+     {"kernel_shape": [3, 3], "pads": [1, 1, 1, 1]}, post=("PRelu", cf((4,), 9)[1]), expect="refused")
+case("refuse_PRelu_wider_slope", "refused", "PRelu", [x(3, 1, 1), x(2, 3, 10, 11)], expect="refused")
+
+VALUE_CASES = [k for k in CASES if k.expect == "value"]
+REFUSED_CASES = [k for k in CASES if k.expect == "refused"]
+BY_NAME = {k.name: k for k in CASES}
+
+
+def groups():
+    """{family: its value cases}; a family has one opset, so one model holds it."""
+    out: dict[str, list[Case]] = {}
+    for k in VALUE_CASES:
+        out.setdefault(k.family, []).append(k)
+    for fam, ks in out.items():
+        assert len({k.opset for k in ks}) == 1, fam
+    return out
+
+
+def _input_name(cs: Case, pos_: int):
+    kind, shape = cs.inputs[pos_]
+    return f"{cs.family}_{kind}{pos_}_{_tag(shape)}_s{cs.seed}"
+
+
+def _generate(name, kind, shape):
+    rng = np.random.default_rng(zlib.crc32(name.encode()))
+    if kind == "pos":
+        a = rng.random(shape) + 0.5
+    elif kind == "pm80":
+        a = rng.choice([-80.0, 80.0], size=shape) + rng.standard_normal(shape)
+    else:  # "x", "x3", "x4": standard normal, times 3 / 4 (wider activations)
+        a = rng.standard_normal(shape) * (float(kind[1:]) if len(kind) > 1 else 1.0)
+    return a.astype(np.float32)
+
+
+def output_names(cs: Case):
+    return [cs.name] if cs.n_out == 1 else [f"{cs.name}.{k}" for k in range(cs.n_out)]
+
+
+def build(cases):
+    """(model bytes, feeds, {case name: its graph outputs}) of one model holding
+    `cases`: cases of one family share the graph inputs they describe alike."""
+    cases = list(cases)
+    opset = cases[0].opset
+    assert all(k.opset == opset for k in cases)
+    b = M.Builder(0)
+    feeds, graph_in, graph_out, outs = {}, [], [], {}
+    for cs in cases:
+        names = []
+        for pos_, spec in enumerate(cs.inputs):
+            if spec is None:
+                names.append("")
+            elif spec[0] == "c":
+                names.append(b.const(spec[1]))
+            else:
+                n = _input_name(cs, pos_)
+                if n not in feeds:
+                    feeds[n] = _generate(n, *spec)
+                    graph_in.append((n, list(spec[1])))
+                names.append(n)
+        while names and names[-1] == "":
+            names.pop()
+        finals = output_names(cs)
+        if cs.post:
+            mid = b.name("mid")
+            b.nodes.append(R.make_node(cs.op, names, [mid], **cs.attrs))
+            b.nodes.append(R.make_node(cs.post[0], [mid, b.const(cs.post[1])], finals))
+        else:
+            b.nodes.append(R.make_node(cs.op, names, finals, **cs.attrs))
+        # MaxPool's Indices are asked for by naming them; only the values are graph outputs
+        outs[cs.name] = finals[:1] if cs.op == "MaxPool" else finals
+        graph_out += [(o, []) for o in outs[cs.name]]
+    return b.model(graph_in, graph_out, opset=opset), feeds, outs
+
+
+def operands(cs: Case, feeds):
+    """The case's operator inputs as arrays (None where omitted), in operator order."""
+    out = []
+    for pos_, spec in enumerate(cs.inputs):
+        out.append(None if spec is None else spec[1] if spec[0] == "c" else feeds[_input_name(cs, pos_)])
+    return out

@@ -1,0 +1,393 @@
+"""The ONNX oracle (oracle/onnx_ref.py) against an independent float64
+evaluation of every value case of the operator matrix (tests/op_cases.py):
+torch.nn.functional in double precision where torch has the operator, a
+direct numpy statement of the ONNX definition where it has not (asymmetric
+pads, the nearest modes, the coordinate transformations torch lacks).
+Nothing here calls back into onnx_ref for the expected value.
+
+Bars: data movement, MaxPool and nearest Resize compare equal; the rest agree
+to 1e-6 * max(1, |want|) per element (float64 against float64, both rounded
+to float32 once).  The refused cases must raise in the oracle too.
+"""
+import numpy as np
+import pytest
+
+import onnx_ref as R
+import op_cases as OC
+
+TOL = 1e-6
+
+
+def _t(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).double()
+
+
+def _f32(t):
+    return (t.numpy() if hasattr(t, "numpy") else np.asarray(t)).astype(np.float32)
+
+
+# ---- ONNX definitions torch has no operator for, stated directly ------------
+def _same_pads(size, k, s, d, lower):
+    """auto_pad SAME_*: the output is ceil(size / stride); the padding that needs, the odd one at the end (UPPER)."""
+    out = -(-size // s)
+    total = max((out - 1) * s + (k - 1) * d + 1 - size, 0)
+    small, big = total // 2, total - total // 2
+    return (big, small) if lower else (small, big)
+
+
+def _pool_pads(at, shape):
+    k, s, d = at["kernel_shape"], at.get("strides", [1, 1]), at.get("dilations", [1, 1])
+    ap = at.get("auto_pad", "NOTSET")
+    if ap in ("SAME_UPPER", "SAME_LOWER"):
+        (t, b), (l, r) = (_same_pads(shape[2 + i], k[i], s[i], d[i], ap == "SAME_LOWER") for i in range(2))
+        return [t, l, b, r]
+    return [0, 0, 0, 0] if ap == "VALID" else list(at.get("pads", [0, 0, 0, 0]))
+
+
+def _pool_numpy(xv, at, avg):
+    """ONNX MaxPool / AveragePool, window by window.  The padded input spans
+    [-pad_begin, size + pad_end); a ceil_mode window reaching past it is cut
+    there.  count_include_pad=1 divides by what is left of the window,
+    count_include_pad=0 by its taps on the input itself."""
+    k, s, d = at["kernel_shape"], at.get("strides", [1, 1]), at.get("dilations", [1, 1])
+    pt, pl, pb, pr = _pool_pads(at, xv.shape)
+    h, w = xv.shape[2:]
+
+    def out_size(size, p0, p1, kk, ss, dd):
+        span = size + p0 + p1 - ((kk - 1) * dd + 1)
+        o = (int(np.ceil(span / ss)) if at.get("ceil_mode", 0) else span // ss) + 1
+        return o - 1 if (o - 1) * ss >= size + p0 else o  # the last window must start on the input or its left pad
+    ho, wo = out_size(h, pt, pb, k[0], s[0], d[0]), out_size(w, pl, pr, k[1], s[1], d[1])
+    xx = xv.astype(np.float64)
+    out = np.empty(xv.shape[:2] + (ho, wo))
+    for oy in range(ho):
+        rows = [oy * s[0] - pt + i * d[0] for i in range(k[0])]
+        rows = [r for r in rows if r < h + pb]
+        for ox in range(wo):
+            cols = [ox * s[1] - pl + j * d[1] for j in range(k[1])]
+            cols = [q for q in cols if q < w + pr]
+            inside = [(r, q) for r in rows for q in cols if 0 <= r < h and 0 <= q < w]
+            vals = np.stack([xx[:, :, r, q] for r, q in inside], axis=-1)
+            if avg:
+                out[:, :, oy, ox] = vals.sum(-1) / (len(rows) * len(cols) if at.get("count_include_pad", 0) else len(inside))
+            else:
+                out[:, :, oy, ox] = vals.max(-1)
+    return out.astype(np.float32)
+
+
+def _pool_expected(cs, xv):
+    import torch.nn.functional as F
+    at = cs.attrs
+    avg = cs.op == "AveragePool"
+    pads = _pool_pads(at, xv.shape)
+    k, s, d = tuple(at["kernel_shape"]), tuple(at.get("strides", [1, 1])), tuple(at.get("dilations", [1, 1]))
+    if pads[0] != pads[2] or pads[1] != pads[3]:
+        return _pool_numpy(xv, at, avg)  # torch pads both sides alike
+    if avg:
+        return _f32(F.avg_pool2d(_t(xv), k, s, (pads[0], pads[1]), ceil_mode=bool(at.get("ceil_mode", 0)),
+                                 count_include_pad=bool(at.get("count_include_pad", 0))))
+    return _f32(F.max_pool2d(_t(xv), k, s, (pads[0], pads[1]), dilation=d, ceil_mode=bool(at.get("ceil_mode", 0))))
+
+
+def _resize_geometry(cs, ops):
+    """(ctm, nearest_mode, mode, [(in, out, scale in float32, scale in float64)] for H and W) of a
+    Resize / Upsample case: `sizes` mean the scale out / in, worked out in either precision."""
+    at = cs.attrs
+    xv = ops[0]
+    if cs.op == "Upsample":
+        ctm, nmode, scales, sizes = "asymmetric", "floor", ops[1], None
+    else:
+        ctm = at.get("coordinate_transformation_mode", "half_pixel")
+        nmode = at.get("nearest_mode", "round_prefer_floor")
+        scales = ops[2] if len(ops) > 2 and ops[2] is not None else None
+        sizes = ops[3] if len(ops) > 3 else None
+    dims = []
+    for ax in (2, 3):
+        n_in = xv.shape[ax]
+        if sizes is not None:
+            n_out = int(sizes[ax])
+            dims.append((n_in, n_out, np.float32(n_out) / np.float32(n_in), n_out / n_in))
+        else:
+            dims.append((n_in, int(np.floor(n_in * float(scales[ax]))), np.float32(scales[ax]), float(scales[ax])))
+    return ctm, nmode, at.get("mode", "nearest"), dims
+
+
+def _src_coord(o, n_in, n_out, scale, ctm, ft):
+    """x_original of output coordinate o (ONNX Resize), every operation in float type `ft`."""
+    o, half = ft(o), ft(0.5)
+    if ctm == "half_pixel":
+        return (o + half) / ft(scale) - half
+    if ctm == "pytorch_half_pixel":
+        return (o + half) / ft(scale) - half if n_out > 1 else ft(0)
+    if ctm == "align_corners":
+        return o * ft(n_in - 1) / ft(n_out - 1) if n_out > 1 else ft(0)
+    assert ctm == "asymmetric"
+    return o / ft(scale)
+
+
+def _nearest_index(v, nmode, n_in):
+    if nmode == "round_prefer_floor":
+        r = np.floor(v) if v - np.floor(v) <= 0.5 else np.ceil(v)   # halves go down
+    elif nmode == "round_prefer_ceil":
+        r = np.ceil(v) if v - np.floor(v) >= 0.5 else np.floor(v)   # halves go up
+    elif nmode == "floor":
+        r = np.floor(v)
+    else:
+        assert nmode == "ceil"
+        r = np.ceil(v)
+    return int(min(max(r, 0), n_in - 1))
+
+
+def _linear_index(v, n_in):
+    return int(np.floor(min(max(v, 0), n_in - 1)))
+
+
+def _resize_expected(cs, ops):
+    import torch.nn.functional as F
+    ctm, nmode, mode, dims = _resize_geometry(cs, ops)
+    xx = ops[0].astype(np.float64)
+    (h, ho, _, sh), (w, wo, _, sw) = dims
+    if mode == "linear" and ho > 1 and wo > 1 and ctm in ("half_pixel", "pytorch_half_pixel", "align_corners"):
+        # torch's bilinear: (o + 0.5) / scale - 0.5 clamped at 0 from below, or the corner-aligned map
+        kw = {"size": (ho, wo)} if cs.op == "Resize" and len(ops) > 3 else \
+            {"scale_factor": (sh, sw), "recompute_scale_factor": False}
+        return _f32(F.interpolate(_t(ops[0]), mode="bilinear", align_corners=ctm == "align_corners", **kw))
+    if mode == "nearest":
+        ys = [_nearest_index(_src_coord(o, h, ho, sh, ctm, np.float64), nmode, h) for o in range(ho)]
+        xs = [_nearest_index(_src_coord(o, w, wo, sw, ctm, np.float64), nmode, w) for o in range(wo)]
+        return xx[:, :, ys][:, :, :, xs].astype(np.float32)
+    out = np.empty(xx.shape[:2] + (ho, wo))
+    for oy in range(ho):
+        cy = min(max(_src_coord(oy, h, ho, sh, ctm, np.float64), 0.0), h - 1.0)
+        y0 = int(np.floor(cy))
+        y1, fy = min(y0 + 1, h - 1), cy - y0
+        for ox in range(wo):
+            cx = min(max(_src_coord(ox, w, wo, sw, ctm, np.float64), 0.0), w - 1.0)
+            x0 = int(np.floor(cx))
+            x1, fx = min(x0 + 1, w - 1), cx - x0
+            top = xx[:, :, y0, x0] * (1 - fx) + xx[:, :, y0, x1] * fx
+            bot = xx[:, :, y1, x0] * (1 - fx) + xx[:, :, y1, x1] * fx
+            out[:, :, oy, ox] = top * (1 - fy) + bot * fy
+    return out.astype(np.float32)
+
+
+def _onnx_slice_indices(length, start, end, step):
+    """The indices ONNX Slice takes from an axis of `length`."""
+    start = start + length if start < 0 else start
+    end = end + length if end < 0 else end
+    if step > 0:
+        start, end = min(max(start, 0), length), min(max(end, 0), length)
+    else:
+        start, end = min(max(start, 0), length - 1), min(max(end, -1), length - 1)
+    return list(range(start, end, step))
+
+
+def _slice_expected(cs, ops):
+    import torch
+    xv = ops[0]
+    if len(ops) == 1:
+        starts, ends, axes, steps = cs.attrs["starts"], cs.attrs["ends"], cs.attrs.get("axes"), None
+    else:
+        starts, ends = ops[1], ops[2]
+        axes = ops[3] if len(ops) > 3 else None
+        steps = ops[4] if len(ops) > 4 else None
+    axes = list(range(len(starts))) if axes is None else axes
+    steps = [1] * len(starts) if steps is None else steps
+    t = torch.from_numpy(xv)
+    for b, e, ax, st in zip(starts, ends, axes, steps):
+        ax = int(ax) % xv.ndim
+        idx = _onnx_slice_indices(xv.shape[ax], int(b), int(e), int(st))
+        t = t.index_select(ax, torch.tensor(idx, dtype=torch.long))
+    return t.numpy()
+
+
+def _pad_expected(cs, ops):
+    import torch.nn.functional as F
+    xv = ops[0]
+    r = xv.ndim
+    pads = [int(v) for v in (ops[1] if len(ops) > 1 else cs.attrs["pads"])]
+    value = float(ops[2]) if len(ops) > 2 and ops[2] is not None else cs.attrs.get("value", 0.0)
+    axes = [int(v) % r for v in ops[3]] if len(ops) > 3 else list(range(r))
+    lo, hi = [0] * r, [0] * r
+    for k, ax in enumerate(axes):
+        lo[ax], hi[ax] = pads[k], pads[k + len(axes)]
+    flat = []  # torch lists the last axis first; negative entries crop
+    for ax in reversed(range(r)):
+        flat += [lo[ax], hi[ax]]
+    return F.pad(_t(xv), flat, value=value).float().numpy()
+
+
+def expected(cs, ops):
+    """Outputs of the case (a list), evaluated independently of onnx_ref."""
+    import torch
+    import torch.nn.functional as F
+    op, at = cs.op, cs.attrs
+    xv = ops[0]
+    if op in ("MaxPool", "AveragePool"):
+        return [_pool_expected(cs, xv)]
+    if op in ("Resize", "Upsample"):
+        return [_resize_expected(cs, ops)]
+    if op == "Conv":  # + PRelu
+        y = F.conv2d(_t(xv), _t(ops[1]), _t(ops[2]), padding=1).float().double()  # the Conv's own float32 output
+        return [_f32(torch.where(y < 0, y * _t(cs.post[1]), y))]
+    if op == "Relu":
+        return [_f32(F.relu(_t(xv)))]
+    if op == "LeakyRelu":
+        return [_f32(F.leaky_relu(_t(xv), float(np.float32(at.get("alpha", 0.01)))))]
+    if op == "Sigmoid":
+        return [_f32(torch.sigmoid(_t(xv)))]
+    if op == "Tanh":
+        return [_f32(torch.tanh(_t(xv)))]
+    if op == "Clip":
+        lo = float(ops[1]) if len(ops) > 1 and ops[1] is not None else at.get("min")
+        hi = float(ops[2]) if len(ops) > 2 and ops[2] is not None else at.get("max")
+        return [_f32(torch.clamp(_t(xv), lo, hi)) if lo is not None or hi is not None else xv]
+    if op == "PRelu":
+        sl = ops[1]
+        if sl.size == 1 or (sl.ndim >= 3 and sl.shape[-3] == sl.size == xv.shape[1]):  # one value, or per channel
+            return [_f32(F.prelu(_t(xv), _t(sl).reshape(-1)))]
+        return [_f32(torch.where(_t(xv) < 0, _t(xv) * _t(sl), _t(xv)))]  # numpy-style broadcast of the slope
+    if op in ("Add", "Sub", "Mul", "Div"):
+        fn = {"Add": torch.add, "Sub": torch.sub, "Mul": torch.mul, "Div": torch.div}[op]
+        return [_f32(fn(_t(ops[0]), _t(ops[1])))]
+    if op == "Slice":
+        return [_slice_expected(cs, ops)]
+    if op == "Concat":
+        return [torch.cat([torch.from_numpy(o) for o in ops], dim=at["axis"]).numpy()]
+    if op == "Split":
+        ax = at.get("axis", 0)
+        n = xv.shape[ax]
+        if len(ops) > 1:
+            sizes = [int(v) for v in ops[1]]
+        elif "split" in at:
+            sizes = list(at["split"])
+        else:  # equal parts; opset 18: ceil-sized parts, the last one smaller
+            part = -(-n // cs.n_out)
+            sizes = [min(part, n - k * part) for k in range(cs.n_out)]
+            assert cs.opset >= 18 or n % cs.n_out == 0
+        return [t.numpy() for t in torch.split(torch.from_numpy(xv), sizes, dim=ax)]
+    if op == "Transpose":
+        return [torch.from_numpy(xv).permute(*at.get("perm", list(range(xv.ndim))[::-1])).contiguous().numpy()]
+    if op == "Pad":
+        return [_pad_expected(cs, ops)]
+    if op == "Squeeze":
+        axes = at.get("axes", ops[1] if len(ops) > 1 else None)
+        t = torch.from_numpy(xv)
+        for ax in sorted((int(a) % xv.ndim for a in axes), reverse=True) if axes is not None else ():
+            t = t.squeeze(ax)
+        return [(t if axes is not None else t.squeeze()).numpy()]
+    if op == "Unsqueeze":
+        axes = at.get("axes", ops[1] if len(ops) > 1 else None)
+        t = torch.from_numpy(xv)
+        for ax in sorted(int(a) % (xv.ndim + len(axes)) for a in axes):
+            t = t.unsqueeze(ax)
+        return [t.numpy()]
+    if op == "Flatten":
+        ax = at.get("axis", 1)
+        ax = ax + xv.ndim if ax < 0 else ax
+        return [torch.from_numpy(xv).reshape(int(np.prod(xv.shape[:ax], dtype=np.int64)), -1).numpy()]
+    if op == "Reshape":
+        shp = [xv.shape[k] if v == 0 else int(v) for k, v in enumerate(ops[1])]
+        return [torch.from_numpy(xv).reshape(shp).numpy()]
+    if op == "Gemm":
+        a, b = _t(ops[0]), _t(ops[1])
+        y = float(np.float32(at.get("alpha", 1.0))) * ((a.T if at.get("transA") else a) @ (b.T if at.get("transB") else b))
+        if len(ops) > 2:
+            y = y + float(np.float32(at.get("beta", 1.0))) * _t(ops[2])
+        return [_f32(y)]
+    if op == "MatMul":
+        return [_f32(torch.matmul(_t(ops[0]), _t(ops[1])))]
+    if op == "BatchNormalization":
+        w, b, mean, var = (_t(o) for o in ops[1:5])
+        return [_f32(F.batch_norm(_t(xv), mean, var, w, b, training=False, eps=float(np.float32(at.get("epsilon", 1e-5)))))]
+    if op == "InstanceNormalization":
+        eps = float(np.float32(at.get("epsilon", 1e-5)))
+        if int(np.prod(xv.shape[2:])) == 1:  # torch refuses single-element planes: (x - x) / sqrt(0 + eps) * w + b
+            return [np.broadcast_to(ops[2].reshape((1, -1) + (1,) * (xv.ndim - 2)), xv.shape).astype(np.float32)]
+        return [_f32(F.instance_norm(_t(xv), weight=_t(ops[1]), bias=_t(ops[2]), eps=eps))]
+    if op == "GlobalAveragePool":
+        return [_f32(_t(xv).flatten(2).mean(dim=2).reshape(xv.shape[:2] + (1,) * (xv.ndim - 2)))]
+    if op == "Softmax":
+        if cs.opset < 13:  # the input as a matrix [prod(:axis), prod(axis:)], each row normalised
+            ax = at.get("axis", 1) % xv.ndim
+            m = _t(xv).reshape(int(np.prod(xv.shape[:ax], dtype=np.int64)), -1)
+            return [_f32(F.softmax(m, dim=1).reshape(xv.shape))]
+        return [_f32(F.softmax(_t(xv), dim=at.get("axis", -1)))]
+    raise AssertionError(f"no independent evaluation for {op}")
+
+
+# ---- the tests ---------------------------------------------------------------
+_runs = {}
+
+
+def _oracle_outputs(cs):
+    """The oracle's outputs of the case, from one run of its whole family's model."""
+    if cs.family not in _runs:
+        fam = OC.groups()[cs.family]
+        data, feeds, outs = OC.build(fam)
+        try:
+            _runs[cs.family] = (feeds, outs, R.run(R.load(data), feeds), None)
+        except Exception as e:  # one broken case must not hide the others: run them one by one
+            _runs[cs.family] = (feeds, outs, None, e)
+    feeds, outs, got, err = _runs[cs.family]
+    if got is None:
+        data, feeds, outs = OC.build([cs])
+        got = R.run(R.load(data), feeds)
+    return feeds, [got[o] for o in outs[cs.name]]
+
+
+@pytest.mark.parametrize("name", [k.name for k in OC.VALUE_CASES])
+def test_oracle_matches_independent_f64(name):
+    cs = OC.BY_NAME[name]
+    feeds, got = _oracle_outputs(cs)
+    want = expected(cs, OC.operands(cs, feeds))
+    assert len(got) == len(want)
+    for k, (g, w) in enumerate(zip(got, want)):
+        assert g.dtype == np.float32 and w.dtype == np.float32, (name, k, g.dtype, w.dtype)
+        assert g.shape == w.shape, (name, k, g.shape, w.shape)
+        if cs.exact:
+            assert np.array_equal(g, w), (name, k, float(np.abs(g - w).max()))
+        else:
+            excess = np.abs(g.astype(np.float64) - w) - TOL * np.maximum(1.0, np.abs(w))
+            assert excess.max() <= 0, (name, k, float(np.abs(g.astype(np.float64) - w).max()))
+
+
+@pytest.mark.parametrize("name", [k.name for k in OC.REFUSED_CASES])
+def test_oracle_refuses(name):
+    cs = OC.BY_NAME[name]
+    data, feeds, _ = OC.build([cs])
+    with pytest.raises((ValueError, NotImplementedError), match=cs.post[0] if cs.post else cs.op):
+        R.run(R.load(data), feeds)
+
+
+RESIZE_INDEX_CASES = [k.name for k in OC.VALUE_CASES if k.op in ("Resize", "Upsample")]
+
+
+@pytest.mark.parametrize("name", RESIZE_INDEX_CASES)
+def test_resize_indices_agree_in_f32_and_f64(name):
+    """A condition on the inputs: k_resize works its source coordinates out in
+    float32 (as onnxruntime does), the oracle in float64.  A case is only
+    meaningful where both select the same source index for every output
+    coordinate (nearest: the index taken; linear: the lower neighbour)."""
+    cs = OC.BY_NAME[name]
+    data, feeds, _ = OC.build([cs])
+    ctm, nmode, mode, dims = _resize_geometry(cs, OC.operands(cs, feeds))
+    for n_in, n_out, scale32, scale64 in dims:
+        assert n_out >= 1
+        for o in range(n_out):
+            v32 = _src_coord(o, n_in, n_out, scale32, ctm, np.float32)
+            v64 = _src_coord(o, n_in, n_out, scale64, ctm, np.float64)
+            assert isinstance(v32, np.float32)
+            if mode == "nearest":
+                assert _nearest_index(v32, nmode, n_in) == _nearest_index(v64, nmode, n_in), (name, n_in, n_out, o, v32, v64)
+            else:
+                assert _linear_index(v32, n_in) == _linear_index(v64, n_in), (name, n_in, n_out, o, v32, v64)
+
+
+def test_matrix_covers_the_kernel_forms():
+    """Each kernel form the GPU file asserts has a case that names it."""
+    named = {k for cs in OC.VALUE_CASES for k in cs.kernels}
+    for form in ("k_resize<true>(", "k_resize<false>(", "k_gap_wave(", "k_gap(", "k_gemm<true>(", "k_gemm<false>(",
+                 "k_binary_planes(", "k_binary(", "k_copy_rows<true>(", "k_copy_rows<false>(", "k_copy(", "k_affine("):
+        assert form in named, form

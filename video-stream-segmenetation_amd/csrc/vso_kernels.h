@@ -138,8 +138,9 @@ struct PoolParams {
   const float* x;
   float* y;
   int N, C, H, W, Ho, Wo, kh, kw, sh, sw, dh, dw, pt, pl;
+  int He, We;             // H + bottom pad, W + right pad: where the padded input ends
   int max_mode;           // 1 max, 0 average
-  int count_include_pad;
+  int count_include_pad;  // divide by the window's taps inside the padded input [-pt, He) x [-pl, We)
 };
 
 struct RowParams {  // per-row reductions over `inner` contiguous elements (rows = N*C)

@@ -979,9 +979,13 @@ __device__ __forceinline__ void pool_body(const PoolParams& p, I total) {
     const I nc = t / (I)p.Ho;
     const float* xc = p.x + (long)nc * p.H * p.W;
     float m = -INFINITY, s = 0.f;
-    int cnt = 0;
+    // cnt: taps on the input; ny x nx: taps on the padded input (ceil_mode's
+    // last window may reach past it: those taps count for neither)
+    int cnt = 0, ny = 0, nx = 0;
+    for (int kx = 0; kx < p.kw; ++kx) nx += ox * p.sw - p.pl + kx * p.dw < p.We;
     for (int ky = 0; ky < p.kh; ++ky) {
       const int iy = oy * p.sh - p.pt + ky * p.dh;
+      ny += iy < p.He;
       if (iy < 0 || iy >= p.H) continue;
       for (int kx = 0; kx < p.kw; ++kx) {
         const int ix = ox * p.sw - p.pl + kx * p.dw;
@@ -992,7 +996,7 @@ __device__ __forceinline__ void pool_body(const PoolParams& p, I total) {
         ++cnt;
       }
     }
-    p.y[o] = p.max_mode ? m : s / (float)(p.count_include_pad ? p.kh * p.kw : (cnt > 0 ? cnt : 1));
+    p.y[o] = p.max_mode ? m : s / (float)(p.count_include_pad ? ny * nx : (cnt > 0 ? cnt : 1));
   }
 }
 

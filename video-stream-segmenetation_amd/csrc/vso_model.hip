@@ -379,6 +379,7 @@ struct Graph {
   std::vector<Node> nodes;
   std::map<std::string, Const> inits;
   std::vector<IO> inputs, outputs;
+  int64_t opset = 0;  // the default domain's opset_import version (0: none stated)
 };
 
 bool parse_model(const uint8_t* data, size_t n, Graph* g, std::string* err) {
@@ -386,6 +387,20 @@ bool parse_model(const uint8_t* data, size_t n, Graph* g, std::string* err) {
   uint32_t f, wt;
   bool have_graph = false;
   while (m.more() && m.key(f, wt)) {
+    if (f == 8) {  // opset_import: OperatorSetIdProto {domain = 1, version = 2}
+      PB op = m.sub();
+      std::string domain;
+      int64_t version = 0;
+      uint32_t f2, w2;
+      while (op.more() && op.key(f2, w2)) {
+        if (f2 == 1) domain = op.str();
+        else if (f2 == 2) version = (int64_t)op.varint();
+        else op.skip(w2);
+      }
+      if (op.bad) { *err = "malformed OperatorSetIdProto"; return false; }
+      if (domain.empty() || domain == "ai.onnx") g->opset = std::max(g->opset, version);
+      continue;
+    }
     if (f != 7) { m.skip(wt); continue; }
     have_graph = true;
     PB gp = m.sub();
@@ -930,10 +945,13 @@ struct Planner {
       if (!sl || !sl->is_const) return false;
       const int64_t n = sl->c.numel();
       if (n != 1 && n != channels) return false;
-      // slope must vary along the channel axis only ([C], [C,1,1], [1,C,1,1], or one value)
-      int nontriv = 0;
-      for (int64_t d : sl->c.dims) nontriv += d > 1;
-      if (nontriv > 1) return false;
+      // the slope must be per channel under ONNX broadcasting against NCHW:
+      // [C,1,1], [1,C,1,1] or one value ([C] aligns with W: left to k_binary)
+      const std::vector<int64_t>& sd = sl->c.dims;
+      if (n != 1) {
+        const size_t r = sd.size();
+        if (r < 3 || r > 4 || sd[r - 3] != n) return false;
+      }
       ep->act = ACT_PRELU;
       ep->slope = upload(sl->c);
       ep->slope_stride = n == 1 ? 0 : 1;
@@ -1640,7 +1658,15 @@ struct Planner {
     }
     if (is_act(op)) {
       Epilogue ep{};
-      if (op == "PRelu") return plan_binary(nd, x, in[1], BIN_PRELU);
+      if (op == "PRelu") {
+        // unidirectional: the slope broadcasts to x, never x to the slope
+        const std::vector<int64_t>& ss = in[1]->shape;
+        bool uni = ss.size() <= xs.size();
+        for (size_t d = 0; uni && d < ss.size(); ++d)
+          uni = ss[d] == 1 || ss[d] == xs[d + xs.size() - ss.size()];
+        if (!uni) return fail("PRelu '" + nd.name + "': slope does not broadcast to the input");
+        return plan_binary(nd, x, in[1], BIN_PRELU);
+      }
       if (!act_of(nd, &ep, 0)) return fail(op + " '" + nd.name + "': non-constant parameters");
       UnaryParams p{};
       p.x = dptr(*x);
@@ -1658,6 +1684,9 @@ struct Planner {
       if (xs.size() != 4) return fail(op + ": 2D only");
       std::vector<int64_t> k = nd.ais("kernel_shape"), st = nd.ais("strides"), dl = nd.ais("dilations"), pd = nd.ais("pads");
       if (k.size() != 2) return fail(op + ": kernel_shape must be 2D");
+      if (!pd.empty() && pd.size() != 4) return fail(op + ": pads must have 4 values");
+      if (nd.ai("storage_order", 0) != 0) return fail(op + ": storage_order 1 is not supported");
+      if (nd.out.size() > 1 && !nd.out[1].empty()) return fail(op + ": the Indices output is not supported");
       PoolParams p{};
       p.N = (int)xs[0]; p.C = (int)xs[1]; p.H = (int)xs[2]; p.W = (int)xs[3];
       p.kh = (int)k[0]; p.kw = (int)k[1];
@@ -1678,6 +1707,7 @@ struct Planner {
         pt = lo[0]; pl = lo[1]; pb = hi[0]; pr = hi[1];
       }
       p.pt = pt; p.pl = pl;
+      p.He = p.H + pb; p.We = p.W + pr;
       const bool ceil_mode = nd.ai("ceil_mode", 0) != 0;
       auto osz = [&](int i, int p0, int p1, int kk, int ss, int dd) {
         const int num = i + p0 + p1 - dd * (kk - 1) - 1;
@@ -1745,12 +1775,18 @@ struct Planner {
       return true;
     }
     if (op == "Softmax") {
-      int64_t ax = nd.ai("axis", -1);
-      if (ax < 0) ax += (int64_t)xs.size();
-      if (ax != (int64_t)xs.size() - 1) return fail("Softmax: last axis only");
+      // opset 13 on: along `axis` (default -1), here the last axis only.  Before:
+      // the input flattened to 2-D at `axis` (default 1), each row normalised.
+      const bool flat = g.opset > 0 && g.opset < 13;
+      const int64_t rk = (int64_t)xs.size();
+      int64_t ax = nd.ai("axis", flat ? 1 : -1);
+      if (ax < 0) ax += rk;
+      if (ax < 0 || ax >= rk) return fail("Softmax: axis out of range");
+      if (!flat && ax != rk - 1) return fail("Softmax: last axis only");
       RowParams p{};
       p.x = dptr(*x);
-      p.inner = xs.back();
+      p.inner = 1;
+      for (int64_t d = ax; d < rk; ++d) p.inner *= xs[d];
       p.rows = x->numel() / std::max<int64_t>(p.inner, 1);
       if (!set_runtime(nd.out[0], xs)) return false;
       p.y = dptr(vals[nd.out[0]]);
@@ -1783,20 +1819,29 @@ struct Planner {
       }
       const size_t rk = xs.size();
       std::vector<int64_t> axes;
-      if (in.size() > 3 && in[3]) axes = in[3]->c.i;
+      if (in.size() > 3 && in[3]) {
+        if (!in[3]->is_const) return fail("Pad: constant axes only");
+        axes = in[3]->c.i;
+      }
       std::vector<int64_t> pb(rk, 0), pe(rk, 0);
       if (axes.empty()) {
         if (pads.size() != 2 * rk) return fail("Pad: pads length");
         for (size_t d = 0; d < rk; ++d) { pb[d] = pads[d]; pe[d] = pads[d + rk]; }
       } else {
+        if (pads.size() != 2 * axes.size()) return fail("Pad: pads length");
         for (size_t k = 0; k < axes.size(); ++k) {
           const int64_t a = axes[k] < 0 ? axes[k] + (int64_t)rk : axes[k];
+          if (a < 0 || a >= (int64_t)rk) return fail("Pad: axis out of range");
           pb[a] = pads[k];
           pe[a] = pads[k + axes.size()];
         }
       }
       std::vector<int64_t> os(rk), start(rk);
-      for (size_t d = 0; d < rk; ++d) { os[d] = xs[d] + pb[d] + pe[d]; start[d] = -pb[d]; }
+      for (size_t d = 0; d < rk; ++d) {
+        os[d] = xs[d] + pb[d] + pe[d];
+        start[d] = -pb[d];
+        if (os[d] < 0) return fail("Pad: negative pads remove more than the axis holds");
+      }
       if (!set_runtime(nd.out[0], os)) return false;
       return plan_copy_into(dptr(*x), xs, dptr(vals[nd.out[0]]), os, os, std::vector<int64_t>(rk, 0), start,
                             std::vector<int64_t>(rk, 1), {}, value);
@@ -1851,9 +1896,15 @@ struct Planner {
       if (in.size() > 1 && in[1]) sp = in[1]->c.i;
       const int64_t k = (int64_t)nd.out.size();
       if (sp.empty()) {
+        // opset 18: ceil-sized parts, the last one smaller; before, even parts only
+        if (xs[ax] % k != 0 && g.opset > 0 && g.opset < 18)
+          return fail("Split '" + nd.name + "': uneven default split needs opset 18");
         const int64_t part = (xs[ax] + k - 1) / k;
-        for (int64_t q = 0; q < k; ++q) sp.push_back(std::min(part, xs[ax] - q * part));
+        for (int64_t q = 0; q < k; ++q) sp.push_back(std::max<int64_t>(0, std::min(part, xs[ax] - q * part)));
       }
+      int64_t sum = 0;
+      for (int64_t v : sp) sum += v;
+      if ((int64_t)sp.size() != k || sum != xs[ax]) return fail("Split '" + nd.name + "': sizes do not add up to the axis");
       int64_t off = 0;
       for (int64_t q = 0; q < k; ++q) {
         std::vector<int64_t> os = xs;
@@ -1929,8 +1980,17 @@ struct Planner {
       else if (ctm == "align_corners") p.ctm = 2;
       else if (ctm == "asymmetric") p.ctm = 3;
       else return fail("Resize: coordinate_transformation_mode " + ctm);
-      const std::string nm = nd.as("nearest_mode", "round_prefer_floor");
-      p.nearest = nm == "round_prefer_floor" ? 0 : nm == "round_prefer_ceil" ? 1 : nm == "floor" ? 2 : 3;
+      // Upsample (opset 7-9) has neither attribute: y[o] = x[floor(o / scale)]
+      const std::string nm = nd.as("nearest_mode", op == "Upsample" ? "floor" : "round_prefer_floor");
+      if (nm == "round_prefer_floor") p.nearest = 0;
+      else if (nm == "round_prefer_ceil") p.nearest = 1;
+      else if (nm == "floor") p.nearest = 2;
+      else if (nm == "ceil") p.nearest = 3;
+      else return fail("Resize: nearest_mode " + nm);
+      if (nd.ai("antialias", 0) != 0) return fail("Resize: antialias is not supported");
+      if (nd.has("axes")) return fail("Resize: axes is not supported");
+      if (nd.as("keep_aspect_ratio_policy", "stretch") != "stretch")
+        return fail("Resize: keep_aspect_ratio_policy " + nd.as("keep_aspect_ratio_policy", "") + " is not supported");
       p.x = dptr(*x);
       if (!set_runtime(nd.out[0], {xs[0], xs[1], p.Ho, p.Wo})) return false;
       p.y = dptr(vals[nd.out[0]]);
