@@ -519,6 +519,50 @@ int vss_background_set_blur(vss_background* bg, int radius, double sigma);
  * VSS_E_INVALID_ARG. */
 int vss_background_set_mode(vss_background* bg, int mode);
 
+/* Edge-aware alpha at frame size (csrc/vss_matte.hip): a fast guided filter
+ * (He & Sun).  The plain A above is the bilinear upscale of the mask's alpha
+ * bytes: at 1080p one mask pixel covers 7.5 x 7.5 frame pixels and the person's
+ * outline is a ramp about 15 pixels wide wherever the edge really is.  With
+ * refinement on, linear coefficients of the alpha against the frame's luma are
+ * fitted at mask resolution, upsampled and applied to the luma at frame
+ * resolution, which puts the edge where the frame has it.  Off by default;
+ * independent of the colour / image / blur mode.  Definition, for a frame
+ * fh x fw, alpha bytes p[H][W], radius r in 1..8 (mask pixels), eps in
+ * [1, 65025] (the u8^2 scale):
+ *  1. Luma: Y = (77 R + 150 G + 29 B + 128) >> 8, integer, 0..255.
+ *  2. Guide: L[i][j] = the area mean of Y over rows [i*fh/H, (i+1)*fh/H) and
+ *     columns [j*fw/W, (j+1)*fw/W) (integer division), rounded half up:
+ *     L = (sum Y + cnt/2) / cnt.  Needs fh >= H and fw >= W.
+ *  3. Window sums over [i-r, i+r] x [j-r, j+r] clipped to the mask, N its pixel
+ *     count: S_L = sum L, S_p = sum p, S_Lp = sum L*p, S_LL = sum L*L (each
+ *     below 2^25).
+ *  4. Fit, in 64-bit integers, then doubles, no contraction:
+ *     cov = N*S_Lp - S_L*S_p;  var = N*S_LL - S_L^2 (>= 0);
+ *     a = (double)cov / ((double)var + eps * (double)(N*N));
+ *     b = ((double)S_p - a * (double)S_L) / (double)N, the product rounded first.
+ *  5. Quantise: a_q = (int32)floor(a*65536 + 0.5), b_q = (int32)floor(b*256 +
+ *     0.5), so that the second box filter is an integer sum in any order.
+ *     |a| <= 127.5 / (2 sqrt(eps)) <= 64: a_q, b_q and 289-term sums fit int32.
+ *  6. Mean over the same clipped window: abar = (float)((double)sum a_q /
+ *     (double)(N*65536)), bbar = (float)((double)sum b_q / (double)(N*256)).
+ *  7. Apply: abar and bbar upsampled to the frame size by
+ *     vss_mask_to_frame_device's recipe (the half-pixel taps and three f32 fma
+ *     lerps); q = abar_up * (float)Y + bbar_up in f32, the product rounded
+ *     before the sum; A = (uint32)floorf(fminf(fmaxf(q, 0), 255) + 0.5f).
+ *  8. The blend above runs with this A, in every mode.
+ * A flat guide has var = 0, a = 0: A is the box-smoothed alpha.  A constant
+ * alpha c gives A = c exactly.  tests/matte_ref.py restates all of it in numpy
+ * and the GPU matches it bit for bit.
+ * radius 0: off (eps ignored).  VSS_E_INVALID_ARG for a radius outside 0..8 or,
+ * with radius >= 1, an eps outside [1, 65025], NaN or infinite.  Takes effect
+ * from the next composite.  A composite with refinement on and a frame smaller
+ * than the mask in either direction fails with VSS_E_INVALID_ARG.  The planes
+ * (17 B per mask pixel and frame) belong to the object, grow with n and count
+ * into vss_info.device_bytes. */
+#define VSS_REFINE_MAX_RADIUS 8
+/* The entry points of the refinement (the setter, and the frame-size alpha
+ * plane alone) are declared in vss_matte.h, which this header includes. */
+
 /* The blur's weights w[0 .. 2*radius] (centre at w[radius]); host-only, no GPU
  * needed.  With g_k = exp(-k^2 / (2 sigma^2)): w[k] = floor(65536 g_k / sum(g)
  * + 0.5) off the centre, and the centre takes 65536 - the rest, so the table
@@ -545,5 +589,7 @@ int vss_segment_background(vss_handle* h, vss_post_state* st, vss_background* bg
 #ifdef __cplusplus
 }
 #endif
+
+#include "vss_matte.h"
 
 #endif /* VSS_H_ */

@@ -8,7 +8,15 @@ the four interleaved round by round so that drift hits all alike; the spread
 of the yardstick's per-round medians; each mode's algorithmic bytes and the
 share of 8 TB/s they imply at the measured time.  Prints one JSON line.
 
-    python tools/bench_background.py [--radius 7 --sigma 2.5 --rounds 5 --calls 8]
+    python tools/bench_background.py [--radius 7 --sigma 2.5 --rounds 5 --calls 8] [--refine R,EPS]
+
+--refine R,EPS (opt-in; without it the output is what it always was) adds, in
+the same interleaved rounds: the three modes with the edge-aware matte on
+(colour_refined, image_refined, blur_refined; each with its ratio to its own
+unrefined mode), and the frame-size alpha plane alone with refinement off and
+on (alpha_plain, alpha_refined).  The mask-resolution stage has no entry point
+of its own: matte_stage_us is alpha_refined - alpha_plain, an upper estimate
+(the refined alpha kernel also reads the frame, which the plain one does not).
 
 Needs a GPU: there is no fall-back.
 """
@@ -47,6 +55,12 @@ def algorithmic_bytes(mode, n, fh, fw, fc, H, W):
     return base + px * (fc + 4) + px * 4   # blur: the horizontal pass (frame in, RGBX out), RGBX back in
 
 
+def refined_extra_bytes(n, fh, fw, fc, H, W):
+    """What refinement adds: the guide pass reads the frame once more; per mask pixel L out and in,
+    p in, (a_q, b_q) out and in, (abar, bbar) out and in, in place of nothing (the alpha bytes stay)."""
+    return n * fh * fw * fc + n * H * W * (1 + 1 + 1 + 8 + 8 + 8 + 8)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--radius", type=int, default=7)
@@ -54,9 +68,16 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--calls", type=int, default=8, help="timed calls per mode and round")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--refine", default=None, metavar="R,EPS", help="also time the edge-aware matte (opt-in)")
     a = ap.parse_args()
     if a.rounds * a.calls < 20:
         ap.error("at least 20 timed calls per mode (rounds * calls)")
+    refine = None
+    if a.refine:
+        try:
+            refine = (int(a.refine.split(",")[0]), float(a.refine.split(",")[1]))
+        except (ValueError, IndexError):
+            ap.error("--refine takes R,EPS, e.g. 4,16")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("bench_background: no GPU")
@@ -65,6 +86,8 @@ def main():
     rng = np.random.default_rng(0)
     result = {"bench": "background", "n": n, "radius": a.radius, "sigma": a.sigma,
               "timed_calls_per_mode": a.rounds * a.calls, "sizes": {}}
+    if refine:
+        result["refine"] = {"radius": refine[0], "eps": refine[1]}
     with pkg.Session(model_h=H, model_w=W, dtype="bf16x2", max_batch=n, autotune=False) as s:
         # a stream of its own: handle 0 (the null stream) would send the calls to the session's stream,
         # away from the events
@@ -78,15 +101,29 @@ def main():
             bgs["image"].set_image(rng.integers(0, 256, (720, 1280, 3), dtype=np.uint8))
             bgs["blur"].set_blur(a.radius, a.sigma)
             geo = (n, fh, fw, fc, fw * fc, fh * fw * fc)
+            if refine:
+                for m in ("colour", "image", "blur"):
+                    bgs[m + "_refined"] = pkg.Background(s)
+                bgs["image_refined"].set_image(rng.integers(0, 256, (720, 1280, 3), dtype=np.uint8))
+                bgs["blur_refined"].set_blur(a.radius, a.sigma)
+                bgs["alpha_plain"], bgs["alpha_refined"] = pkg.Background(s), pkg.Background(s)
+                for m in ("colour_refined", "image_refined", "blur_refined", "alpha_refined"):
+                    bgs[m].set_refine(*refine)
+                dal = torch.empty((n, fh, fw), dtype=torch.uint8, device="cuda")
 
             def call(mode):
                 if mode == "composite":
                     pkg.composite_device(s, df.data_ptr(), *geo, da.data_ptr(), do.data_ptr(), stream=stream)
+                elif mode.startswith("alpha_"):
+                    pkg.background_alpha_device(s, bgs[mode], df.data_ptr(), *geo, da.data_ptr(), dal.data_ptr(),
+                                                stream=stream)
                 else:
                     pkg.background_composite_device(s, bgs[mode], df.data_ptr(), *geo, da.data_ptr(), do.data_ptr(),
                                                     stream=stream)
 
             modes = ("composite", "colour", "image", "blur")
+            if refine:  # the default modes stay first and warm up last-but-these, so `check` below is still blur's
+                modes = ("colour_refined", "image_refined", "blur_refined", "alpha_plain", "alpha_refined") + modes
             for m in modes:
                 for _ in range(a.warmup):
                     call(m)
@@ -113,15 +150,27 @@ def main():
             for m in modes:
                 flat = [t for rr in times[m] for t in rr]
                 med = statistics.median(flat)
-                by = algorithmic_bytes(m, n, fh, fw, fc, H, W)
+                if m.startswith("alpha_"):
+                    by = n * fh * fw + n * H * W + (n * fh * fw * fc if m == "alpha_refined" else 0)
+                else:
+                    by = algorithmic_bytes(m.replace("_refined", ""), n, fh, fw, fc, H, W)
+                if m.endswith("_refined"):
+                    by += refined_extra_bytes(n, fh, fw, fc, H, W)
                 rounds = [statistics.median(rr) for rr in times[m]]
                 out[m] = {"median_us": round(med, 2), "round_medians_us": [round(v, 2) for v in rounds],
                           "bytes": by, "bytes_per_px": round(by / (n * fh * fw), 3),
                           "hbm_fraction": round(by / (med * 1e-6) / HBM_BYTES_PER_S, 4)}
             base = out["composite"]
             base["spread"] = round(max(base["round_medians_us"]) / min(base["round_medians_us"]) - 1, 4)
-            for m in modes[1:]:
+            for m in ("colour", "image", "blur"):
                 out[m]["ratio_to_composite"] = round(out[m]["median_us"] / base["median_us"], 3)
+                if refine:
+                    rm = out[m + "_refined"]
+                    rm["ratio_to_unrefined"] = round(rm["median_us"] / out[m]["median_us"], 3)
+                    rm["bytes_ratio_to_unrefined"] = round(rm["bytes"] / out[m]["bytes"], 3)
+                    rm["spread"] = round(max(rm["round_medians_us"]) / min(rm["round_medians_us"]) - 1, 4)
+            if refine:
+                out["matte_stage_us"] = round(out["alpha_refined"]["median_us"] - out["alpha_plain"]["median_us"], 2)
             result["sizes"][f"{fw}x{fh}"] = out
             for b in bgs.values():
                 b.close()

@@ -179,6 +179,9 @@ def lib() -> ctypes.CDLL:
                 "vss_background_set_image": ([P, P, I, I, I, S], I),
                 "vss_background_set_blur": ([P, I, ctypes.c_double], I),
                 "vss_background_set_mode": ([P, I], I),
+                "vss_background_set_refine": ([P, I, ctypes.c_double], I),
+                "vss_background_alpha_device": ([P, P, P, I, I, I, I, S, S, P, P, S, S, P], I),
+                "vss_background_alpha_device_at": ([P, P, P, I, I, I, I, S, S, P, I, I, P, S, S, P], I),
                 "vss_blur_weights": ([I, ctypes.c_double, P], I),
                 "vss_background_composite_device": ([P, P, P, I, I, I, I, S, S, P, P, S, S, P], I),
                 "vss_segment_background": ([P, P, P, P, I, I, I, I, S, P], I),
@@ -668,6 +671,12 @@ class Background:
         """Back to VSS_BG_COLOR / _IMAGE / _BLUR with what that mode was last given."""
         _check(lib().vss_background_set_mode(self._bg, int(mode)), self.session._h)
 
+    def set_refine(self, radius: int, eps: float = 16.0):
+        """Edge-aware alpha (vss_background_set_refine): a guided filter of the alpha by
+        the frame's luma, radius 1..8 mask pixels, eps in [1, 65025]; radius 0 = off
+        (the default).  Independent of the mode; from the next composite."""
+        _check(lib().vss_background_set_refine(self._bg, int(radius), float(eps)), self.session._h)
+
 
 def background_composite_device(session: Session, bg: Background, frames_ptr: int, n: int, h: int, w: int, c: int,
                                 row_stride: int, frame_stride: int, alpha_u8_ptr: int, out_ptr: int,
@@ -677,6 +686,24 @@ def background_composite_device(session: Session, bg: Background, frames_ptr: in
     _check(lib().vss_background_composite_device(session._h, bg._bg, frames_ptr, n, h, w, c, row_stride,
                                                  frame_stride, alpha_u8_ptr, out_ptr, ors,
                                                  out_frame_stride or ors * h, stream or None), session._h)
+
+
+def background_alpha_device(session: Session, bg: Background, frames_ptr: int, n: int, h: int, w: int, c: int,
+                            row_stride: int, frame_stride: int, alpha_u8_ptr: int, out_ptr: int,
+                            out_row_stride: int = 0, out_frame_stride: int = 0, stream: int = 0, mask_hw=None):
+    """HBM in/out: the frame-size alpha bytes [n][h][w] that `bg`'s composite blends with.
+    mask_hw: the alpha bytes' own (H, W) where they are not the session's model size."""
+    ors = out_row_stride or w
+    mh, mw = mask_hw or (session.mask_h, session.mask_w)
+    if mask_hw is None:
+        rc = lib().vss_background_alpha_device(session._h, bg._bg, frames_ptr, n, h, w, c, row_stride, frame_stride,
+                                               alpha_u8_ptr, out_ptr, ors, out_frame_stride or ors * h,
+                                               stream or None)
+    else:
+        rc = lib().vss_background_alpha_device_at(session._h, bg._bg, frames_ptr, n, h, w, c, row_stride,
+                                                  frame_stride, alpha_u8_ptr, int(mh), int(mw), out_ptr, ors,
+                                                  out_frame_stride or ors * h, stream or None)
+    _check(rc, session._h)
 
 
 def blur_weights(radius: int, sigma: float) -> np.ndarray:

@@ -22,6 +22,10 @@
 //                          with the alpha upscale and the blend: the blurred
 //                          frame never goes to HBM.
 // Edges replicate.  The sums stay below 2^32 (65536 * 255 + 32768).
+// Every k_bg_composite also has a REFINE form (the edge-aware matte,
+// vss_matte.hip): only where A comes from changes — two bilinear fetches of the
+// (abar, bbar) plane applied to the luma of the frame bytes the thread loads
+// anyway, in place of the one of the alpha bytes.
 #include <hip/hip_runtime.h>
 
 #include "vss_kernels.h"
@@ -30,8 +34,11 @@ namespace vss {
 
 namespace {
 
-// 4 consecutive pixels x0.. of row y of frame t over bg[4] (r | g<<8 | b<<16)
-__device__ __forceinline__ void blend_quad(const CompositeParams& p, int t, int y, int x0, const uint32_t (&bg)[4]) {
+// 4 consecutive pixels x0.. of row y of frame t over bg[4] (r | g<<8 | b<<16);
+// REFINE: the alpha from frame t's (abar, bbar) taps m (pixel_alpha, vss_kernels.h)
+template <bool REFINE>
+__device__ __forceinline__ void blend_quad(const CompositeParams& p, const MatteTaps& m, int t, int y, int x0,
+                                           const uint32_t (&bg)[4]) {
 #pragma clang fp contract(off)
   int ya, yb;
   float ly;
@@ -39,6 +46,12 @@ __device__ __forceinline__ void blend_quad(const CompositeParams& p, int t, int 
   const uint8_t* a = p.alpha + (long)t * p.H * p.W;
   const uint8_t* ra = a + (long)ya * p.W;
   const uint8_t* rb = a + (long)yb * p.W;
+  const float2* ma = nullptr;
+  const float2* mb = nullptr;
+  if constexpr (REFINE) {
+    ma = m.p + (ya - m.row0) * m.pitch;
+    mb = m.p + (yb - m.row0) * m.pitch;
+  }
   const uint8_t* f = p.frames + (long)t * p.frame_stride + (long)y * p.row_stride;
   uint32_t px[4];
 #pragma unroll
@@ -47,10 +60,8 @@ __device__ __forceinline__ void blend_quad(const CompositeParams& p, int t, int 
     int xa, xb;
     float lx;
     up_coord(x, p.sx, p.W, xa, xb, lx);
-    const float a00 = ra[xa], a01 = ra[xb], a10 = rb[xa], a11 = rb[xb];
-    const float top = __builtin_fmaf(a01 - a00, lx, a00), bot = __builtin_fmaf(a11 - a10, lx, a10);
-    const uint32_t A = (uint32_t)floorf(__builtin_fmaf(bot - top, ly, top) + 0.5f);
     const uint8_t* q = f + (long)x * p.fc;
+    const uint32_t A = pixel_alpha<REFINE>(ra, rb, ma, mb, xa, xb, m.col0, lx, ly, q);
     uint32_t o = 0xFF000000u;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -71,13 +82,18 @@ constexpr int kBlurTW = 64, kBlurTH = 32;  // k_bg_composite<BLUR>'s tile: 16 x 
 
 }  // namespace
 
-template <int MODE>
+template <int MODE, bool REFINE>
 __global__ __launch_bounds__(256) void k_bg_composite(BgCompositeParams p) {
   const CompositeParams& c = p.c;
   const int t = blockIdx.z;
   if constexpr (MODE != kBgBlur) {
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     const int x0 = (blockIdx.x * 64 + (threadIdx.x & 63)) * 4;
+    MatteTaps m{};
+    if constexpr (REFINE) {
+      __shared__ float2 taps[kMatteTapRows * kMatteTapCols];
+      m = stage_matte_taps(c, p.ab + (long)t * c.H * c.W, blockIdx.y * 4, blockIdx.x * 256, taps);
+    }
     if (y >= c.fh || x0 >= c.fw) return;
     uint32_t bg[4];
     if constexpr (MODE == kBgColor) {
@@ -91,7 +107,7 @@ __global__ __launch_bounds__(256) void k_bg_composite(BgCompositeParams p) {
       bg[2] = (d1 >> 16) | ((d2 & 0xFFu) << 16);
       bg[3] = d2 >> 8;
     }
-    blend_quad(c, t, y, x0, bg);
+    blend_quad<REFINE>(c, m, t, y, x0, bg);
   } else {
     extern __shared__ __align__(16) uint32_t tile[];  // [kBlurTH + 2r][kBlurTW] RGBX, then the r + 1 weights
     const int r = p.radius, rows = kBlurTH + 2 * r;
@@ -99,6 +115,8 @@ __global__ __launch_bounds__(256) void k_bg_composite(BgCompositeParams p) {
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int X0 = blockIdx.x * kBlurTW, Y0 = blockIdx.y * kBlurTH;
     const uint32_t* h = p.hblur + (long)t * c.fh * c.fw;
+    // REFINE: the taps straight from the plane (a 64 x 32 tile's window is up to 34 x 66 taps on top of the blur's tile)
+    const MatteTaps m = {REFINE ? p.ab + (long)t * c.H * c.W : nullptr, c.W, 0, 0};
     for (int i = tid; i < rows * kBlurTW; i += 256) {
       const int yy = min(max(Y0 - r + i / kBlurTW, 0), c.fh - 1), xx = min(X0 + i % kBlurTW, c.fw - 1);
       tile[i] = h[(long)yy * c.fw + xx];
@@ -127,7 +145,7 @@ __global__ __launch_bounds__(256) void k_bg_composite(BgCompositeParams p) {
       uint32_t bg[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) bg[k] = (acc[k][0] >> 16) | ((acc[k][1] >> 16) << 8) | ((acc[k][2] >> 16) << 16);
-      blend_quad(c, t, y, x0, bg);
+      blend_quad<REFINE>(c, m, t, y, x0, bg);
     }
   }
 }
@@ -188,14 +206,24 @@ void launch_blur_h(const BlurHParams& p, int n, hipStream_t s) {
 
 void launch_bg_composite(const BgCompositeParams& p, int mode, int n, hipStream_t s) {
   const dim3 grid((p.c.fw + 255) / 256, (p.c.fh + 3) / 4, n);
+  const bool refine = p.ab != nullptr;
   if (mode == kBgColor) {
-    hipLaunchKernelGGL(k_bg_composite<kBgColor>, grid, dim3(256), 0, s, p);
+    if (refine)
+      hipLaunchKernelGGL((k_bg_composite<kBgColor, true>), grid, dim3(256), 0, s, p);
+    else
+      hipLaunchKernelGGL((k_bg_composite<kBgColor, false>), grid, dim3(256), 0, s, p);
   } else if (mode == kBgImage) {
-    hipLaunchKernelGGL(k_bg_composite<kBgImage>, grid, dim3(256), 0, s, p);
+    if (refine)
+      hipLaunchKernelGGL((k_bg_composite<kBgImage, true>), grid, dim3(256), 0, s, p);
+    else
+      hipLaunchKernelGGL((k_bg_composite<kBgImage, false>), grid, dim3(256), 0, s, p);
   } else {
     const size_t lds = ((size_t)(kBlurTH + 2 * p.radius) * kBlurTW + p.radius + 1) * 4;
-    hipLaunchKernelGGL(k_bg_composite<kBgBlur>, dim3((p.c.fw + kBlurTW - 1) / kBlurTW, (p.c.fh + kBlurTH - 1) / kBlurTH, n),
-                       dim3(256), lds, s, p);
+    const dim3 bgrid((p.c.fw + kBlurTW - 1) / kBlurTW, (p.c.fh + kBlurTH - 1) / kBlurTH, n);
+    if (refine)
+      hipLaunchKernelGGL((k_bg_composite<kBgBlur, true>), bgrid, dim3(256), lds, s, p);
+    else
+      hipLaunchKernelGGL((k_bg_composite<kBgBlur, false>), bgrid, dim3(256), lds, s, p);
   }
 }
 

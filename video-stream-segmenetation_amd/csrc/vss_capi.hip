@@ -3146,6 +3146,10 @@ struct vss_background {
   size_t hblur_bytes = 0;
   int radius = 0;
   uint16_t w[kBlurMaxRadius + 1] = {};  // taps 0 (centre) .. radius
+  int refine_radius = 0;         // the edge-aware matte: 0 = off
+  double refine_eps = 0.0;
+  uint8_t* d_matte = nullptr;    // its planes for n frames: (abar, bbar), (a_q, b_q), L; grown on demand
+  size_t matte_bytes = 0;
   hipEvent_t last = nullptr;     // recorded after every composite
   hipStream_t last_stream = nullptr;
   bool used = false;
@@ -3224,6 +3228,52 @@ int bg_quiesce(vss_background* bg) {
   return VSS_OK;
 }
 
+// bg->mu held.  The matte's mask-resolution stage for these frames (refinement
+// on): *ab = the (abar, bbar) plane the frame-resolution kernels apply.
+int matte_enqueue(vss_handle* h, vss_background* bg, const uint8_t* d_frames, int n, int fh, int fw, int fc, size_t rs,
+                  size_t fs, const uint8_t* d_alpha, int H, int W, hipStream_t s, const float2** ab) {
+  if (fh < H || fw < W)
+    return fail(h, VSS_E_INVALID_ARG, "refinement needs a frame no smaller than the mask (" + std::to_string(H) +
+                                          " x " + std::to_string(W) + "); turn it off for smaller frames");
+  if (W > 16384) return fail(h, VSS_E_INVALID_ARG, "refinement: mask wider than 16384");
+  const size_t px = (size_t)n * H * W, need = px * 17;  // float2 + int2 + u8 per mask pixel
+  if (need > bg->matte_bytes) {
+    int rc = bg_quiesce(bg);
+    if (!rc) rc = bg_alloc(bg, &bg->d_matte, &bg->matte_bytes, need);
+    if (rc) return rc;
+  }
+  MatteParams m{};
+  m.frames = d_frames;
+  m.row_stride = (long)rs;
+  m.frame_stride = (long)fs;
+  m.fh = fh; m.fw = fw; m.fc = fc;
+  m.alpha = d_alpha;
+  m.H = H; m.W = W;
+  m.radius = bg->refine_radius;
+  m.eps = bg->refine_eps;
+  m.ab = reinterpret_cast<float2*>(bg->d_matte);
+  m.q = reinterpret_cast<int2*>(bg->d_matte + px * 8);
+  m.L = bg->d_matte + px * 16;
+  launch_matte_stage(m, n, s);
+  *ab = m.ab;
+  return VSS_OK;
+}
+
+void composite_params(CompositeParams* c, const uint8_t* d_frames, int fh, int fw, int fc, size_t rs, size_t fs,
+                      const uint8_t* d_alpha, int H, int W, uint8_t* d_out, size_t ors, size_t ofs) {
+  c->frames = d_frames;
+  c->row_stride = (long)rs;
+  c->frame_stride = (long)fs;
+  c->fh = fh; c->fw = fw; c->fc = fc;
+  c->alpha = d_alpha;
+  c->H = H; c->W = W;
+  c->sy = (float)c->H / (float)fh;
+  c->sx = (float)c->W / (float)fw;
+  c->out = d_out;
+  c->out_row_stride = (long)ors;
+  c->out_frame_stride = (long)ofs;
+}
+
 // bg->mu held
 int bg_enqueue(vss_handle* h, vss_background* bg, const uint8_t* d_frames, int n, int fh, int fw, int fc, size_t rs,
                size_t fs, const uint8_t* d_alpha, uint8_t* d_out, size_t ors, size_t ofs, hipStream_t s) {
@@ -3234,18 +3284,12 @@ int bg_enqueue(vss_handle* h, vss_background* bg, const uint8_t* d_frames, int n
   // the previous composite (and the image it may have scaled) ran on another stream
   if (bg->used && bg->last_stream != s) HIP_TRY(h, hipStreamWaitEvent(s, bg->last, 0));
   BgCompositeParams p{};
-  p.c.frames = d_frames;
-  p.c.row_stride = (long)rs;
-  p.c.frame_stride = (long)fs;
-  p.c.fh = fh; p.c.fw = fw; p.c.fc = fc;
-  p.c.alpha = d_alpha;
-  p.c.H = h->cfg.model_h; p.c.W = h->cfg.model_w;
-  p.c.sy = (float)p.c.H / (float)fh;
-  p.c.sx = (float)p.c.W / (float)fw;
-  p.c.out = d_out;
-  p.c.out_row_stride = (long)ors;
-  p.c.out_frame_stride = (long)ofs;
+  composite_params(&p.c, d_frames, fh, fw, fc, rs, fs, d_alpha, h->cfg.model_h, h->cfg.model_w, d_out, ors, ofs);
   p.color = bg->color;
+  if (bg->refine_radius) {
+    const int rc = matte_enqueue(h, bg, d_frames, n, fh, fw, fc, rs, fs, d_alpha, p.c.H, p.c.W, s, &p.ab);
+    if (rc) return rc;
+  }
   if (bg->mode == VSS_BG_IMAGE) {
     if (bg->img_fh != fh || bg->img_fw != fw) {  // (re)build the cached scaled image
       const size_t need = (size_t)bg_image_stride(fw) * fh;
@@ -3329,6 +3373,7 @@ void vss_background_destroy(vss_background* bg) {
   (void)bg_alloc(bg, &bg->d_src, &bg->src_bytes, 0);
   (void)bg_alloc(bg, &bg->d_img, &bg->img_bytes, 0);
   (void)bg_alloc(bg, &bg->d_hblur, &bg->hblur_bytes, 0);
+  (void)bg_alloc(bg, &bg->d_matte, &bg->matte_bytes, 0);
   if (bg->last) (void)hipEventDestroy(bg->last);
   delete bg;
 }
@@ -3389,6 +3434,60 @@ int vss_background_set_blur(vss_background* bg, int radius, double sigma) {
   for (int k = 0; k <= radius; ++k) bg->w[k] = w[radius + k];
   bg->radius = radius;
   bg->mode = VSS_BG_BLUR;
+  return VSS_OK;
+}
+
+int vss_background_set_refine(vss_background* bg, int radius, double eps) {
+  if (!bg) return fail(nullptr, VSS_E_INVALID_ARG, "null background");
+  if (radius < 0 || radius > VSS_REFINE_MAX_RADIUS)
+    return fail(bg->h, VSS_E_INVALID_ARG, "refine radius must be 0 (off) or in [1, 8]");
+  if (radius && !(eps >= 1.0 && eps <= 65025.0))  // NaN fails both
+    return fail(bg->h, VSS_E_INVALID_ARG, "refine eps must be in [1, 65025]");
+  std::lock_guard<std::mutex> lk(bg->mu);
+  bg->refine_radius = radius;
+  bg->refine_eps = radius ? eps : 0.0;
+  return VSS_OK;
+}
+
+int vss_background_alpha_device(vss_handle* h, vss_background* bg, const uint8_t* d_frames, int n, int height,
+                                int width, int channels, size_t row_stride, size_t frame_stride,
+                                const uint8_t* d_alpha_u8, uint8_t* d_out_alpha, size_t out_row_stride,
+                                size_t out_frame_stride, void* stream) {
+  if (!h) return fail(nullptr, VSS_E_INVALID_ARG, "null handle");
+  return vss_background_alpha_device_at(h, bg, d_frames, n, height, width, channels, row_stride, frame_stride,
+                                        d_alpha_u8, h->cfg.model_h, h->cfg.model_w, d_out_alpha, out_row_stride,
+                                        out_frame_stride, stream);
+}
+
+int vss_background_alpha_device_at(vss_handle* h, vss_background* bg, const uint8_t* d_frames, int n, int height,
+                                   int width, int channels, size_t row_stride, size_t frame_stride,
+                                   const uint8_t* d_alpha_u8, int mask_h, int mask_w, uint8_t* d_out_alpha,
+                                   size_t out_row_stride, size_t out_frame_stride, void* stream) {
+  if (!h) return fail(nullptr, VSS_E_INVALID_ARG, "null handle");
+  if (mask_h < 1 || mask_w < 1) return fail(h, VSS_E_INVALID_ARG, "mask_h / mask_w must be >= 1");
+  if (!bg || bg->h != h) return fail(h, VSS_E_INVALID_ARG, "handle / background mismatch");
+  if (!d_frames || !d_alpha_u8 || !d_out_alpha) return fail(h, VSS_E_INVALID_ARG, "null device pointer");
+  int rc = check_frames(h, n, height, width, channels, row_stride, frame_stride,
+                        std::max(h->cfg.max_batch, h->user_max_batch));
+  if (rc) return rc;
+  if (out_row_stride < (size_t)width || out_frame_stride < out_row_stride * height)
+    return fail(h, VSS_E_INVALID_ARG, "bad alpha output geometry (row stride >= width)");
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  std::lock_guard<std::mutex> lk(bg->mu);
+  if (bg->used && bg->last_stream != s) HIP_TRY(h, hipStreamWaitEvent(s, bg->last, 0));
+  MatteAlphaParams p{};
+  composite_params(&p.c, d_frames, height, width, channels, row_stride, frame_stride, d_alpha_u8, mask_h, mask_w,
+                   d_out_alpha, out_row_stride, out_frame_stride);
+  if (bg->refine_radius && (rc = matte_enqueue(h, bg, d_frames, n, height, width, channels, row_stride, frame_stride,
+                                               d_alpha_u8, mask_h, mask_w, s, &p.ab)))
+    return rc;
+  launch_matte_alpha(p, n, s);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, VSS_E_HIP, std::string("alpha launch: ") + hipGetErrorString(e));
+  HIP_TRY(h, hipEventRecord(bg->last, s));
+  bg->last_stream = s;
+  bg->used = true;
   return VSS_OK;
 }
 

@@ -533,8 +533,70 @@ constexpr int kBlurMaxRadius = 32;
 // the cached scaled image: RGB, 3 B per pixel, rows padded so that every
 // thread's 4 pixels are 3 whole dwords
 __host__ __device__ constexpr long bg_image_stride(int fw) { return (long)((fw + 3) / 4) * 12; }
+// One pixel's alpha at frame resolution.  REFINE = false: k_composite's, the
+// half-pixel bilinear of the mask's alpha bytes (rows ra / rb of the u8 plane).
+// REFINE = true (the edge-aware matte, include/vss.h): the same bilinear of the
+// two coefficient planes (rows ma / mb of the interleaved (abar, bbar) plane),
+// applied to the pixel's luma, A = floor(clamp(abar * Y + bbar, 0, 255) + 0.5),
+// the product rounded before the sum.  rgb = the pixel's frame bytes.
+__device__ __forceinline__ uint32_t matte_luma(const uint8_t* rgb) {
+  return (77u * rgb[0] + 150u * rgb[1] + 29u * rgb[2] + 128u) >> 8;
+}
+template <bool REFINE>
+__device__ __forceinline__ uint32_t pixel_alpha(const uint8_t* ra, const uint8_t* rb, const float2* ma,
+                                                const float2* mb, int xa, int xb, int col0, float lx, float ly,
+                                                const uint8_t* rgb) {
+#pragma clang fp contract(off)
+  if constexpr (REFINE) {
+    const float2 v00 = ma[xa - col0], v01 = ma[xb - col0], v10 = mb[xa - col0], v11 = mb[xb - col0];
+    const float ta = __builtin_fmaf(v01.x - v00.x, lx, v00.x), ba = __builtin_fmaf(v11.x - v10.x, lx, v10.x);
+    const float tb = __builtin_fmaf(v01.y - v00.y, lx, v00.y), bb = __builtin_fmaf(v11.y - v10.y, lx, v10.y);
+    const float au = __builtin_fmaf(ba - ta, ly, ta), bu = __builtin_fmaf(bb - tb, ly, tb);
+    const float prod = au * (float)matte_luma(rgb);
+    const float q = prod + bu;
+    return (uint32_t)floorf(fminf(fmaxf(q, 0.f), 255.f) + 0.5f);
+  } else {
+    const float a00 = ra[xa], a01 = ra[xb], a10 = rb[xa], a11 = rb[xb];
+    const float top = __builtin_fmaf(a01 - a00, lx, a00), bot = __builtin_fmaf(a11 - a10, lx, a10);
+    return (uint32_t)floorf(__builtin_fmaf(bot - top, ly, top) + 0.5f);
+  }
+}
+
+// Where a kernel reads one frame's (abar, bbar) taps: element (row, col) of the
+// mask plane is p[(row - row0) * pitch + col - col0].  The plane itself in HBM
+// (row0 = col0 = 0, pitch = W), or a workgroup's window of it staged in LDS.
+struct MatteTaps {
+  const float2* p;
+  int pitch, row0, col0;
+};
+// A workgroup of k_composite's shape (frame rows Y0 .. Y0 + 3, pixels X0 .. X0 +
+// 255) reads mask rows ya(Y0) .. yb(Y0 + 3) and columns xa(X0) .. xb(X0 + 255):
+// with a frame no smaller than the mask, at most 5 rows and 257 columns.  They
+// are staged in LDS once, so that the four 8-B taps of every pixel are LDS
+// reads (most lanes of a wave share them) instead of global gathers.  Every
+// thread of the workgroup calls it (one barrier).
+constexpr int kMatteTapRows = 6, kMatteTapCols = 260;
+__device__ __forceinline__ MatteTaps stage_matte_taps(const CompositeParams& c, const float2* plane, int Y0, int X0,
+                                                      float2* tile) {
+  int r0, r1, c0, c1, unused;
+  float l;
+  up_coord(Y0, c.sy, c.H, r0, unused, l);
+  up_coord(min(Y0 + 3, c.fh - 1), c.sy, c.H, unused, r1, l);
+  up_coord(X0, c.sx, c.W, c0, unused, l);
+  up_coord(min(X0 + 255, c.fw - 1), c.sx, c.W, unused, c1, l);
+  // fh >= H and fw >= W (the host's check): the clamps never bind; they keep the loop inside the tile
+  const int R = min(r1 - r0 + 1, kMatteTapRows), C = min(c1 - c0 + 1, kMatteTapCols);
+  for (int k = threadIdx.x; k < R * C; k += 256) {
+    const int r = k / C, col = k - r * C;
+    tile[r * kMatteTapCols + col] = plane[(long)(r0 + r) * c.W + c0 + col];
+  }
+  __syncthreads();
+  return {tile, kMatteTapCols, r0, c0};
+}
+
 struct BgCompositeParams {
   CompositeParams c;       // frames, alpha, output: as k_composite
+  const float2* ab;        // refinement on: [n][H][W] (abar, bbar), k_matte_mean's output; else null
   uint32_t color;          // COLOR: r | g << 8 | b << 16
   const uint8_t* image;    // IMAGE: [fh][bg_image_stride(fw)] RGB at frame size
   const uint32_t* hblur;   // BLUR: [n][fh][fw] RGBX, the horizontal pass
@@ -561,6 +623,34 @@ struct BgResizeParams {
   int fh, fw;
 };
 void launch_bg_resize(const BgResizeParams& p, hipStream_t s);
+
+// Edge-aware matte (vss_matte.hip; the definition: include/vss.h): a guided
+// filter of the alpha bytes by the frame's luma.  The mask-resolution stage —
+// k_matte_guide (L = the area mean of the luma per mask pixel), k_matte_coeff
+// (the window sums and the f64 fit, quantised) and k_matte_mean (their box
+// mean) — leaves the (abar, bbar) plane that k_bg_composite<.., REFINE> and
+// k_matte_alpha apply at frame resolution.
+constexpr int kMatteMaxRadius = 8;
+struct MatteParams {
+  const uint8_t* frames;   // [n] frames, row_stride / frame_stride bytes, fc = 3 or 4
+  long row_stride, frame_stride;
+  int fh, fw, fc;          // fh >= H, fw >= W
+  const uint8_t* alpha;    // [n][H][W] u8 (the post chain's alpha bytes)
+  int H, W;
+  int radius;              // 1 .. kMatteMaxRadius, mask pixels
+  double eps;              // [1, 65025]
+  uint8_t* L;              // [n][H][W] scratch: the low-resolution guide
+  int2* q;                 // [n][H][W] scratch: (a_q, b_q)
+  float2* ab;              // [n][H][W] out: (abar, bbar)
+};
+void launch_matte_stage(const MatteParams& p, int n, hipStream_t s);
+
+// The frame-resolution alpha plane alone: ab != null the refined alpha, else k_composite's.
+struct MatteAlphaParams {
+  CompositeParams c;       // frames, alpha, geometry; out = [n] u8 planes, out_row_stride / out_frame_stride bytes
+  const float2* ab;
+};
+void launch_matte_alpha(const MatteAlphaParams& p, int n, hipStream_t s);
 
 // Queued host path: only the frame rows the resize reads, pinned host -> HBM
 // (vss_stage.hip).  rows: device list of the row indices; src / dst = frame 0.

@@ -40,6 +40,7 @@
 //   backgroundSetColor(background, r, g, b)
 //   backgroundSetImage(background, pixels: Uint8Array, height, width, channels, rowStride)
 //   backgroundSetBlur(background, radius, sigma), backgroundDestroy(background)
+//   backgroundSetRefine(background, radius, eps)   the edge-aware alpha; radius 0 = off
 //   segmentBackground(handle, post, frames, n, height, width, channels, rowStride, background)
 //       -> Promise<Uint8Array>   opaque RGBA frames, the person over the background
 //   ortCreate(modelBytes: Uint8Array, inputDims: number[] | null, deviceId, convPrecision) -> session
@@ -589,6 +590,21 @@ napi_value BackgroundSetBlur(napi_env env, napi_callback_info info) {
   napi_get_value_double(env, argv[2], &sigma);
   const int rc = vss_background_set_blur(b->bg, radius, sigma);
   if (rc != VSS_OK) throw_vss(env, "vss_background_set_blur", rc, vss_last_error(b->hd->h));
+  return nullptr;
+}
+
+napi_value BackgroundSetRefine(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Bg* b = argc >= 3 ? get_bg(env, argv[0]) : nullptr;
+  if (!b) return nullptr;
+  int radius = 0;
+  double eps = 0.0;
+  napi_get_value_int32(env, argv[1], &radius);
+  napi_get_value_double(env, argv[2], &eps);
+  const int rc = vss_background_set_refine(b->bg, radius, eps);
+  if (rc != VSS_OK) throw_vss(env, "vss_background_set_refine", rc, vss_last_error(b->hd->h));
   return nullptr;
 }
 
@@ -1905,6 +1921,7 @@ napi_value Init(napi_env env, napi_value exports) {
       {"backgroundSetColor", nullptr, BackgroundSetColor, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"backgroundSetImage", nullptr, BackgroundSetImage, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"backgroundSetBlur", nullptr, BackgroundSetBlur, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"backgroundSetRefine", nullptr, BackgroundSetRefine, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"backgroundDestroy", nullptr, BackgroundDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"segmentBackground", nullptr, SegmentBackground, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ortCreate", nullptr, OrtCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
