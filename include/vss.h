@@ -591,5 +591,6 @@ int vss_segment_background(vss_handle* h, vss_post_state* st, vss_background* bg
 #endif
 
 #include "vss_matte.h"
+#include "vss_video.h"
 
 #endif /* VSS_H_ */

@@ -18,6 +18,16 @@ on (alpha_plain, alpha_refined).  The mask-resolution stage has no entry point
 of its own: matte_stage_us is alpha_refined - alpha_plain, an upper estimate
 (the refined alpha kernel also reads the frame, which the plain one does not).
 
+--nv12 (opt-in) adds a leg for the NV12 video I/O, 8 x 1080p resident in HBM, in
+interleaved rounds of its own: the two conversion kernels alone (nv12_unpack,
+nv12_pack: median, algorithmic bytes, achieved GB/s), k_bg_composite<COLOR> over
+the same RGBA frames (colour_rgba: the yardstick of a streaming kernel in this
+run), vss_video_process_device in colour mode (video_process), and the same
+frames, already RGBA, through vss_segment_device + vss_postprocess_device +
+vss_background_composite_device as before NV12 existed (rgba_path).
+nv12_overhead_us is video_process - rgba_path: both conversions and the RGBA
+round trip through the scratch.
+
 Needs a GPU: there is no fall-back.
 """
 import argparse
@@ -61,6 +71,91 @@ def refined_extra_bytes(n, fh, fw, fc, H, W):
     return n * fh * fw * fc + n * H * W * (1 + 1 + 1 + 8 + 8 + 8 + 8)
 
 
+def nv12_leg(pkg, torch, s, a, n, H, W):
+    """The --nv12 leg (see the module docstring) -> its result dict."""
+    fh, fw = 1080, 1920
+    rng = np.random.default_rng(1)
+    st = torch.cuda.Stream()
+    stream = st.cuda_stream
+    dy = torch.from_numpy(rng.integers(0, 256, (n, fh, fw), dtype=np.uint8)).cuda()
+    duv = torch.from_numpy(rng.integers(0, 256, (n, fh // 2, fw), dtype=np.uint8)).cuda()
+    oy, ouv = torch.empty_like(dy), torch.empty_like(duv)
+    drgba = torch.empty((n, fh, fw, 4), dtype=torch.uint8, device="cuda")
+    dout = torch.empty_like(drgba)
+    masks = torch.empty((n, H * W), dtype=torch.float32, device="cuda")
+    alpha = torch.empty((n, H * W), dtype=torch.uint8, device="cuda")
+    bg, bg2 = pkg.Background(s), pkg.Background(s)   # colour mode, one per path
+    chain, chain2 = pkg.PostChain(s), pkg.PostChain(s)
+    video = pkg.Video(s, "bt709")
+    ygeo = (dy.data_ptr(), fw, fw * fh, duv.data_ptr(), fw, fw * fh // 2)
+    ogeo = (oy.data_ptr(), fw, fw * fh, ouv.data_ptr(), fw, fw * fh // 2)
+    rgeo = (n, fh, fw, 4, fw * 4, fh * fw * 4)
+
+    def call(mode):
+        if mode == "nv12_unpack":
+            pkg.nv12_to_rgba_device(s, "bt709", *ygeo, n, fh, fw, drgba.data_ptr(), stream=stream)
+        elif mode == "nv12_pack":
+            pkg.rgba_to_nv12_device(s, "bt709", drgba.data_ptr(), 0, 0, n, fh, fw, *ogeo, stream=stream)
+        elif mode == "colour_rgba":
+            pkg.background_composite_device(s, bg2, drgba.data_ptr(), *rgeo, alpha.data_ptr(), dout.data_ptr(),
+                                            stream=stream)
+        elif mode == "video_process":
+            video.process_device(chain, bg, *ygeo, n, fh, fw, *ogeo, stream=stream)
+        else:  # rgba_path
+            s.segment_device(drgba.data_ptr(), *rgeo, masks.data_ptr(), stream)
+            chain2.process_device(drgba.data_ptr(), *rgeo, masks.data_ptr(), 0, alpha.data_ptr(), stream)
+            pkg.background_composite_device(s, bg2, drgba.data_ptr(), *rgeo, alpha.data_ptr(), dout.data_ptr(),
+                                            stream=stream)
+
+    # each entry reads what an earlier one wrote
+    modes = ("nv12_unpack", "rgba_path", "colour_rgba", "nv12_pack", "video_process")
+    for m in modes:
+        for _ in range(a.warmup):
+            call(m)
+    torch.cuda.synchronize()
+    times = {m: [[] for _ in range(a.rounds)] for m in modes}
+    for r in range(a.rounds):
+        pairs = []
+        for _ in range(a.calls):
+            for m in modes:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(st)
+                call(m)
+                e1.record(st)
+                pairs.append((m, e0, e1))
+        torch.cuda.synchronize()
+        for m, e0, e1 in pairs:
+            times[m][r].append(e0.elapsed_time(e1) * 1e3)  # us
+    px = n * fh * fw
+    conv_bytes = px + px // 2 + px * 4
+    out = {"width": fw, "height": fh, "n": n}
+    for m in modes:
+        flat = [t for rr in times[m] for t in rr]
+        med = statistics.median(flat)
+        rounds = [statistics.median(rr) for rr in times[m]]
+        out[m] = {"median_us": round(med, 2), "round_medians_us": [round(v, 2) for v in rounds],
+                  "spread": round(max(rounds) / min(rounds) - 1, 4)}
+        by = {"nv12_unpack": conv_bytes, "nv12_pack": conv_bytes,
+              "colour_rgba": algorithmic_bytes("colour", n, fh, fw, 4, H, W)}.get(m)
+        if by:
+            out[m].update({"bytes": by, "gb_per_s": round(by / (med * 1e-6) / 1e9, 1),
+                           "hbm_fraction": round(by / (med * 1e-6) / HBM_BYTES_PER_S, 4)})
+    out["nv12_overhead_us"] = round(out["video_process"]["median_us"] - out["rgba_path"]["median_us"], 2)
+    # the conversions are deterministic: pack(unpack(in)) twice gives the same planes
+    call("nv12_unpack")
+    call("nv12_pack")
+    torch.cuda.synchronize()
+    ref_planes = (oy.clone(), ouv.clone())
+    call("nv12_unpack")
+    call("nv12_pack")
+    torch.cuda.synchronize()
+    if not (torch.equal(ref_planes[0], oy) and torch.equal(ref_planes[1], ouv)):
+        raise SystemExit("bench_background: the NV12 output changed between two runs of the same call")
+    for o in (video, chain, chain2, bg, bg2):
+        o.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--radius", type=int, default=7)
@@ -69,6 +164,7 @@ def main():
     ap.add_argument("--calls", type=int, default=8, help="timed calls per mode and round")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--refine", default=None, metavar="R,EPS", help="also time the edge-aware matte (opt-in)")
+    ap.add_argument("--nv12", action="store_true", help="also time the NV12 video I/O at 8 x 1080p (opt-in)")
     a = ap.parse_args()
     if a.rounds * a.calls < 20:
         ap.error("at least 20 timed calls per mode (rounds * calls)")
@@ -174,6 +270,8 @@ def main():
             result["sizes"][f"{fw}x{fh}"] = out
             for b in bgs.values():
                 b.close()
+        if a.nv12:
+            result["nv12"] = nv12_leg(pkg, torch, s, a, n, H, W)
     print(json.dumps(result))
 
 

@@ -185,6 +185,13 @@ def lib() -> ctypes.CDLL:
                 "vss_blur_weights": ([I, ctypes.c_double, P], I),
                 "vss_background_composite_device": ([P, P, P, I, I, I, I, S, S, P, P, S, S, P], I),
                 "vss_segment_background": ([P, P, P, P, I, I, I, I, S, P], I),
+                "vss_nv12_to_rgba_device": ([P, I, P, S, S, P, S, S, I, I, I, P, S, S, P], I),
+                "vss_rgba_to_nv12_device": ([P, I, P, S, S, I, I, I, P, S, S, P, S, S, P], I),
+                "vss_video_create": ([P, I, ctypes.POINTER(P)], I),
+                "vss_video_destroy": ([P], None),
+                "vss_video_set_standard": ([P, I], I),
+                "vss_video_process_device": ([P, P, P, P, S, S, P, S, S, I, I, I, P, S, S, P, S, S, P], I),
+                "vss_video_process": ([P, P, P, P, P, I, I, I, P, P], I),
             }
             for name, (args, res) in sig.items():
                 fn = getattr(L, name)
@@ -246,10 +253,11 @@ class Session:
         self._tickets = {}
         self._posts = []
         self._backgrounds = []
+        self._videos = []
 
     # -- lifecycle --------------------------------------------------------
     def close(self):
-        for p in getattr(self, "_posts", []) + getattr(self, "_backgrounds", []):
+        for p in getattr(self, "_videos", []) + getattr(self, "_posts", []) + getattr(self, "_backgrounds", []):
             p.close()
         if getattr(self, "_h", None):
             lib().vss_destroy(self._h)
@@ -704,6 +712,95 @@ def background_alpha_device(session: Session, bg: Background, frames_ptr: int, n
                                                   frame_stride, alpha_u8_ptr, int(mh), int(mw), out_ptr, ors,
                                                   out_frame_stride or ors * h, stream or None)
     _check(rc, session._h)
+
+
+VSS_CSC_BT601_LIMITED, VSS_CSC_BT709_LIMITED, VSS_CSC_BT601_FULL, VSS_CSC_BT709_FULL = 0, 1, 2, 3
+CSC_STANDARDS = {"bt601": VSS_CSC_BT601_LIMITED, "bt709": VSS_CSC_BT709_LIMITED,
+                 "bt601-full": VSS_CSC_BT601_FULL, "bt709-full": VSS_CSC_BT709_FULL}
+
+
+def _csc(standard) -> int:
+    """A name of CSC_STANDARDS or a VSS_CSC_* value (range-checked by the library)."""
+    if isinstance(standard, str):
+        if standard not in CSC_STANDARDS:
+            raise VssError(VSS_E_INVALID_ARG, f"standard must be one of {sorted(CSC_STANDARDS)}")
+        return CSC_STANDARDS[standard]
+    return int(standard)
+
+
+def _as_nv12(y, uv):
+    """y [N,H,W] uint8 and uv [N,H/2,W] uint8 (U, V interleaved), H and W even -> contiguous arrays."""
+    ya, ua = np.asarray(y), np.asarray(uv)
+    if ya.dtype != np.uint8 or ua.dtype != np.uint8 or ya.ndim != 3 or ua.ndim != 3:
+        raise VssError(VSS_E_INVALID_ARG, "y must be uint8 [N,H,W] and uv uint8 [N,H/2,W]")
+    n, hh, ww = ya.shape
+    if hh < 2 or ww < 2 or hh % 2 or ww % 2:
+        raise VssError(VSS_E_INVALID_ARG, "NV12 needs an even height and width, both >= 2")
+    if ua.shape != (n, hh // 2, ww):
+        raise VssError(VSS_E_INVALID_ARG, f"uv must be [N,H/2,W] = {(n, hh // 2, ww)}, got {ua.shape}")
+    return np.ascontiguousarray(ya), np.ascontiguousarray(ua)
+
+
+def nv12_to_rgba_device(session: Session, standard, y_ptr: int, y_pitch: int, y_frame_stride: int, uv_ptr: int,
+                        uv_pitch: int, uv_frame_stride: int, n: int, h: int, w: int, rgba_ptr: int,
+                        row_stride: int = 0, frame_stride: int = 0, stream: int = 0):
+    """HBM in/out: NV12 planes -> packed RGBA (alpha 255), include/vss_video.h."""
+    rs = row_stride or w * 4
+    _check(lib().vss_nv12_to_rgba_device(session._h, _csc(standard), y_ptr or None, y_pitch, y_frame_stride,
+                                         uv_ptr or None, uv_pitch, uv_frame_stride, n, h, w, rgba_ptr or None, rs,
+                                         frame_stride or rs * h, stream or None), session._h)
+
+
+def rgba_to_nv12_device(session: Session, standard, rgba_ptr: int, row_stride: int, frame_stride: int, n: int,
+                        h: int, w: int, y_ptr: int, y_pitch: int, y_frame_stride: int, uv_ptr: int, uv_pitch: int,
+                        uv_frame_stride: int, stream: int = 0):
+    """HBM in/out: packed RGBA (alpha ignored) -> NV12 planes."""
+    rs = row_stride or w * 4
+    _check(lib().vss_rgba_to_nv12_device(session._h, _csc(standard), rgba_ptr or None, rs, frame_stride or rs * h,
+                                         n, h, w, y_ptr or None, y_pitch, y_frame_stride, uv_ptr or None, uv_pitch,
+                                         uv_frame_stride, stream or None), session._h)
+
+
+class Video:
+    """NV12 in, NV12 out (include/vss_video.h): a decoder's frames through the
+    seam, a PostChain and a Background back to an encoder's layout in one call.
+    Owns the RGBA scratch between the stages; one call in flight per object."""
+
+    def __init__(self, session: Session, standard="bt709"):
+        self.session = session
+        v = ctypes.c_void_p()
+        _check(lib().vss_video_create(session._h, _csc(standard), ctypes.byref(v)), session._h)
+        self._v = v
+        session._videos.append(self)
+
+    def close(self):
+        if getattr(self, "_v", None):
+            lib().vss_video_destroy(self._v)
+            self._v = None
+
+    def set_standard(self, standard):
+        _check(lib().vss_video_set_standard(self._v, _csc(standard)), self.session._h)
+
+    def process(self, y: np.ndarray, uv: np.ndarray, chain: PostChain, bg: Background):
+        """Host NV12: y [N,H,W] u8 and uv [N,H/2,W] u8 (U, V interleaved), consecutive
+        frames of chain's stream -> (y, uv) of the person over `bg`; synchronous."""
+        ya, ua = _as_nv12(y, uv)
+        n, hh, ww = ya.shape
+        oy, ouv = np.empty_like(ya), np.empty_like(ua)
+        _check(lib().vss_video_process(self._v, chain._st, bg._bg, ya.ctypes.data, ua.ctypes.data, n, hh, ww,
+                                       oy.ctypes.data, ouv.ctypes.data), self.session._h)
+        return oy, ouv
+
+    def process_device(self, chain: PostChain, bg: Background, y_ptr: int, y_pitch: int, y_frame_stride: int,
+                       uv_ptr: int, uv_pitch: int, uv_frame_stride: int, n: int, h: int, w: int, out_y_ptr: int,
+                       out_y_pitch: int, out_y_frame_stride: int, out_uv_ptr: int, out_uv_pitch: int,
+                       out_uv_frame_stride: int, stream: int = 0):
+        """HBM in/out, everything enqueued on `stream`, nothing waited for."""
+        _check(lib().vss_video_process_device(self._v, chain._st if chain is not None else None,
+                                              bg._bg if bg is not None else None, y_ptr or None, y_pitch,
+                                              y_frame_stride, uv_ptr or None, uv_pitch, uv_frame_stride, n, h, w,
+                                              out_y_ptr or None, out_y_pitch, out_y_frame_stride, out_uv_ptr or None,
+                                              out_uv_pitch, out_uv_frame_stride, stream or None), self.session._h)
 
 
 def blur_weights(radius: int, sigma: float) -> np.ndarray:

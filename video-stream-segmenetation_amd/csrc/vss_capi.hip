@@ -353,7 +353,7 @@ struct vss_handle {
   std::vector<int> trace_wgs;              // workgroups of the layer's last launch
 #endif
   uint8_t* d_comp = nullptr;      // vss_segment_composite / _background output, allocated on first use
-  std::atomic<size_t> bg_bytes{0};  // device buffers of the handle's vss_background objects
+  std::atomic<size_t> bg_bytes{0};  // device buffers of the handle's vss_background and vss_video objects
   float* d_post_alpha = nullptr;  // vss_segment_post outputs [max_batch][P]
   uint8_t* d_post_u8 = nullptr;
   int use_graph = 1;
@@ -2033,6 +2033,10 @@ void destroy_engine(vss_handle* h) {
 
 }  // namespace
 
+static inline int segment_device_on(vss_handle* h, int* slot, const uint8_t* d_frames, int n, int height, int width,
+                                    int channels, size_t row_stride, size_t frame_stride, float* d_masks, void* stream)
+    __attribute__((always_inline));
+
 extern "C" {
 
 int vss_version(void) { return VSS_VERSION; }
@@ -2296,8 +2300,15 @@ int vss_host_free(void* ptr) {
   return hipHostFree(ptr) == hipSuccess ? VSS_OK : VSS_E_HIP;
 }
 
-int vss_segment_device(vss_handle* h, const uint8_t* d_frames, int n, int height, int width, int channels,
-                       size_t row_stride, size_t frame_stride, float* d_masks, void* stream) {
+// vss_segment_device; slot != null: *slot < 0 takes the next slot of the
+// round-robin and returns it, *slot >= 0 runs on that slot (a caller that keeps
+// one buffer pair, vss_video, stays on one slot's executable graph).
+// always_inline: vss_segment_device keeps a body of its own; as a call into a
+// shared function the bench line read 1.7 % lower in three alternating A/B
+// pairs against the parent.
+static inline int segment_device_on(vss_handle* h, int* slot, const uint8_t* d_frames, int n, int height, int width,
+                                    int channels, size_t row_stride, size_t frame_stride, float* d_masks,
+                                    void* stream) {
   if (!h) return fail(nullptr, VSS_E_INVALID_ARG, "null handle");
   if (!d_frames || !d_masks) return fail(h, VSS_E_INVALID_ARG, "null device pointer");
   g_device_clock.begin();
@@ -2310,7 +2321,8 @@ int vss_segment_device(vss_handle* h, const uint8_t* d_frames, int n, int height
   // round-robin slots, ordered on the device (no host wait): consecutive
   // calls on different streams run concurrently.  Device calls take no
   // ticket: a host batch in the same slot keeps its ticket and completion.
-  const int k = (int)(h->device_calls++ % h->slots.size());
+  const int k = slot && *slot >= 0 ? *slot : (int)(h->device_calls++ % h->slots.size());
+  if (slot) *slot = k;
   Slot& sl = h->slots[k];
   if ((rc = claim_slot(h, sl, s))) return rc;
   g_device_clock.mark(2);
@@ -2318,6 +2330,11 @@ int vss_segment_device(vss_handle* h, const uint8_t* d_frames, int n, int height
   const int rr = release_slot(h, sl, s);  // also after a failed enqueue: the next user orders after it
   g_device_clock.mark(7);
   return rc ? rc : rr;
+}
+
+int vss_segment_device(vss_handle* h, const uint8_t* d_frames, int n, int height, int width, int channels,
+                       size_t row_stride, size_t frame_stride, float* d_masks, void* stream) {
+  return segment_device_on(h, nullptr, d_frames, n, height, width, channels, row_stride, frame_stride, d_masks, stream);
 }
 
 int vss_comm_status(vss_handle* h, int* async_errors, int cap, int* nslots, unsigned long long* gather_calls) {
@@ -3202,10 +3219,10 @@ int blur_weights(int radius, double sigma, uint16_t* w, std::string* why) {
   return VSS_OK;
 }
 
-// the device buffers of a background count into vss_info.device_bytes
+// (re)allocate one device buffer of a background or video object to `bytes`
+// (0: free it); these buffers count into vss_info.device_bytes
 template <class T>
-int bg_alloc(vss_background* bg, T** p, size_t* have, size_t bytes) {
-  vss_handle* h = bg->h;
+int counted_alloc(vss_handle* h, T** p, size_t* have, size_t bytes) {
   if (*p) {
     (void)hipFree(*p);
     h->bg_bytes -= *have;
@@ -3219,6 +3236,11 @@ int bg_alloc(vss_background* bg, T** p, size_t* have, size_t bytes) {
   *have = bytes;
   h->bg_bytes += bytes;
   return VSS_OK;
+}
+
+template <class T>
+int bg_alloc(vss_background* bg, T** p, size_t* have, size_t bytes) {
+  return counted_alloc(bg->h, p, have, bytes);
 }
 
 // before a device buffer of bg is freed or overwritten: its latest composite has ended
@@ -3543,6 +3565,266 @@ int vss_segment_background(vss_handle* h, vss_post_state* st, vss_background* bg
     if (e != hipSuccess) rc = fail(h, VSS_E_HIP, std::string("D2H: ") + hipGetErrorString(e));
   }
   return finish_seam(h, lk, k, rc);
+}
+
+}  // extern "C"
+
+// ---- NV12 video I/O (vss_video.hip; the definition: include/vss_video.h) -----
+struct vss_video {
+  vss_handle* h = nullptr;
+  std::mutex mu;                 // setters and calls of one object are serialised
+  int std_ = VSS_CSC_BT709_LIMITED;
+  uint8_t* d_buf = nullptr;      // RGBA in | RGBA out (px_cap pixels each) | masks f32 | alpha u8 (max_batch frames)
+  size_t buf_bytes = 0, px_cap = 0;
+  uint8_t* d_nv = nullptr;       // the host call's device planes: Y in | UV in | Y out | UV out
+  size_t nv_bytes = 0;
+  int slot = -1;                 // the handle slot whose executable graph is bound to d_buf (taken by the first call)
+  hipEvent_t last = nullptr;     // recorded after every call
+  hipStream_t last_stream = nullptr;
+  bool used = false;
+};
+
+namespace {
+
+constexpr CscCoef kCsc[4] = {
+    {16, 298, 409, -100, -208, 516, 66, 129, 25, -38, -74, 112, 112, -94, -18},    // BT.601 limited
+    {16, 298, 459, -55, -136, 541, 47, 157, 16, -26, -86, 112, 112, -102, -10},    // BT.709 limited
+    {0, 256, 359, -88, -183, 454, 77, 150, 29, -43, -85, 128, 128, -107, -21},     // BT.601 full
+    {0, 256, 403, -48, -120, 475, 54, 183, 19, -29, -99, 128, 128, -116, -12},     // BT.709 full
+};
+
+int check_std(vss_handle* h, int std) {
+  if (std < 0 || std > 3) return fail(h, VSS_E_INVALID_ARG, "std must be one of VSS_CSC_* (0..3)");
+  return VSS_OK;
+}
+
+// one NV12 batch's geometry; `what` names the planes in the message
+int check_nv12(vss_handle* h, const char* what, const uint8_t* y, size_t yp, size_t yfs, const uint8_t* uv, size_t up,
+               size_t ufs, int n, int fh, int fw, int max_n) {
+  const std::string w(what);
+  if (!y || !uv) return fail(h, VSS_E_INVALID_ARG, w + ": null plane pointer");
+  if (n < 1 || n > max_n) return fail(h, VSS_E_INVALID_ARG, "n must be in [1, max_batch]");
+  if (fh < 2 || fw < 2 || (fh & 1) || (fw & 1))
+    return fail(h, VSS_E_INVALID_ARG, "NV12 needs an even height and width, both >= 2");
+  if (yp < (size_t)fw || up < (size_t)fw) return fail(h, VSS_E_INVALID_ARG, w + ": pitch < width");
+  if (yfs < yp * (size_t)fh) return fail(h, VSS_E_INVALID_ARG, w + ": y_frame_stride < y_pitch * height");
+  if (ufs < up * (size_t)(fh / 2)) return fail(h, VSS_E_INVALID_ARG, w + ": uv_frame_stride < uv_pitch * height/2");
+  return VSS_OK;
+}
+
+int check_rgba(vss_handle* h, const uint8_t* p, size_t rs, size_t fs, int fh, int fw) {
+  if (!p) return fail(h, VSS_E_INVALID_ARG, "null RGBA pointer");
+  if (rs < (size_t)fw * 4 || rs % 4 || fs < rs * (size_t)fh || fs % 4 || (reinterpret_cast<uintptr_t>(p) & 3))
+    return fail(h, VSS_E_INVALID_ARG,
+                "bad RGBA geometry (row stride >= 4*width; strides and base pointer multiples of 4)");
+  return VSS_OK;
+}
+
+Nv12Params nv12_params(int std, const uint8_t* y, size_t yp, size_t yfs, const uint8_t* uv, size_t up, size_t ufs,
+                       const uint8_t* rgba, size_t rs, size_t fs, int fh, int fw) {
+  Nv12Params p{};
+  p.y = const_cast<uint8_t*>(y);
+  p.uv = const_cast<uint8_t*>(uv);
+  p.y_pitch = (long)yp; p.y_frame_stride = (long)yfs;
+  p.uv_pitch = (long)up; p.uv_frame_stride = (long)ufs;
+  p.rgba = const_cast<uint8_t*>(rgba);
+  p.row_stride = (long)rs; p.frame_stride = (long)fs;
+  p.fh = fh; p.fw = fw;
+  p.k = kCsc[std];
+  return p;
+}
+
+int launched(vss_handle* h, const char* what) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, VSS_E_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+  return VSS_OK;
+}
+
+int video_alloc(vss_video* v, uint8_t** p, size_t* have, size_t bytes) {
+  return counted_alloc(v->h, p, have, bytes);
+}
+
+// before a device buffer of v is freed: its latest call has ended
+int video_quiesce(vss_video* v) {
+  HIP_TRY(v->h, hipSetDevice(v->h->device));
+  if (v->used) HIP_TRY(v->h, hipEventSynchronize(v->last));
+  return VSS_OK;
+}
+
+// v->mu held; arguments checked.  The whole chain on s.
+int video_enqueue(vss_video* v, vss_post_state* st, vss_background* bg, const uint8_t* d_y, size_t yp, size_t yfs,
+                  const uint8_t* d_uv, size_t up, size_t ufs, int n, int fh, int fw, uint8_t* d_oy, size_t oyp,
+                  size_t oyfs, uint8_t* d_ouv, size_t oup, size_t oufs, hipStream_t s) {
+  vss_handle* h = v->h;
+  const size_t px = (size_t)n * fh * fw, P = (size_t)h->cfg.model_h * h->cfg.model_w;
+  const size_t nb = (size_t)std::max(h->cfg.max_batch, h->user_max_batch);
+  int rc;
+  if (px > v->px_cap) {
+    if ((rc = video_quiesce(v))) return rc;
+    v->px_cap = 0;
+    if ((rc = video_alloc(v, &v->d_buf, &v->buf_bytes, px * 8 + nb * P * 5))) return rc;
+    v->px_cap = px;
+  }
+  if (v->used && v->last_stream != s) HIP_TRY(h, hipStreamWaitEvent(s, v->last, 0));
+  uint8_t* d_in = v->d_buf;
+  uint8_t* d_out = v->d_buf + v->px_cap * 4;
+  float* d_masks = reinterpret_cast<float*>(v->d_buf + v->px_cap * 8);
+  uint8_t* d_alpha = v->d_buf + v->px_cap * 8 + nb * P * 4;
+  const size_t rs = (size_t)fw * 4, fs = rs * fh;
+  launch_nv12_unpack(nv12_params(v->std_, d_y, yp, yfs, d_uv, up, ufs, d_in, rs, fs, fh, fw), n, s);
+  rc = launched(h, "nv12 unpack");
+  if (!rc) rc = segment_device_on(h, &v->slot, d_in, n, fh, fw, 4, rs, fs, d_masks, s);
+  if (!rc) rc = vss_postprocess_device(st, d_in, n, fh, fw, 4, rs, fs, d_masks, nullptr, d_alpha, s);
+  if (!rc) {
+    std::lock_guard<std::mutex> bl(bg->mu);
+    rc = bg_enqueue(h, bg, d_in, n, fh, fw, 4, rs, fs, d_alpha, d_out, rs, fs, s);
+  }
+  if (!rc) {
+    launch_nv12_pack(nv12_params(v->std_, d_oy, oyp, oyfs, d_ouv, oup, oufs, d_out, rs, fs, fh, fw), n, s);
+    rc = launched(h, "nv12 pack");
+  }
+  // also after a failed enqueue: what did go out reads or writes the scratch
+  HIP_TRY(h, hipEventRecord(v->last, s));
+  v->last_stream = s;
+  v->used = true;
+  return rc;
+}
+
+int check_video_call(vss_video* v, vss_post_state* st, vss_background* bg) {
+  if (!v) return fail(nullptr, VSS_E_INVALID_ARG, "null video");
+  if (!st || st->h != v->h) return fail(v->h, VSS_E_INVALID_ARG, "video / post state mismatch");
+  if (!bg || bg->h != v->h) return fail(v->h, VSS_E_INVALID_ARG, "video / background mismatch");
+  return VSS_OK;
+}
+
+}  // namespace
+
+static_assert(VSS_CSC_BT601_LIMITED == 0 && VSS_CSC_BT709_LIMITED == 1 && VSS_CSC_BT601_FULL == 2 &&
+                  VSS_CSC_BT709_FULL == 3,
+              "kCsc is indexed by VSS_CSC_*");
+
+extern "C" {
+
+int vss_nv12_to_rgba_device(vss_handle* h, int std, const uint8_t* d_y, size_t y_pitch, size_t y_frame_stride,
+                            const uint8_t* d_uv, size_t uv_pitch, size_t uv_frame_stride, int n, int height, int width,
+                            uint8_t* d_rgba, size_t row_stride, size_t frame_stride, void* stream) {
+  if (!h) return fail(nullptr, VSS_E_INVALID_ARG, "null handle");
+  int rc = check_std(h, std);
+  if (!rc)
+    rc = check_nv12(h, "input", d_y, y_pitch, y_frame_stride, d_uv, uv_pitch, uv_frame_stride, n, height, width,
+                    std::max(h->cfg.max_batch, h->user_max_batch));
+  if (!rc) rc = check_rgba(h, d_rgba, row_stride, frame_stride, height, width);
+  if (rc) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  launch_nv12_unpack(nv12_params(std, d_y, y_pitch, y_frame_stride, d_uv, uv_pitch, uv_frame_stride, d_rgba, row_stride,
+                                 frame_stride, height, width), n, s);
+  return launched(h, "nv12 unpack");
+}
+
+int vss_rgba_to_nv12_device(vss_handle* h, int std, const uint8_t* d_rgba, size_t row_stride, size_t frame_stride,
+                            int n, int height, int width, uint8_t* d_y, size_t y_pitch, size_t y_frame_stride,
+                            uint8_t* d_uv, size_t uv_pitch, size_t uv_frame_stride, void* stream) {
+  if (!h) return fail(nullptr, VSS_E_INVALID_ARG, "null handle");
+  int rc = check_std(h, std);
+  if (!rc)
+    rc = check_nv12(h, "output", d_y, y_pitch, y_frame_stride, d_uv, uv_pitch, uv_frame_stride, n, height, width,
+                    std::max(h->cfg.max_batch, h->user_max_batch));
+  if (!rc) rc = check_rgba(h, d_rgba, row_stride, frame_stride, height, width);
+  if (rc) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  launch_nv12_pack(nv12_params(std, d_y, y_pitch, y_frame_stride, d_uv, uv_pitch, uv_frame_stride, d_rgba, row_stride,
+                               frame_stride, height, width), n, s);
+  return launched(h, "nv12 pack");
+}
+
+int vss_video_create(vss_handle* h, int std, vss_video** out) {
+  if (!h || !out) return fail(h, VSS_E_INVALID_ARG, "null handle/out");
+  *out = nullptr;
+  if (int rc = check_std(h, std)) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  vss_video* v = new vss_video();
+  v->h = h;
+  v->std_ = std;
+  const hipError_t e = hipEventCreateWithFlags(&v->last, hipEventDisableTiming);
+  if (e != hipSuccess) {
+    delete v;
+    return fail(h, VSS_E_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
+  }
+  *out = v;
+  return VSS_OK;
+}
+
+void vss_video_destroy(vss_video* v) {
+  if (!v) return;
+  (void)video_quiesce(v);
+  (void)video_alloc(v, &v->d_buf, &v->buf_bytes, 0);
+  (void)video_alloc(v, &v->d_nv, &v->nv_bytes, 0);
+  if (v->last) (void)hipEventDestroy(v->last);
+  delete v;
+}
+
+int vss_video_set_standard(vss_video* v, int std) {
+  if (!v) return fail(nullptr, VSS_E_INVALID_ARG, "null video");
+  if (int rc = check_std(v->h, std)) return rc;
+  std::lock_guard<std::mutex> lk(v->mu);
+  v->std_ = std;
+  return VSS_OK;
+}
+
+int vss_video_process_device(vss_video* v, vss_post_state* st, vss_background* bg, const uint8_t* d_y, size_t y_pitch,
+                             size_t y_frame_stride, const uint8_t* d_uv, size_t uv_pitch, size_t uv_frame_stride, int n,
+                             int height, int width, uint8_t* d_out_y, size_t oy_pitch, size_t oy_frame_stride,
+                             uint8_t* d_out_uv, size_t ouv_pitch, size_t ouv_frame_stride, void* stream) {
+  int rc = check_video_call(v, st, bg);
+  if (rc) return rc;
+  vss_handle* h = v->h;
+  rc = check_nv12(h, "input", d_y, y_pitch, y_frame_stride, d_uv, uv_pitch, uv_frame_stride, n, height, width,
+                  h->cfg.max_batch);
+  if (!rc)
+    rc = check_nv12(h, "output", d_out_y, oy_pitch, oy_frame_stride, d_out_uv, ouv_pitch, ouv_frame_stride, n, height,
+                    width, h->cfg.max_batch);
+  if (rc) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  std::lock_guard<std::mutex> lk(v->mu);
+  return video_enqueue(v, st, bg, d_y, y_pitch, y_frame_stride, d_uv, uv_pitch, uv_frame_stride, n, height, width,
+                       d_out_y, oy_pitch, oy_frame_stride, d_out_uv, ouv_pitch, ouv_frame_stride, s);
+}
+
+int vss_video_process(vss_video* v, vss_post_state* st, vss_background* bg, const uint8_t* y, const uint8_t* uv, int n,
+                      int height, int width, uint8_t* out_y, uint8_t* out_uv) {
+  int rc = check_video_call(v, st, bg);
+  if (rc) return rc;
+  vss_handle* h = v->h;
+  const size_t w = width > 0 ? (size_t)width : 0, hh = height > 0 ? (size_t)height : 0;
+  rc = check_nv12(h, "input", y, w, w * hh, uv, w, w * (hh / 2), n, height, width, h->cfg.max_batch);
+  if (!rc) rc = check_nv12(h, "output", out_y, w, w * hh, out_uv, w, w * (hh / 2), n, height, width, h->cfg.max_batch);
+  if (rc) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  std::lock_guard<std::mutex> lk(v->mu);
+  const size_t yb = (size_t)n * w * hh, ub = yb / 2;  // bytes of the Y planes and of the UV planes
+  if (2 * (yb + ub) > v->nv_bytes) {
+    if ((rc = video_quiesce(v))) return rc;
+    if ((rc = video_alloc(v, &v->d_nv, &v->nv_bytes, 2 * (yb + ub)))) return rc;
+  }
+  uint8_t* d_y = v->d_nv;
+  uint8_t* d_uv = d_y + yb;
+  uint8_t* d_oy = d_uv + ub;
+  uint8_t* d_ouv = d_oy + yb;
+  hipStream_t s = h->stream;
+  if (v->used && v->last_stream != s) HIP_TRY(h, hipStreamWaitEvent(s, v->last, 0));  // the planes' previous reader
+  HIP_TRY(h, hipMemcpyAsync(d_y, y, yb, hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(d_uv, uv, ub, hipMemcpyHostToDevice, s));
+  rc = video_enqueue(v, st, bg, d_y, w, w * hh, d_uv, w, w * (hh / 2), n, height, width, d_oy, w, w * hh, d_ouv, w,
+                     w * (hh / 2), s);
+  if (!rc) {
+    HIP_TRY(h, hipMemcpyAsync(out_y, d_oy, yb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(h, hipMemcpyAsync(out_uv, d_ouv, ub, hipMemcpyDeviceToHost, s));
+  }
+  HIP_TRY(h, hipStreamSynchronize(s));
+  return rc;
 }
 
 }  // extern "C"

@@ -652,6 +652,25 @@ struct MatteAlphaParams {
 };
 void launch_matte_alpha(const MatteAlphaParams& p, int n, hipStream_t s);
 
+// NV12 video I/O (vss_video.hip; the definition: include/vss_video.h).  One
+// row of the table there: the four standards are values of this struct, a
+// kernel argument, not template instances.
+struct CscCoef {
+  int y0, cy, rv, gu, gv, bu;   // unpack
+  int yr, yg, yb, ur, ug, ub, vr, vg, vb;   // pack
+};
+struct Nv12Params {      // both directions: unpack reads y / uv and writes rgba, pack the reverse
+  uint8_t* y;            // [n] Y planes [fh][y_pitch]
+  uint8_t* uv;           // [n] UV planes [fh/2][uv_pitch]
+  long y_pitch, y_frame_stride, uv_pitch, uv_frame_stride;
+  uint8_t* rgba;         // [n] RGBA frames, 4-byte aligned rows
+  long row_stride, frame_stride;
+  int fh, fw;            // even, >= 2
+  CscCoef k;
+};
+void launch_nv12_unpack(const Nv12Params& p, int n, hipStream_t s);
+void launch_nv12_pack(const Nv12Params& p, int n, hipStream_t s);
+
 // Queued host path: only the frame rows the resize reads, pinned host -> HBM
 // (vss_stage.hip).  rows: device list of the row indices; src / dst = frame 0.
 struct FetchRowsParams {

@@ -42,6 +42,8 @@
 //   backgroundSetBlur(background, radius, sigma), backgroundDestroy(background)
 //   backgroundSetRefine(background, radius, eps)   the edge-aware alpha; radius 0 = off
 //   segmentBackground(handle, post, frames, n, height, width, channels, rowStride, background)
+//   videoCreate(handle, std) / videoSetStandard(video, std) / videoDestroy(video)   NV12 I/O (vss_video.h)
+//   videoProcess(handle, video, post, background, y, uv, n, height, width) -> Promise<{y, uv}>
 //       -> Promise<Uint8Array>   opaque RGBA frames, the person over the background
 //   ortCreate(modelBytes: Uint8Array, inputDims: number[] | null, deviceId, convPrecision) -> session
 //       ONNX sessions (include/vso.h) behind InferenceSession.create (model.ts:14, :38, :61)
@@ -98,6 +100,7 @@ std::atomic<bool> g_env_closing{false};
 
 struct Post;
 struct Bg;
+struct Vid;
 struct Submitter;
 
 struct Handle {
@@ -105,6 +108,7 @@ struct Handle {
   int mask_h = 0, mask_w = 0;
   std::vector<Post*> posts;  // destroyed before the handle, whatever order the GC finalizes in
   std::vector<Bg*> bgs;      // the same for the backgrounds
+  std::vector<Vid*> vids;    // ... and the NV12 video objects
   // Queued batches whose libuv work still holds h (JS thread only): destroy()
   // or the GC finalizer while some are pending defers vss_destroy to the last
   // one's completion, so no worker ever waits on a destroyed handle.
@@ -126,6 +130,11 @@ struct Bg {
   vss_background* bg = nullptr;
 };
 
+struct Vid {
+  Handle* hd = nullptr;
+  vss_video* v = nullptr;
+};
+
 void release_handle(Handle* hd) {
   hd->closing = true;
   if (hd->pending > 0) return;  // work_done() of the last queued batch finishes the release
@@ -141,6 +150,12 @@ void release_handle(Handle* hd) {
     b->hd = nullptr;
   }
   hd->bgs.clear();
+  for (Vid* v : hd->vids) {
+    if (v->v) vss_video_destroy(v->v);
+    v->v = nullptr;
+    v->hd = nullptr;
+  }
+  hd->vids.clear();
   stop_submitter(hd);
   if (hd->h) vss_destroy(hd->h);
   hd->h = nullptr;
@@ -185,6 +200,19 @@ void finalize_bg(napi_env, void* data, void*) {
   Bg* b = static_cast<Bg*>(data);
   release_bg(b);
   delete b;
+}
+
+void release_vid(Vid* v) {
+  if (v->v) vss_video_destroy(v->v);
+  v->v = nullptr;
+  if (v->hd) v->hd->vids.erase(std::remove(v->hd->vids.begin(), v->hd->vids.end(), v), v->hd->vids.end());
+  v->hd = nullptr;
+}
+
+void finalize_vid(napi_env, void* data, void*) {
+  Vid* v = static_cast<Vid*>(data);
+  release_vid(v);
+  delete v;
 }
 
 Handle* get_handle(napi_env env, napi_value v) {
@@ -1399,6 +1427,201 @@ napi_value SegmentPost(napi_env env, napi_callback_info info) { return SegmentIm
 napi_value SegmentComposite(napi_env env, napi_callback_info info) { return SegmentImpl(env, info, true, true); }
 napi_value SegmentBackground(napi_env env, napi_callback_info info) { return SegmentImpl(env, info, true, true, true); }
 
+// ---- NV12 video I/O (include/vss_video.h) ---------------------------------------
+Vid* get_vid(napi_env env, napi_value v) {
+  void* p = nullptr;
+  if (napi_get_value_external(env, v, &p) != napi_ok || !p) {
+    napi_throw_type_error(env, nullptr, "expected a vss video");
+    return nullptr;
+  }
+  Vid* vd = static_cast<Vid*>(p);
+  if (!vd->v) {
+    napi_throw_error(env, nullptr, "vss video already destroyed");
+    return nullptr;
+  }
+  return vd;
+}
+
+napi_value VideoCreate(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Handle* hd = argc >= 2 ? get_handle(env, argv[0]) : nullptr;
+  if (!hd) return nullptr;
+  int std_ = -1;
+  napi_get_value_int32(env, argv[1], &std_);
+  vss_video* v = nullptr;
+  const int rc = vss_video_create(hd->h, std_, &v);
+  if (rc != VSS_OK) {
+    throw_vss(env, "vss_video_create", rc, vss_last_error(hd->h));
+    return nullptr;
+  }
+  Vid* vd = new Vid();
+  vd->hd = hd;
+  vd->v = v;
+  hd->vids.push_back(vd);
+  napi_value ext;
+  NAPI_OK(env, napi_create_external(env, vd, finalize_vid, nullptr, &ext));
+  return ext;
+}
+
+napi_value VideoSetStandard(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Vid* vd = argc >= 2 ? get_vid(env, argv[0]) : nullptr;
+  if (!vd) return nullptr;
+  int std_ = -1;
+  napi_get_value_int32(env, argv[1], &std_);
+  const int rc = vss_video_set_standard(vd->v, std_);
+  if (rc != VSS_OK) throw_vss(env, "vss_video_set_standard", rc, vss_last_error(vd->hd->h));
+  return nullptr;
+}
+
+napi_value VideoDestroy(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  void* p = nullptr;
+  if (argc >= 1 && napi_get_value_external(env, argv[0], &p) == napi_ok && p) release_vid(static_cast<Vid*>(p));
+  return nullptr;
+}
+
+struct VideoWork {
+  napi_async_work work = nullptr;
+  napi_deferred deferred = nullptr;
+  napi_ref y_ref = nullptr, uv_ref = nullptr, oy_ref = nullptr, ouv_ref = nullptr;
+  Handle* hd = nullptr;  // pending counted until VideoComplete
+  vss_video* v = nullptr;
+  vss_post_state* post = nullptr;
+  vss_background* bg = nullptr;
+  const uint8_t* y = nullptr;
+  const uint8_t* uv = nullptr;
+  uint8_t* oy = nullptr;
+  uint8_t* ouv = nullptr;
+  int n = 0, height = 0, width = 0;
+  int rc = 0;
+  std::string err;
+};
+
+void VideoExecute(napi_env, void* data) {  // libuv worker thread: no JS calls here
+  VideoWork* w = static_cast<VideoWork*>(data);
+  w->rc = vss_video_process(w->v, w->post, w->bg, w->y, w->uv, w->n, w->height, w->width, w->oy, w->ouv);
+  if (w->rc != VSS_OK) w->err = vss_last_error(w->hd->h);
+}
+
+void VideoComplete(napi_env env, napi_status, void* data) {
+  VideoWork* w = static_cast<VideoWork*>(data);
+  if (w->rc == VSS_OK) {
+    const size_t yb = (size_t)w->n * w->height * w->width;
+    napi_value aby = nullptr, abuv = nullptr, ay, auv, o;
+    napi_get_reference_value(env, w->oy_ref, &aby);
+    napi_get_reference_value(env, w->ouv_ref, &abuv);
+    napi_create_typedarray(env, napi_uint8_array, yb, aby, 0, &ay);
+    napi_create_typedarray(env, napi_uint8_array, yb / 2, abuv, 0, &auv);
+    napi_create_object(env, &o);
+    napi_set_named_property(env, o, "y", ay);
+    napi_set_named_property(env, o, "uv", auv);
+    napi_resolve_deferred(env, w->deferred, o);
+  } else {
+    napi_value msg, code, e;
+    const std::string m = "vss_video_process failed (" + std::to_string(w->rc) + "): " + w->err;
+    napi_create_string_utf8(env, m.c_str(), m.size(), &msg);
+    napi_create_string_utf8(env, std::to_string(w->rc).c_str(), NAPI_AUTO_LENGTH, &code);
+    napi_create_error(env, code, msg, &e);
+    napi_reject_deferred(env, w->deferred, e);
+  }
+  napi_delete_reference(env, w->y_ref);
+  napi_delete_reference(env, w->uv_ref);
+  napi_delete_reference(env, w->oy_ref);
+  napi_delete_reference(env, w->ouv_ref);
+  napi_delete_async_work(env, w->work);
+  Handle* hd = w->hd;
+  delete w;
+  work_done(hd);
+}
+
+// videoProcess(handle, video, post, background, y, uv, n, height, width): tightly
+// packed NV12, y [n][height][width] and uv [n][height/2][width] bytes.
+napi_value VideoProcess(napi_env env, napi_callback_info info) {
+  size_t argc = 9;
+  napi_value a[9];
+  NAPI_OK(env, napi_get_cb_info(env, info, &argc, a, nullptr, nullptr));
+  if (argc < 9) {
+    napi_throw_type_error(env, nullptr, "videoProcess(handle, video, post, background, y, uv, n, height, width)");
+    return nullptr;
+  }
+  Handle* hd = get_handle(env, a[0]);
+  if (!hd) return nullptr;
+  Vid* vd = get_vid(env, a[1]);
+  if (!vd) return nullptr;
+  Post* ps = get_post(env, a[2]);
+  if (!ps) return nullptr;
+  Bg* bgp = get_bg(env, a[3]);
+  if (!bgp) return nullptr;
+  if (vd->hd != hd || ps->hd != hd || bgp->hd != hd) {
+    napi_throw_error(env, nullptr, "video, post state or background belongs to another handle");
+    return nullptr;
+  }
+  const uint8_t* planes[2] = {nullptr, nullptr};
+  size_t lens[2] = {0, 0};
+  for (int k = 0; k < 2; ++k) {
+    bool is_ta = false;
+    napi_is_typedarray(env, a[4 + k], &is_ta);
+    napi_typedarray_type tt = napi_int8_array;
+    size_t off = 0;
+    void* data = nullptr;
+    napi_value buf;
+    if (is_ta) NAPI_OK(env, napi_get_typedarray_info(env, a[4 + k], &tt, &lens[k], &data, &buf, &off));
+    if (!is_ta || (tt != napi_uint8_array && tt != napi_uint8_clamped_array)) {
+      napi_throw_type_error(env, nullptr, "y and uv must be Uint8Array or Uint8ClampedArray");
+      return nullptr;
+    }
+    planes[k] = static_cast<const uint8_t*>(data);
+  }
+  int n = 0, height = 0, width = 0;
+  napi_get_value_int32(env, a[6], &n);
+  napi_get_value_int32(env, a[7], &height);
+  napi_get_value_int32(env, a[8], &width);
+  if (n < 1 || height < 2 || width < 2) {
+    napi_throw_range_error(env, nullptr, "n >= 1 and an NV12 frame of at least 2 x 2 expected");
+    return nullptr;
+  }
+  const size_t yb = (size_t)n * height * width, ub = (size_t)n * (height / 2) * width;
+  if (lens[0] < yb || lens[1] < ub) {
+    napi_throw_range_error(env, nullptr, "y smaller than n * height * width, or uv than n * height/2 * width");
+    return nullptr;
+  }
+  VideoWork* w = new VideoWork();
+  w->v = vd->v;
+  w->post = ps->st;
+  w->bg = bgp->bg;
+  w->y = planes[0];
+  w->uv = planes[1];
+  w->n = n;
+  w->height = height;
+  w->width = width;
+  napi_value aby, abuv;
+  void* oy = nullptr;
+  void* ouv = nullptr;
+  NAPI_OK(env, napi_create_arraybuffer(env, yb, &oy, &aby));
+  NAPI_OK(env, napi_create_arraybuffer(env, yb / 2, &ouv, &abuv));
+  w->oy = static_cast<uint8_t*>(oy);
+  w->ouv = static_cast<uint8_t*>(ouv);
+  napi_create_reference(env, a[4], 1, &w->y_ref);  // keep the planes alive until done
+  napi_create_reference(env, a[5], 1, &w->uv_ref);
+  napi_create_reference(env, aby, 1, &w->oy_ref);
+  napi_create_reference(env, abuv, 1, &w->ouv_ref);
+  napi_value promise, name;
+  NAPI_OK(env, napi_create_promise(env, &w->deferred, &promise));
+  napi_create_string_utf8(env, "vss_video_process", NAPI_AUTO_LENGTH, &name);
+  NAPI_OK(env, napi_create_async_work(env, nullptr, name, VideoExecute, VideoComplete, w, &w->work));
+  NAPI_OK(env, napi_queue_async_work(env, w->work));
+  w->hd = hd;
+  ++hd->pending;
+  return promise;
+}
+
 // ---- ONNX sessions (include/vso.h) -------------------------------------------
 struct OrtSess {
   vso_session* s = nullptr;
@@ -1924,6 +2147,10 @@ napi_value Init(napi_env env, napi_value exports) {
       {"backgroundSetRefine", nullptr, BackgroundSetRefine, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"backgroundDestroy", nullptr, BackgroundDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"segmentBackground", nullptr, SegmentBackground, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"videoCreate", nullptr, VideoCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"videoSetStandard", nullptr, VideoSetStandard, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"videoDestroy", nullptr, VideoDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"videoProcess", nullptr, VideoProcess, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ortCreate", nullptr, OrtCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ortInfo", nullptr, OrtInfo, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ortRun", nullptr, OrtRun, nullptr, nullptr, nullptr, napi_default, nullptr},
