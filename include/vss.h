@@ -390,6 +390,20 @@ int vss_profile_read(vss_handle* h, double* ms_per_layer, int cap, int* count);
  * csrc/vss_kernels.h); no GPU needed.  tools/gen_registry.py mirrors it. */
 int vss_block_lds_bytes(int mode, int stride, int th, int tw, int cin, int cskip, int chid, int cout, int stem_in);
 
+/* The expand layers' fragment-ordered weight image (expand_frag in
+ * csrc/vss_kernels.h), built once at vss_create; no GPU needed.  An expand
+ * block's waves each own whole 16-channel hidden chunks and load a chunk's
+ * weights from its record in global memory straight into registers.
+ * vss_expand_frag_layout: out4 = {bytes per record, offsets of the W1
+ * fragments, the float4s (expand bias, 9 dw taps, dw bias) and the W2
+ * fragments}.  vss_expand_frag_image: the cs / 16 records of hidden channels
+ * [h0, h0 + cs) from the layer's row-major f32 arrays w1 [chid][cin], b1
+ * [chid], wdw [chid][9], bdw [chid], w2 [cout][chid] (pointwise weights
+ * bf16-exact); channel counts are multiples of 16. */
+void vss_expand_frag_layout(int cin, int cout, int* out4);
+int vss_expand_frag_image(int cin, int chid, int cout, int h0, int cs, const float* w1, const float* b1,
+                          const float* wdw, const float* bdw, const float* w2, void* out);
+
 /* ---- §8(f) row 1: the reference's mask post-processing, on the GPU ----------
  * processFrame's steps after the seam (frameProcessorTest.ts:115-169):
  * temporalEMA (:218) -> morphologicalOpening (:644) -> jointBilateral3x3 with the

@@ -86,8 +86,10 @@ def block_lds_bytes(mode, stride, th, tw, cin, cskip, chid, cout, stem_in=False)
     hid = 16 * 4 * (p_in_pad + (1 if stride == 2 else 0)) if (SWZ and xr1) else 4 * p_in_pad * HID_STRIDE
     f = xt_floats
     f += r4(p_out * cin) if (mode == 0 and stride == 1 and cin == cout) else 0
-    f += r4(chid * (cin + 8) // 2) if mode == 0 else 0
-    f += r4(cout * (chid + 8) // 2) + r4(9 * chid) + r4(chid) + (r4(chid) if mode == 0 else 0) + r4(cout)
+    # the LDS weight image: W2 rows, dw taps and biases; an expand layer keeps only
+    # the project bias there (its waves read their chunks' weights from global memory)
+    f += r4(cout * (chid + 8) // 2) + r4(9 * chid) + r4(chid) if mode != 0 else 0
+    f += r4(cout)
     f += r4(2 * cin) if mode == 2 else 0
     f += 4 * p_in_pad if mode == 2 and (th % 2 or tw % 2) else 0  # the decoder's upsample tap records (L.uc; odd tiles)
     # work: expand scratch / slabs / (decoder) the low-res src region; the

@@ -80,7 +80,7 @@ class Lds:
         self.P_out = TH * TW
         self.CX = cin + cskip if mode == 2 else cin
         self.XS = self.CX + xs_pad
-        self.LD1, self.LD2 = cin + 8, chid + 8
+        self.LD2 = chid + 8
         self.SR, self.SC = (TH + 1) // 2 + 3, (TW + 1) // 2 + 3
         self.NCB, self.NPB, self.NCHUNK = cout // 16, self.P_out // 16, chid // 16
         self.CS = 4 if self.NCHUNK >= 4 else (2 if self.NCHUNK >= 2 else 1)
@@ -91,11 +91,12 @@ class Lds:
         o = 0
         self.xt = o; o += r4(self.P_in_pad * self.XS)
         self.xr = o; o += r4(self.P_out * cin) if (mode == 0 and stride == 1 and cin == cout) else 0
-        self.w1 = o; o += r4(chid * self.LD1 // 2) if mode == 0 else 0
-        self.w2 = o; o += r4(cout * self.LD2 // 2)
-        self.wdw = o; o += r4(9 * chid)
-        self.bdw = o; o += r4(chid)
-        self.b1 = o; o += r4(chid) if mode == 0 else 0
+        # (an expand layer keeps only the project bias in LDS: its waves take their
+        # chunks' weights from global memory, csrc/vss_kernels.h expand_frag)
+        self.w1 = o
+        self.w2 = o; o += r4(cout * self.LD2 // 2) if mode != 0 else 0
+        self.wdw = o; o += r4(9 * chid) if mode != 0 else 0
+        self.bdw = o; o += r4(chid) if mode != 0 else 0
         self.b2 = o; o += r4(cout)
         self.wimg_end = o
         xt_floats = r4(self.P_in_pad * self.XS)
@@ -148,11 +149,10 @@ class Lds:
         xt_floats = self.P_in_pad * self.CX if self.xqm else r4(self.P_in_pad * self.XS)
         self.xt = o; o += xt_floats
         self.xr = o; o += r4(self.P_out * self.cin) if (mode == 0 and S == 1 and self.cin == self.cout) else 0
-        self.w1 = o; o += r4(self.CH * self.LD1 // 2) if mode == 0 else 0
-        self.w2 = o; o += r4(self.cout * self.LD2 // 2)
-        self.wdw = o; o += r4(9 * self.CH)
-        self.bdw = o; o += r4(self.CH)
-        self.b1 = o; o += r4(self.CH) if mode == 0 else 0
+        self.w1 = o
+        self.w2 = o; o += r4(self.cout * self.LD2 // 2) if mode != 0 else 0
+        self.wdw = o; o += r4(9 * self.CH) if mode != 0 else 0
+        self.bdw = o; o += r4(self.CH) if mode != 0 else 0
         self.b2 = o; o += r4(self.cout)
         self.wimg_end = o
         slab_in_xt = mode == 2 and self.CS * self.slab_stride <= xt_floats
@@ -423,11 +423,7 @@ def sites(L, tile, img, stem_geo=None):
         for ck in chunks:
             c0 = ck * 16
             if L.mode == 0:
-                NK = L.cin // 16
-                for s_ in range(NK):  # aw: lds_a rows (b64)
-                    emit("ir: expand A frags (r64)", "r64", w,
-                         lambda t, s_=s_: L.w1 + ((c0 + t % 16) * L.LD1 + 16 * s_ + 4 * ((t % 64) // 16)) // 2)
-                emit("ir: expand bias (r128)", "r128", w, lambda t: L.b1 + c0 + 4 * ((t % 64) // 16))
+                NK = L.cin // 16  # (the chunk's weights come from global memory: no LDS sites)
                 hid = L.work + w * (4 * L.HPL if L.hqm else L.P_in_pad * L.HSD)
                 for cb in range(L.P_in_pad // 16):
                     for s_ in range(NK):
@@ -438,10 +434,11 @@ def sites(L, tile, img, stem_geo=None):
                 at, npbw, cbase = (lambda pix, ch, hid=hid: L.hid_at(hid, pix, ch)), L.NPB, 0
             else:
                 at, npbw, cbase = L.xt_at, L.NPBW, c0
-            for tt in range(9):
+            for tt in range(9 if L.mode != 0 else 0):
                 emit("dw tap weights (r128)", "r128", w, lambda t, tt=tt: L.wdw + tt * L.CH + c0 + 4 * ((t % 64) // 16))
-            emit("dw bias (r128)", "r128", w, lambda t: L.bdw + c0 + 4 * ((t % 64) // 16))
-            for cb in range(L.NCB):
+            if L.mode != 0:
+                emit("dw bias (r128)", "r128", w, lambda t: L.bdw + c0 + 4 * ((t % 64) // 16))
+            for cb in range(L.NCB if L.mode != 0 else 0):
                 emit("project A frags (r64)", "r64", w,
                      lambda t, cb=cb: L.w2 + ((cb * 16 + t % 16) * L.LD2 + c0 + 4 * ((t % 64) // 16)) // 2)
             nq = (L.NPB if L.mode == 0 else npbw) // XR

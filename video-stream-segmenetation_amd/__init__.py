@@ -150,6 +150,8 @@ def lib() -> ctypes.CDLL:
                 "vss_segment_gather_device": ([P, P, I, I, I, I, S, S, P, P], I),
                 "vss_comm_status": ([P, ctypes.POINTER(I), I, ctypes.POINTER(I), ctypes.POINTER(ctypes.c_uint64)], I),
                 "vss_block_lds_bytes": ([I] * 9, I),
+                "vss_expand_frag_layout": ([I, I, ctypes.POINTER(I)], None),
+                "vss_expand_frag_image": ([I] * 5 + [P] * 6, I),
                 "vss_preprocess_device": ([P, P, I, I, I, I, S, S, P, P], I),
                 "vss_mask_to_frame_device": ([P, P, I, I, I, P, P], I),
                 "vss_synchronize": ([P], I),
@@ -859,3 +861,26 @@ def version() -> int:
 def block_lds_bytes(mode, stride, th, tw, cin, cskip, chid, cout, stem_in=0) -> int:
     """block_lds() of csrc/vss_kernels.h through the library (no GPU needed)."""
     return lib().vss_block_lds_bytes(mode, stride, th, tw, cin, cskip, chid, cout, stem_in)
+
+
+def expand_frag_layout(cin: int, cout: int) -> dict:
+    """expand_frag() of csrc/vss_kernels.h: byte size of one 16-channel chunk's fragment
+    record of an expand layer and the offsets of its sections."""
+    out = (ctypes.c_int * 4)()
+    lib().vss_expand_frag_layout(cin, cout, out)
+    return dict(zip(("bytes", "aw", "f4s", "a2"), out))
+
+
+def expand_frag_image(w1, b1, wdw, bdw, w2, h0: int = 0, cs: int | None = None) -> np.ndarray:
+    """The fragment records (uint8 [cs / 16][bytes]) of hidden channels [h0, h0 + cs) of an
+    expand layer from its row-major float32 arrays w1 [chid][cin], b1 [chid], wdw [chid][9],
+    bdw [chid], w2 [cout][chid], as the library builds them at vss_create (no GPU needed)."""
+    arrs = [np.ascontiguousarray(a, np.float32) for a in (w1, b1, wdw, bdw, w2)]
+    chid, cin = arrs[0].shape
+    cout = arrs[4].shape[0]
+    if arrs[1].shape != (chid,) or arrs[2].shape != (chid, 9) or arrs[3].shape != (chid,) or arrs[4].shape != (cout, chid):
+        raise VssError(VSS_E_INVALID_ARG, "expand_frag_image: array shapes")
+    cs = chid - h0 if cs is None else cs
+    out = np.zeros((max(cs, 0) // 16, expand_frag_layout(cin, cout)["bytes"]), np.uint8)
+    _check(lib().vss_expand_frag_image(cin, chid, cout, h0, cs, *[a.ctypes.data for a in arrs], out.ctypes.data))
+    return out

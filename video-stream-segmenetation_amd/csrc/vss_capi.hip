@@ -77,6 +77,8 @@ struct LayerPlan {
   bool fused = false;          // computed inside its only consumer's prologue (no launch of its own)
   int acc_off = -1;            // DEC: offset of its [kAccSlots][2][C] norm accumulator in a frame's row
   const float* wimg = nullptr;  // LDS weight image (block_lds regions w1..b2)
+  const char* wfrag = nullptr;  // expand layers: the chunks' fragment records (expand_frag), slice after slice
+  long wfrag_stride = 0;        // bytes between the slices' records
   const float *gamma = nullptr, *beta = nullptr;
   const float *stem_w = nullptr, *stem_b = nullptr, *head_w = nullptr;
   float head_b = 0.f;
@@ -321,10 +323,6 @@ class CopyPool {
 }  // namespace
 
 constexpr long kDefaultKsplitPixels = 256;
-// expand layers whose unsplit LDS weight image exceeds this also split their
-// hidden channels (keeps every layer's LDS small enough for two workgroups per
-// CU; mirrors KSPLIT_WEIGHT_BYTES in tools/gen_registry.py)
-constexpr size_t kKsplitWeightBytes = 40 * 1024;
 
 struct vss_handle {
   vss_config cfg{};            // this engine's config (max_batch = its share of the handle's)
@@ -597,12 +595,6 @@ int load_weights(vss_handle* h) {
   return VSS_OK;
 }
 
-// Bytes of an unsplit expand layer's LDS weight image (block_lds regions w1..b2).
-size_t weight_image_bytes(const LayerPlan& l) {
-  const BlockLds B = block_lds(l.mode, l.stride, 1, 16, (int)l.rec.cin, 0, l.chid, l.C);
-  return (size_t)(B.wimg_end - B.w1) * 4;
-}
-
 int plan(vss_handle* h) {
   const int Hm = h->cfg.model_h, Wm = h->cfg.model_w, N = h->cfg.max_batch;
   const int nl = (int)h->recs.size();
@@ -667,9 +659,9 @@ int plan(vss_handle* h) {
     // pixels per frame (a function of the model resolution only, so results
     // never depend on the batch or the autotuner)
     // (only with VSS_KSPLIT=1: see ksplit_on)
-    if (l.mode == MODE_IR_EXPAND && h->ksplit_on &&
-        ((long)l.H * l.W <= h->ksplit_pixels || weight_image_bytes(l) > kKsplitWeightBytes))
-      l.ks = ks_max(l);
+    // (the rule that also split layers whose LDS weight image exceeded 40 KiB is
+    // gone with that image: an expand layer keeps only its project bias in LDS)
+    if (l.mode == MODE_IR_EXPAND && h->ksplit_on && (long)l.H * l.W <= h->ksplit_pixels) l.ks = ks_max(l);
     if (r.kind == K_IR || r.kind == K_DEC) l.xp = h->L[r.src].ks;
     if (r.kind == K_DEC) l.sp = h->L[r.skip].ks;
     if (r.kind == K_IR) l.flags = block_flags(0, (r.flags & F_RESIDUAL) != 0, l.xp, 1, l.ks);
@@ -689,6 +681,45 @@ int plan(vss_handle* h) {
   return VSS_OK;
 }
 
+// The fragment records (expand_frag, vss_kernels.h) of one hidden slice of an
+// expand layer, from the layer's row-major arrays: w1 [chid][cin], b1 [chid],
+// wdw [chid][9], bdw [chid], w2 [cout][chid]; the slice = hidden channels
+// [h0, h0 + cs), cs a multiple of 16.  out: cs / 16 records of
+// expand_frag(cin, cout).bytes.  Lane l = 16 g + r of the chunk's wave finds
+// exactly the bytes it used to read from the LDS image: lds_a's 4 bf16 of W1
+// row c0 + r at k = 16 s + 4 g and of W2 row 16 cb + r at k = c0 + 4 g, and the
+// float4s b1 / wdw[tap] / bdw at c0 + 4 g.
+void expand_frag_image(int cin, int chid, int cout, int h0, int cs, const float* w1, const float* b1, const float* wdw,
+                       const float* bdw, const float* w2, unsigned char* out) {
+  const ExpandFrag F = expand_frag(cin, cout);
+  for (int ck = 0; ck < cs / 16; ++ck) {
+    unsigned char* rec = out + (size_t)ck * F.bytes;
+    const int c0 = h0 + 16 * ck;  // the chunk's first hidden channel in the layer
+    for (int l = 0; l < 64; ++l) {
+      const int r = l & 15, g = l >> 4;
+      for (int s = 0; s < F.NK; ++s) {
+        uint16_t v[4];
+        for (int e = 0; e < 4; ++e) v[e] = bf16_bits(w1[(size_t)(c0 + r) * cin + 16 * s + 4 * g + e]);
+        std::memcpy(rec + F.aw + frag_off(F.NK, s, l), v, 8);
+      }
+      for (int cb = 0; cb < F.NCB; ++cb) {
+        uint16_t v[4];
+        for (int e = 0; e < 4; ++e) v[e] = bf16_bits(w2[(size_t)(16 * cb + r) * chid + c0 + 4 * g + e]);
+        std::memcpy(rec + F.a2 + frag_off(F.NCB, cb, l), v, 8);
+      }
+    }
+    for (int g = 0; g < 4; ++g)
+      for (int k = 0; k < kFragF4; ++k) {
+        float v[4];
+        for (int e = 0; e < 4; ++e) {
+          const int c = c0 + 4 * g + e;
+          v[e] = k == 0 ? b1[c] : (k == 10 ? bdw[c] : wdw[(size_t)c * 9 + (k - 1)]);
+        }
+        std::memcpy(rec + F.f4s + (4 * k + g) * 16, v, 16);
+      }
+  }
+}
+
 int upload(vss_handle* h) {
   float* d_data = nullptr;
   int rc = dalloc(h, &d_data, h->hdata.size() * 4);
@@ -696,10 +727,14 @@ int upload(vss_handle* h) {
   HIP_TRY(h, hipMemcpy(d_data, h->hdata.data(), h->hdata.size() * 4, hipMemcpyHostToDevice));
   auto dp = [&](uint32_t off) -> const float* { return off == kNone ? nullptr : d_data + off; };
   // Per-layer LDS weight images: the exact bytes of block_lds regions w1..b2
-  // (pointwise weights as bf16 rows padded to LD1/LD2, dw weights [9][C],
-  // biases), so the kernel prologue is one flat 16-B copy.
+  // (W2 as bf16 rows padded to LD2, dw weights [9][C], biases; an expand
+  // layer's: the project bias only), so the kernel prologue is one flat 16-B
+  // copy.  Expand layers read everything else from their fragment records
+  // (expand_frag_image), which stay in HBM.
   std::vector<float> img;
   std::vector<size_t> img_off(h->L.size(), 0), img_len(h->L.size(), 0);
+  std::vector<unsigned char> frag;
+  std::vector<size_t> frag_off_(h->L.size(), 0), frag_len(h->L.size(), 0);
   for (size_t i = 0; i < h->L.size(); ++i) {
     const LayerPlan& l = h->L[i];
     const Rec& r = l.rec;
@@ -728,11 +763,18 @@ int upload(vss_handle* h) {
       img.resize(base + span, 0.f);
       float* im = img.data() + base;
       auto bf = [&](uint32_t off, size_t k) { return bf16_bits(h->hdata[off + k]); };
+      for (int c = 0; c < l.C; ++c) im[B.b2 - B.w1 + c] = h->hdata[r.off[O_B2] + c];
       if (expand) {
-        uint16_t* d = reinterpret_cast<uint16_t*>(im + (B.w1 - B.w1));
-        for (int a = 0; a < cs; ++a)
-          for (int b = 0; b < (int)r.cin; ++b) d[(size_t)a * B.LD1 + b] = bf(r.off[O_W1], (size_t)(h0 + a) * r.cin + b);
-        for (int c = 0; c < cs; ++c) im[B.b1 - B.w1 + c] = h->hdata[r.off[O_B1] + h0 + c];
+        const size_t fb = (size_t)(cs / 16) * expand_frag((int)r.cin, l.C).bytes;
+        if (sl == 0) {
+          frag_off_[i] = frag.size();
+          frag_len[i] = fb;
+        }
+        frag.resize(frag.size() + fb, 0);
+        expand_frag_image((int)r.cin, l.chid, l.C, h0, cs, &h->hdata[r.off[O_W1]], &h->hdata[r.off[O_B1]],
+                          &h->hdata[r.off[O_WDW]], &h->hdata[r.off[O_BDW]], &h->hdata[r.off[O_W2]],
+                          frag.data() + frag.size() - fb);
+        continue;
       }
       uint16_t* d2 = reinterpret_cast<uint16_t*>(im + (B.w2 - B.w1));
       for (int a = 0; a < l.C; ++a)
@@ -740,9 +782,12 @@ int upload(vss_handle* h) {
       for (int t = 0; t < 9; ++t)
         for (int c = 0; c < cs; ++c) im[B.wdw - B.w1 + t * cs + c] = h->hdata[r.off[O_WDW] + (size_t)(h0 + c) * 9 + t];
       for (int c = 0; c < cs; ++c) im[B.bdw - B.w1 + c] = h->hdata[r.off[O_BDW] + h0 + c];
-      for (int c = 0; c < l.C; ++c) im[B.b2 - B.w1 + c] = h->hdata[r.off[O_B2] + c];
     }
   }
+  // (records are 64-B multiples and hipMalloc's base is aligned: every record starts a cache line)
+  unsigned char* d_frag = nullptr;
+  if ((rc = dalloc(h, &d_frag, frag.size()))) return rc;
+  if (!frag.empty()) HIP_TRY(h, hipMemcpy(d_frag, frag.data(), frag.size(), hipMemcpyHostToDevice));
   float* d_img = nullptr;
   if ((rc = dalloc(h, &d_img, img.size() * 4))) return rc;
   if (!img.empty()) HIP_TRY(h, hipMemcpy(d_img, img.data(), img.size() * 4, hipMemcpyHostToDevice));
@@ -757,6 +802,10 @@ int upload(vss_handle* h) {
     } else if (r.kind == K_IR || r.kind == K_DEC) {
       l.wimg = d_img + img_off[i];
       l.wimg_stride = (long)img_len[i];
+      if (l.mode == MODE_IR_EXPAND) {
+        l.wfrag = reinterpret_cast<const char*>(d_frag) + frag_off_[i];
+        l.wfrag_stride = (long)frag_len[i];
+      }
       if (r.kind == K_DEC) {
         l.gamma = dp(r.off[O_GAMMA]);
         l.beta = dp(r.off[O_BETA]);
@@ -910,6 +959,8 @@ BlockParams block_params(const vss_handle* h, const Slot& s, int li, int n, cons
   BlockParams p{};
   p.wimg = l.wimg;
   p.wimg_stride = l.wimg_stride;
+  p.wfrag = l.wfrag;
+  p.wfrag_stride = l.wfrag_stride;
   p.x_part_stride = (long)src.part_stride;
   p.y_part_stride = (long)l.part_stride;
   p.x = s.act[r.src];
@@ -3831,6 +3882,22 @@ int vss_video_process(vss_video* v, vss_post_state* st, vss_background* bg, cons
 
 // Introspection for the registry generator's LDS mirror (tests/test_registry.py):
 // the bytes of LDS block_lds() carves for one k_block shape.
+// The expand layers' fragment-ordered weight image, without a GPU
+// (tests/test_expand_frag_image.py): the record layout of expand_frag() as
+// {bytes, aw, f4s, a2}, and the records of one hidden slice.
+extern "C" void vss_expand_frag_layout(int cin, int cout, int* out4) {
+  const ExpandFrag F = expand_frag(cin, cout);
+  out4[0] = F.bytes; out4[1] = F.aw; out4[2] = F.f4s; out4[3] = F.a2;
+}
+extern "C" int vss_expand_frag_image(int cin, int chid, int cout, int h0, int cs, const float* w1, const float* b1,
+                                     const float* wdw, const float* bdw, const float* w2, void* out) {
+  if (cin < 16 || cin % 16 || cout < 16 || cout % 16 || chid % 16 || cs < 16 || cs % 16 || h0 < 0 || h0 % 16 ||
+      h0 + cs > chid || !w1 || !b1 || !wdw || !bdw || !w2 || !out)
+    return VSS_E_INVALID_ARG;
+  expand_frag_image(cin, chid, cout, h0, cs, w1, b1, wdw, bdw, w2, static_cast<unsigned char*>(out));
+  return VSS_OK;
+}
+
 extern "C" int vss_block_lds_bytes(int mode, int stride, int th, int tw, int cin, int cskip, int chid, int cout,
                                    int stem_in) {
   return block_lds(mode, stride, th, tw, cin, cskip, chid, cout, stem_in).total * 4;

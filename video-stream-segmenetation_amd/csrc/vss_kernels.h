@@ -138,14 +138,14 @@ __host__ __device__ constexpr int dw_run(int TW, int NPB, int PW) {
 // compile time in the kernel and at run time by the host planner, so the two
 // can never disagree.  Every region is a multiple of 4 floats (16-B aligned).
 struct BlockLds {
-  int IH, IW, P_in, P_in_pad, P_out, CX, XS, LD1, LD2, SR, SC;
+  int IH, IW, P_in, P_in_pad, P_out, CX, XS, LD2, SR, SC;
   // layouts (VSS_SWZ): XQM = xt quad-major (plane XPL floats; XS = 4 then),
   // XSW / RSW / XRW = the xt / slab / residual-centre swizzle modulus (1 = none),
   // HPL = the hidden chunk's plane (floats; 0 = the padded pixel-major chunk)
   bool XQM;
   int XPL, XSW, HPL, RS, RSW, XRW;
   int NCB, NPB, NCHUNK, PW, CS, NPBW, NACC;  // CS = chunk groups, PW = pixel-block groups
-  int xt, xr, w1, w2, wdw, bdw, b1, b2, wimg_end, lr, nrm, uc, work, stt, total;  // [w1, wimg_end): the weight image
+  int xt, xr, w1, w2, wdw, bdw, b2, wimg_end, lr, nrm, uc, work, stt, total;  // [w1, wimg_end): the weight image
   int slab_stride;  // floats per wave slab = P_out * (cout + 4)
   int slab;         // the epilogue's accumulator slabs: the work region, or (decoder) the input tile
 };
@@ -186,8 +186,7 @@ __host__ __device__ constexpr BlockLds block_lds(int mode, int stride, int TH, i
   L.RS = VSS_SWZ ? cout : cout + 4;
   L.RSW = VSS_SWZ ? pow2div16(cout / 4) : 1;
   L.XRW = VSS_SWZ ? pow2div16(cin / 4) : 1;
-  L.LD1 = cin + 8;   // bf16 elements per W1 row in LDS (16-B aligned rows)
-  L.LD2 = chid + 8;  // bf16 elements per W2 row
+  L.LD2 = chid + 8;  // bf16 elements per W2 row in LDS (16-B aligned rows)
   L.SR = (TH + 1) / 2 + 3;
   L.SC = (TW + 1) / 2 + 3;
   L.NCB = cout / 16;
@@ -212,11 +211,15 @@ __host__ __device__ constexpr BlockLds block_lds(int mode, int stride, int TH, i
   // expand blocks keep xt as MFMA operands (bf16 hi/lo pairs in the split
   // mode); the residual-capable shape keeps the exact f32 centre here
   L.xr = o;  o += (mode == 0 && stride == 1 && cin == cout) ? r4(L.P_out * cin) : 0;
-  L.w1 = o;  o += mode == 0 ? r4(chid * L.LD1 / 2) : 0;
-  L.w2 = o;  o += r4(cout * L.LD2 / 2);
-  L.wdw = o; o += r4(9 * chid);
-  L.bdw = o; o += r4(chid);
-  L.b1 = o;  o += mode == 0 ? r4(chid) : 0;
+  // The LDS weight image.  Direct and decoder blocks: W2 rows, dw taps and
+  // biases, which several waves share.  Expand blocks keep only the project
+  // bias b2 here (the epilogue reads it from every thread): each of their
+  // 16-channel chunks belongs to one wave, which takes the chunk's W1 / W2
+  // fragments, taps and biases straight from global memory (expand_frag below).
+  L.w1 = o;
+  L.w2 = o;  o += mode == 0 ? 0 : r4(cout * L.LD2 / 2);
+  L.wdw = o; o += mode == 0 ? 0 : r4(9 * chid);
+  L.bdw = o; o += mode == 0 ? 0 : r4(chid);
   L.b2 = o;  o += r4(cout);
   L.wimg_end = o;
   // per-wave scratch during the main loop (expand: each wave's hidden chunk
@@ -243,6 +246,38 @@ __host__ __device__ constexpr BlockLds block_lds(int mode, int stride, int TH, i
   L.stt = slab_in_xt ? L.work : L.xt;
   L.total = o;
   return L;
+}
+
+// Fragment-ordered weights of an expand block (built once by the host:
+// expand_frag_image in vss_capi.hip).  One record per 16-channel hidden chunk,
+// holding what the chunk's wave needs in the order it needs it; with lane
+// l = 16 g + r, c0 = the chunk's first hidden channel:
+//   aw  : fragment s < NK = cin / 16 : W1[c0 + r][16 s + 4 g .. + 3], 4 bf16 (8 B)
+//   f4s : 11 float4 per lane group g (the 16 lanes of a group share them):
+//         k = 0: b1[c0 + 4 g ..], k = 1 .. 9: wdw[tap k - 1][c0 + 4 g ..],
+//         k = 10: bdw[c0 + 4 g ..]; float4 k of group g at f4s + (4 k + g) * 16
+//   a2  : fragment cb < NCB = cout / 16 : W2[16 cb + r][c0 + 4 g .. + 3], 8 B
+// A section of N 8-B fragments is stored as N / 2 pairs — lane l's fragments
+// 2 j, 2 j + 1 side by side at j * 1024 + l * 16, one 16-B load per lane, 1 KiB
+// contiguous per wave — followed, for odd N, by the last one at (N / 2) * 1024
+// + l * 8.  Records are 64-B multiples, chunk ck of a slice at ck * bytes.
+struct ExpandFrag {
+  int NK, NCB, aw, f4s, a2, bytes;
+};
+constexpr int kFragF4 = 11;
+__host__ __device__ constexpr ExpandFrag expand_frag(int cin, int cout) {
+  ExpandFrag F{};
+  F.NK = cin / 16;
+  F.NCB = cout / 16;
+  F.aw = 0;
+  F.f4s = F.aw + 512 * F.NK;
+  F.a2 = F.f4s + kFragF4 * 64;
+  F.bytes = F.a2 + 512 * F.NCB;
+  return F;
+}
+// byte offset of lane l's 8-B fragment i within a section of n fragments
+__host__ __device__ constexpr int frag_off(int n, int i, int l) {
+  return (n % 2 == 1 && i == n - 1) ? (n / 2) * 1024 + l * 8 : (i / 2) * 1024 + l * 16 + (i % 2) * 8;
 }
 
 // Fused block: [prologue: stage X tile (or upsample+concat)] ->
@@ -299,6 +334,8 @@ struct BlockParams {
   const float* wimg;     // the layer's LDS weight image (block_lds regions w1..b2), built by the host;
                          // with KS > 1 one image per hidden slice, wimg_stride floats apart
   long wimg_stride;
+  const char* wfrag;     // expand blocks: the chunks' fragment records (expand_frag), slice after slice
+  long wfrag_stride;     // bytes between the slices' records
   long x_part_stride;    // floats between the parts of x / skip / y (see block_flags)
   long skip_part_stride;
   long y_part_stride;

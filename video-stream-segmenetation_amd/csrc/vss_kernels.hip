@@ -14,8 +14,10 @@
 //   k_stem   : tfjs-legacy bilinear resize + /255 computed on the fly into an
 //              LDS tile, fused with the 3x3 s2 stem conv + ReLU6 (VALU).
 //   k_block  : one inverted-residual or decoder block.  The hidden (expanded)
-//              tensor never touches HBM: the workgroup stages the layer's
-//              weights and its input tile (+halo) in LDS once; its 4 waves then
+//              tensor never touches HBM: the workgroup stages its input tile
+//              (+halo) and, where waves share them, the layer's weights in LDS
+//              once (an expand block's waves load their own chunks' weights
+//              from global memory into registers); its 4 waves then
 //              run independent units of 16 hidden channels: expand 1x1 (MFMA)
 //              -> dw 3x3 (VALU, LDS) -> project 1x1 (MFMA) accumulated in
 //              registers; the waves' partial sums meet in LDS in a fixed order.
@@ -404,21 +406,43 @@ template <> struct AFrag<PREC_BF16X2> { using T = bf8; };
 
 // A fragment from the LDS weight image (bf16-exact pointwise weights, rows of
 // `ld` bf16 elements): 4 consecutive weights of row `row` starting at k.
+// (frag_a: the fragment from its 8 bytes, wherever they were read from)
 template <int PREC>
-__device__ __forceinline__ typename AFrag<PREC>::T lds_a(const uint16_t* w, int ld, int row, int k);
+__device__ __forceinline__ typename AFrag<PREC>::T frag_a(uint2 v);
 
 template <>
-__device__ __forceinline__ f4 lds_a<PREC_F32>(const uint16_t* w, int ld, int row, int k) {
-  const uint2 v = *reinterpret_cast<const uint2*>(w + row * ld + k);
+__device__ __forceinline__ f4 frag_a<PREC_F32>(uint2 v) {
   return f4{__uint_as_float(v.x << 16), __uint_as_float(v.x & 0xFFFF0000u), __uint_as_float(v.y << 16),
             __uint_as_float(v.y & 0xFFFF0000u)};
 }
 template <>
-__device__ __forceinline__ bf8 lds_a<PREC_BF16X2>(const uint16_t* w, int ld, int row, int k) {
+__device__ __forceinline__ bf8 frag_a<PREC_BF16X2>(uint2 v) {
   // elements 0-3 pair with the activation hi parts, 4-7 (the same weights) with the lo parts
-  const bf4 b = __builtin_bit_cast(bf4, *reinterpret_cast<const uint2*>(w + row * ld + k));
+  const bf4 b = __builtin_bit_cast(bf4, v);
   return bf8{b.x, b.y, b.z, b.w, b.x, b.y, b.z, b.w};
 }
+template <int PREC>
+__device__ __forceinline__ typename AFrag<PREC>::T lds_a(const uint16_t* w, int ld, int row, int k) {
+  return frag_a<PREC>(*reinterpret_cast<const uint2*>(w + row * ld + k));
+}
+
+// One section of an expand chunk's fragment record (expand_frag, vss_kernels.h)
+// global memory -> registers: lane l's N 8-B fragments, as N / 2 16-B loads
+// (two fragments each) and, for odd N, one 8-B load; every wave-wide load reads
+// consecutive addresses.  `sec` = the section's wave-uniform base.
+template <int N>
+struct FragRegs {
+  uint2 v[N];
+  __device__ __forceinline__ void load(const char* sec, int lane) {
+#pragma unroll
+    for (int j = 0; j < N / 2; ++j) {
+      const uint4 q = *reinterpret_cast<const uint4*>(sec + j * 1024 + lane * 16);
+      v[2 * j] = uint2{q.x, q.y};
+      v[2 * j + 1] = uint2{q.z, q.w};
+    }
+    if constexpr (N % 2 == 1) v[N - 1] = *reinterpret_cast<const uint2*>(sec + (N / 2) * 1024 + lane * 8);
+  }
+};
 
 template <int PREC>
 __device__ __forceinline__ f4 mma16(f4 acc, typename AFrag<PREC>::T a, f4 b);
@@ -570,7 +594,8 @@ struct Staged16 {
 // 16 B per lane, 1 KiB per wave instruction, written straight into LDS — no
 // register staging (Staged<WIMG_F4> held up to ~19 float4s per lane) and no
 // commit stores; the prologue's closing barrier waits for it (dma_wait).
-// Used by the decoders and the blocks whose image is >= 40 KiB (block_wdma):
+// Used by the decoders (block_wdma; the expand blocks' images of >= 40 KiB,
+// which the figures below include, have since left LDS altogether):
 // measured per layer against register staging (profiles/r05ac, isolated
 // event pass, 3 interleaved runs): b7 6.70 -> 6.14 us, b6 6.43 -> 6.23,
 // b5 5.88 -> 5.75, d1 5.06 -> 4.95, d2 6.48 -> 6.22, but b2 6.50 -> 6.85 and
@@ -659,11 +684,9 @@ __device__ __forceinline__ void block_body(const BlockParams& p, int bx, int by,
   const int iy0 = STRIDE * oy0 - 1, ix0 = STRIDE * ox0 - 1;
   const int Ho = p.Ho, Wo = p.Wo;
   float* xt = smem + L.xt;
-  const uint16_t* w1s = reinterpret_cast<const uint16_t*>(smem + L.w1);
   const uint16_t* w2s = reinterpret_cast<const uint16_t*>(smem + L.w2);
   const float* wdws = smem + L.wdw;
   const float* bdws = smem + L.bdw;
-  const float* b1s = smem + L.b1;
   const float* b2s = smem + L.b2;
   float* work = smem + L.work;
   float* slabs = smem + L.slab;
@@ -677,6 +700,23 @@ __device__ __forceinline__ void block_body(const BlockParams& p, int bx, int by,
   };
   auto sq = [&](int sl, int pix, int q) { return sl * SS + pix * RS + 4 * (q ^ gray_swz(pix, L.RSW)); };
   auto rq = [&](int pix, int q) { return pix * CIN + 4 * (q ^ (pix & (L.XRW - 1))); };
+  // Expand blocks: a 16-channel hidden chunk belongs to one wave, which takes
+  // the chunk's weights from its fragment record (expand_frag) in global memory
+  // straight into registers — a wave-uniform record base plus a lane offset.
+  // The W1 fragments and the expand bias of the wave's next chunk travel in
+  // w1f / b1f: the first chunk's go out with the prologue's loads, each later
+  // chunk's during the dw / project phase of the chunk before it.
+  constexpr bool EXPAND = MODE == MODE_IR_EXPAND;
+  constexpr ExpandFrag F = expand_frag(CIN, COUT);
+  const char* frag = EXPAND ? p.wfrag + ks * p.wfrag_stride : nullptr;
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);  // (in an SGPR: record bases are scalar)
+  FragRegs<EXPAND ? F.NK : 1> w1f;
+  f4 b1f;
+  auto load_w1 = [&](int ck) {
+    const char* rec = frag + ck * F.bytes;
+    w1f.load(rec + F.aw, lane);
+    b1f = *reinterpret_cast<const f4*>(rec + F.f4s + g * 16);
+  };
   VSS_STAMP(0);
 
   // ---- prologue: issue every load, then commit to LDS ----
@@ -1078,6 +1118,8 @@ __device__ __forceinline__ void block_body(const BlockParams& p, int bx, int by,
     }
     if constexpr (WDMA && !VSS_WDMA_FIRST) dma_f4<WIMG_F4>(wsrc, reinterpret_cast<f4*>(smem + L.w1));
     st_w.issue([&](int i) { return wsrc[i]; });
+    // (after the input tile's loads: weight loads issued first measured slower, NOTES "Weight DMA order")
+    if constexpr (EXPAND) load_w1(wave_u);
     VSS_STAMP(6);  // every load issued
     st_x.commit_sum([&](int i, int k, f4 v) {
       const int pix = i / GI, c4 = (i - pix * GI) * 4 + k;
@@ -1147,11 +1189,20 @@ __device__ __forceinline__ void block_body(const BlockParams& p, int bx, int by,
     }
     auto expand_chunk = [&](int ck, auto first) {
       constexpr bool FIRST = decltype(first)::value;
-      const int c0 = ck << 4;
+      // the chunk's dw taps, dw bias and W2 fragments go out now and land
+      // behind the expand MFMAs; its W1 fragments and expand bias are already
+      // in flight (w1f / b1f)
+      const char* rec = frag + ck * F.bytes;
+      f4 wk[9];
+#pragma unroll
+      for (int t = 0; t < 9; ++t) wk[t] = *reinterpret_cast<const f4*>(rec + F.f4s + (4 * (1 + t) + g) * 16);
+      const f4 bb = *reinterpret_cast<const f4*>(rec + F.f4s + (4 * 10 + g) * 16);
+      FragRegs<NCB> w2f;
+      w2f.load(rec + F.a2, lane);
       typename AFrag<PREC>::T aw[NK];
 #pragma unroll
-      for (int s = 0; s < NK; ++s) aw[s] = lds_a<PREC>(w1s, L.LD1, c0 + r, 16 * s + 4 * g);
-      const f4 bias = *reinterpret_cast<const f4*>(b1s + c0 + 4 * g);
+      for (int s = 0; s < NK; ++s) aw[s] = frag_a<PREC>(w1f.v[s]);
+      const f4 bias = b1f;
       // (the unroll count from template parameters only: a lambda's pragma
       // cannot name the enclosing function's constexpr locals)
       constexpr int UNRL = block_lds(MODE, STRIDE, TH, TW, CIN, CSKIP, CH, COUT, STEM_IN).P_in_pad / 16 <= 6
@@ -1169,13 +1220,13 @@ __device__ __forceinline__ void block_body(const BlockParams& p, int bx, int by,
       // dw 3x3 computed straight into the project MFMA's B layout: lane (r, g)
       // evaluates pixel r of the block for hidden channels c0+4g..c0+4g+3
       {
-        f4 wk[9];
-#pragma unroll
-        for (int t = 0; t < 9; ++t) wk[t] = *reinterpret_cast<const f4*>(wdws + t * CH + c0 + 4 * g);
-        const f4 bb = *reinterpret_cast<const f4*>(bdws + c0 + 4 * g);
+        // the wave's next chunk's W1 fragments and bias: in flight during this dw / project phase
+        // (unconditional, at a clamped index: behind a branch the waits below
+        // could not count which loads are outstanding and would wait for all)
+        if constexpr (NCHUNK > 4) load_w1(min(ck + 4, NCHUNK - 1));
         typename AFrag<PREC>::T a2[NCB];
 #pragma unroll
-        for (int cb = 0; cb < NCB; ++cb) a2[cb] = lds_a<PREC>(w2s, L.LD2, cb * 16 + r, c0 + 4 * g);
+        for (int cb = 0; cb < NCB; ++cb) a2[cb] = frag_a<PREC>(w2f.v[cb]);
 #pragma unroll
         for (int q = 0; q < NPB / XR; ++q) {
           const int pix0 = run_pix(q, 0), ly = pix0 / TW, lx0 = pix0 % TW;
@@ -1211,8 +1262,8 @@ __device__ __forceinline__ void block_body(const BlockParams& p, int bx, int by,
       wave_sync();  // this chunk's hid reads before the next chunk's expand writes
     };
     static_assert(NCHUNK >= 4, "every wave has a first chunk");
-    expand_chunk(wave, ChunkTag<true>{});
-    for (int ck = wave + 4; ck < NCHUNK; ck += 4) expand_chunk(ck, ChunkTag<false>{});
+    expand_chunk(wave_u, ChunkTag<true>{});
+    for (int ck = wave_u + 4; ck < NCHUNK; ck += 4) expand_chunk(ck, ChunkTag<false>{});
   } else {
     // dw 3x3 straight into the project MFMA's B layout (lane (r, g): pixel r
     // of the block, channels c0+4g..c0+4g+3); no LDS round trip, no syncs.
@@ -1422,8 +1473,27 @@ __device__ __forceinline__ void block_body(const BlockParams& p, int bx, int by,
   VSS_STAMP(3);
 }
 
+// Waves per SIMD the register allocation of a block kernel must allow.  An
+// expand block's weights travel in registers while they are in flight; left
+// alone the compiler spends 130-160 VGPRs on them, fewer waves per SIMD than
+// the block's LDS now admits.  The small tiles (8 wide, <= 32 output pixels,
+// <= 96 input pixels, <= 6 accumulators per wave: what the planner and the
+// autotuner pick for b2..b7 at the headline's size) are held to 4 waves (128
+// VGPRs), 5 for the 16-channel input (b2: its LDS admits 5 workgroups per CU;
+// the 8 waves it had with the dw taps re-read from LDS tap row by tap row
+// would spill here), and 3 / 4 for the exact-f32 MFMA form (more operand
+// registers).  Larger tiles would spill under a floor: theirs is 1 (the
+// compiler's choice).  No kernel uses scratch (`make resource-usage`).
+constexpr int block_min_waves(int mode, int stride, int th, int tw, int cin, int cout, int prec) {
+  if (mode != MODE_IR_EXPAND) return 1;
+  const BlockLds L = block_lds(mode, stride, th, tw, cin, 0, 64, cout);  // (geometry only: chid does not matter)
+  if (tw != 8 || L.P_out > 32 || L.P_in_pad > 96 || L.NPB * L.NCB > 6) return 1;
+  return prec == PREC_F32 ? (cin == 16 ? 4 : 3) : (cin == 16 ? 5 : 4);
+}
+
 template <int MODE, int STRIDE, int TH, int TW, int CIN, int CSKIP, int CH, int COUT, int FLAGS, int PREC>
-__global__ __launch_bounds__(256) void k_block(BlockParams p) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(block_min_waves(MODE, STRIDE, TH, TW, CIN, COUT, PREC))))
+void k_block(BlockParams p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const TileIdx t = xcd_tile();
   block_body<MODE, STRIDE, TH, TW, CIN, CSKIP, CH, COUT, FLAGS, PREC, false>(p, t.x, t.y, t.z, smem);
