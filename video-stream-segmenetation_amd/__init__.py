@@ -194,6 +194,12 @@ def lib() -> ctypes.CDLL:
                 "vss_video_set_standard": ([P, I], I),
                 "vss_video_process_device": ([P, P, P, P, S, S, P, S, S, I, I, I, P, S, S, P, S, S, P], I),
                 "vss_video_process": ([P, P, P, P, P, I, I, I, P, P], I),
+                "vss_post_pool_create": ([P, ctypes.POINTER(PostConfig), I, ctypes.POINTER(P)], I),
+                "vss_post_pool_destroy": ([P], None),
+                "vss_post_pool_set_config": ([P, ctypes.POINTER(PostConfig)], I),
+                "vss_post_pool_reset": ([P, I], I),
+                "vss_post_pool_process_device": ([P, P, I, P, I, I, I, S, S, P, P, P, P, P], I),
+                "vss_segment_post_pool": ([P, P, P, P, I, I, I, I, S, P, P], I),
             }
             for name, (args, res) in sig.items():
                 fn = getattr(L, name)
@@ -544,6 +550,19 @@ class FaceFrame(ctypes.Structure):
         return f
 
 
+def _updated_config(current: PostConfig, config: PostConfig | None, overrides: dict) -> PostConfig:
+    """`config` as given, or a copy of `current` with the overrides applied."""
+    if config is not None:
+        return config
+    c = PostConfig.default()
+    for f, _ in PostConfig._fields_:
+        setattr(c, f, getattr(current, f))
+    for k, v in overrides.items():
+        f = PostConfig.KEYS.get(k, k)
+        setattr(c, f, int(v) if f == "use_bilateral" else float(v))
+    return c
+
+
 class PostChain:
     """The reference's per-stream mask post-processing (processFrame
     frameProcessorTest.ts:115-169: temporalEMA -> morphologicalOpening ->
@@ -570,13 +589,7 @@ class PostChain:
 
     def set_config(self, config: PostConfig | None = None, **overrides):
         """Live knob change (the settings sliders, client/script.ts:16-25)."""
-        c = config if config is not None else PostConfig.default()
-        if config is None:
-            for f, _ in PostConfig._fields_:
-                setattr(c, f, getattr(self.config, f))
-            for k, v in overrides.items():
-                f = PostConfig.KEYS.get(k, k)
-                setattr(c, f, int(v) if f == "use_bilateral" else float(v))
+        c = _updated_config(self.config, config, overrides)
         _check(lib().vss_post_set_config(self._st, ctypes.byref(c)), self.session._h)
         self.config = c
 
@@ -628,6 +641,71 @@ class PostChain:
         _check(lib().vss_postprocess_device(self._st, frames_ptr or None, n, h, w, c, row_stride, frame_stride,
                                             masks_ptr, alpha_ptr or None, alpha_u8_ptr or None, stream or None),
                self.session._h)
+
+
+class PostPool:
+    """The post chain over many streams (include/vss_pool.h): `capacity` streams,
+    numbered from 0, and calls that take ONE frame of each of several streams —
+    the newest frame of every camera that has one.  Each stream's outputs equal
+    those of its own PostChain fed its frames one at a time, whatever the
+    interleaving of calls.  One config for the whole pool."""
+
+    def __init__(self, session: Session, capacity: int, config: PostConfig | None = None, **overrides):
+        self.session = session
+        self.capacity = int(capacity)
+        self.config = config if config is not None else PostConfig.default(**overrides)
+        p = ctypes.c_void_p()
+        _check(lib().vss_post_pool_create(session._h, ctypes.byref(self.config), self.capacity, ctypes.byref(p)),
+               session._h)
+        self._p = p
+        session._posts.append(self)
+
+    def close(self):
+        if getattr(self, "_p", None):
+            lib().vss_post_pool_destroy(self._p)
+            self._p = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def reset(self, stream_id: int | None = None):
+        """The stream's next frame is its first (None: every stream's).  Does not wait for the GPU."""
+        _check(lib().vss_post_pool_reset(self._p, -1 if stream_id is None else int(stream_id)), self.session._h)
+
+    def set_config(self, config: PostConfig | None = None, **overrides):
+        """Live knob change for every stream of the pool, from the next call."""
+        c = _updated_config(self.config, config, overrides)
+        _check(lib().vss_post_pool_set_config(self._p, ctypes.byref(c)), self.session._h)
+        self.config = c
+
+    @staticmethod
+    def _ids(ids, n: int):
+        if len(ids) != n:
+            raise VssError(VSS_E_INVALID_ARG, f"{len(ids)} stream ids for {n} frames")
+        return (ctypes.c_int * n)(*(int(i) for i in ids))
+
+    def process_device(self, ids, frames_ptr: int, n: int, h: int, w: int, c: int, row_stride: int, frame_stride: int,
+                       masks_ptr: int, alpha_ptr: int = 0, u8_ptr: int = 0, stream: int = 0, faces_ptr: int = 0):
+        """HBM in/out: frame t is the next frame of stream ids[t]; faces_ptr = n vss_face_frame in device memory."""
+        _check(lib().vss_post_pool_process_device(self._p, self._ids(ids, n), n, frames_ptr or None, h, w, c,
+                                                  row_stride, frame_stride, masks_ptr or None, faces_ptr or None,
+                                                  alpha_ptr or None, u8_ptr or None, stream or None),
+               self.session._h)
+
+    def segment(self, ids, frames: np.ndarray):
+        """frames [N,H,W,3|4] u8, frame t the next frame of stream ids[t] -> (refinedAlpha f32
+        [N, maskH*maskW], alpha bytes u8 [N, maskH*maskW], maskW, maskH)."""
+        s = self.session
+        f = _as_frames(frames)
+        n, hh, ww, c = f.shape
+        a = np.empty((n, s.mask_h * s.mask_w), np.float32)
+        u = np.empty((n, s.mask_h * s.mask_w), np.uint8)
+        _check(lib().vss_segment_post_pool(s._h, self._p, self._ids(ids, n), f.ctypes.data, n, hh, ww, c, ww * c,
+                                           a.ctypes.data, u.ctypes.data), s._h)
+        return a, u, s.mask_w, s.mask_h
 
 
 def composite_device(session: Session, frames_ptr: int, n: int, h: int, w: int, c: int, row_stride: int,

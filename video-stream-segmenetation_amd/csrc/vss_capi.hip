@@ -2828,18 +2828,42 @@ int post_fail(vss_post_state* st, int code, const std::string& msg) {
 // Bilateral weights as the reference computes them (Math.exp of the same
 // double quotients); built on the host so they are the exact doubles the
 // oracle's libm produces.
-int post_tables(vss_post_state* st) {
-  const vss_post_config& c = st->cfg;
+// sw and (when sigma_range changed: *tab_sigma) the device table rtab; false: the upload failed
+bool post_tables_for(const vss_post_config& c, double* sw, double* rtab, double* tab_sigma) {
   const double ts2 = 2.0 * c.sigma_spatial * c.sigma_spatial, tr2 = 2.0 * c.sigma_range * c.sigma_range;
-  for (int k = 0; k < 3; ++k) st->sw[k] = std::exp(-(double)k / ts2);
-  if (st->tab_sigma != c.sigma_range) {
+  for (int k = 0; k < 3; ++k) sw[k] = std::exp(-(double)k / ts2);
+  if (*tab_sigma != c.sigma_range) {
     std::vector<double> t(kRangeTab);
     for (int r = 0; r < kRangeTab; ++r) t[r] = std::exp(-(double)r / tr2);
-    if (hipMemcpy(st->rtab, t.data(), t.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-      return post_fail(st, VSS_E_HIP, "post: table upload failed");
-    st->tab_sigma = c.sigma_range;
+    if (hipMemcpy(rtab, t.data(), t.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return false;
+    *tab_sigma = c.sigma_range;
   }
+  return true;
+}
+
+int post_tables(vss_post_state* st) {
+  if (!post_tables_for(st->cfg, st->sw, st->rtab, &st->tab_sigma))
+    return post_fail(st, VSS_E_HIP, "post: table upload failed");
   return VSS_OK;
+}
+
+// the filter's parameters that do not depend on where the EMA comes from
+void post_filter_params(PostFilterParams* pf, const vss_handle* h, const vss_post_config& c, const double* sw,
+                        const double* rtab, int fh, int fw, int fc, size_t rs, size_t fs) {
+  const int H = h->cfg.model_h, W = h->cfg.model_w;
+  pf->row_stride = (long)rs;
+  pf->frame_stride = (long)fs;
+  pf->fh = fh; pf->fw = fw; pf->fc = fc;
+  pf->ry = (float)((double)fh / (double)H);
+  pf->rx = (float)((double)fw / (double)W);
+  pf->H = H; pf->W = W;
+  pf->rtab = rtab;
+  for (int k = 0; k < 3; ++k) pf->sw[k] = sw[k];
+  pf->lo = c.noise_cutoff;
+  pf->hi = c.high_threshold;
+  pf->denom = std::max(1e-6, c.high_threshold - c.noise_cutoff);
+  pf->gamma = c.gamma;
+  pf->use_bilateral = c.use_bilateral;
 }
 
 int post_enqueue(vss_post_state* st, const uint8_t* d_frames, int n, int fh, int fw, int fc, size_t rs, size_t fs,
@@ -2888,19 +2912,7 @@ int post_enqueue(vss_post_state* st, const uint8_t* d_frames, int n, int fh, int
   pf.faces = faces;
   pf.ema = st->ema;
   pf.frames = d_frames;
-  pf.row_stride = (long)rs;
-  pf.frame_stride = (long)fs;
-  pf.fh = fh; pf.fw = fw; pf.fc = fc;
-  pf.ry = (float)((double)fh / (double)H);
-  pf.rx = (float)((double)fw / (double)W);
-  pf.H = H; pf.W = W;
-  pf.rtab = st->rtab;
-  for (int k = 0; k < 3; ++k) pf.sw[k] = st->sw[k];
-  pf.lo = st->cfg.noise_cutoff;
-  pf.hi = st->cfg.high_threshold;
-  pf.denom = std::max(1e-6, st->cfg.high_threshold - st->cfg.noise_cutoff);
-  pf.gamma = st->cfg.gamma;
-  pf.use_bilateral = st->cfg.use_bilateral;
+  post_filter_params(&pf, h, st->cfg, st->sw, st->rtab, fh, fw, fc, rs, fs);
   pf.alpha = d_alpha;
   pf.alpha_u8 = d_u8;
   launch_post_filter(pf, n, s);
@@ -3876,6 +3888,211 @@ int vss_video_process(vss_video* v, vss_post_state* st, vss_background* bg, cons
   }
   HIP_TRY(h, hipStreamSynchronize(s));
   return rc;
+}
+
+}  // extern "C"
+
+// ---- the post chain over many streams (vss_post.hip k_post_pool; include/vss_pool.h) ----
+struct vss_post_pool {
+  vss_handle* h = nullptr;
+  std::mutex mu;                  // calls, resets and setters of one pool are serialised
+  vss_post_config cfg{};
+  int capacity = 0;
+  float* planes = nullptr;        // [capacity][2][P] prevAlpha, double-buffered per stream
+  size_t planes_bytes = 0;
+  double* rtab = nullptr;         // one range table for every stream
+  size_t rtab_bytes = 0;
+  double sw[3] = {0, 0, 0};
+  double tab_sigma = -1.0;
+  std::vector<uint8_t> seen;      // per stream: it has seen a frame (prevAlpha exists)
+  std::vector<uint8_t> cur;       // per stream: the plane that holds its prevAlpha
+  std::vector<uint64_t> stamp;    // per stream: the last call that named it (duplicate ids)
+  uint64_t calls = 0;
+  hipEvent_t last = nullptr;      // recorded after every call
+  hipStream_t last_stream = nullptr;
+  bool used = false;
+};
+
+namespace {
+
+// before the table is overwritten or the planes are freed: the pool's latest call has ended
+int pool_quiesce(vss_post_pool* p) {
+  HIP_TRY(p->h, hipSetDevice(p->h->device));
+  if (p->used) HIP_TRY(p->h, hipEventSynchronize(p->last));
+  return VSS_OK;
+}
+
+// p->mu held.  What a call may be refused for, before anything is enqueued.
+int pool_check(vss_post_pool* p, const int* ids, int n, const uint8_t* d_frames, int fh, int fw, int fc, size_t rs,
+               size_t fs, int max_n) {
+  vss_handle* h = p->h;
+  if (!ids) return fail(h, VSS_E_INVALID_ARG, "pool: null stream ids");
+  if (!d_frames && p->cfg.use_bilateral) return fail(h, VSS_E_INVALID_ARG, "pool: null frames with use_bilateral on");
+  if (int rc = check_frames(h, n, fh, fw, fc, rs, fs, max_n)) return rc;
+  const uint64_t call = ++p->calls;
+  for (int t = 0; t < n; ++t) {
+    if (ids[t] < 0 || ids[t] >= p->capacity)
+      return fail(h, VSS_E_INVALID_ARG, "pool: stream id " + std::to_string(ids[t]) + " outside [0, " +
+                                            std::to_string(p->capacity) + ")");
+    if (p->stamp[ids[t]] == call)
+      return fail(h, VSS_E_INVALID_ARG, "pool: stream id " + std::to_string(ids[t]) + " twice in one call");
+    p->stamp[ids[t]] = call;
+  }
+  return VSS_OK;
+}
+
+// p->mu held; arguments checked.  ceil(n / kPoolFrames) launches and the ordering event.
+int pool_enqueue(vss_post_pool* p, const int* ids, int n, const uint8_t* d_frames, int fh, int fw, int fc, size_t rs,
+                 size_t fs, const float* d_masks, const FaceFrame* d_faces, float* d_alpha, uint8_t* d_u8,
+                 hipStream_t s) {
+  vss_handle* h = p->h;
+  const long P = (long)h->cfg.model_h * h->cfg.model_w;
+  if (p->used && p->last_stream != s) HIP_TRY(h, hipStreamWaitEvent(s, p->last, 0));
+  PostPoolParams pp{};
+  post_filter_params(&pp.f, h, p->cfg, p->sw, p->rtab, fh, fw, fc, rs, fs);
+  pp.planes = p->planes;
+  pp.a = p->cfg.ema;
+  hipError_t e = hipSuccess;
+  for (int t0 = 0; t0 < n && e == hipSuccess; t0 += kPoolFrames) {
+    const int m = std::min(kPoolFrames, n - t0);
+    pp.f.faces = d_faces ? d_faces + t0 : nullptr;
+    pp.f.frames = d_frames ? d_frames + (size_t)t0 * fs : nullptr;
+    pp.f.alpha = d_alpha ? d_alpha + t0 * P : nullptr;
+    pp.f.alpha_u8 = d_u8 ? d_u8 + t0 * P : nullptr;
+    pp.masks = d_masks + t0 * P;
+    for (int t = 0; t < m; ++t) {
+      const int id = ids[t0 + t];
+      pp.entry[t] = (unsigned)id << 2 | (unsigned)p->cur[id] << 1 | (unsigned)p->seen[id];
+    }
+    launch_post_pool(pp, m, s);
+    e = hipGetLastError();
+    // the launch is in the stream: these streams' prevAlpha is in their other plane from here on
+    if (e == hipSuccess)
+      for (int t = 0; t < m; ++t) {
+        const int id = ids[t0 + t];
+        p->cur[id] ^= 1;
+        p->seen[id] = 1;
+      }
+  }
+  // also after a failed launch: what did go out reads and writes the planes
+  HIP_TRY(h, hipEventRecord(p->last, s));
+  p->last_stream = s;
+  p->used = true;
+  if (e != hipSuccess) return fail(h, VSS_E_HIP, std::string("pool launch: ") + hipGetErrorString(e));
+  return VSS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vss_post_pool_create(vss_handle* h, const vss_post_config* cfg, int capacity, vss_post_pool** out) {
+  if (!h || !out) return fail(h, VSS_E_INVALID_ARG, "null handle/out");
+  *out = nullptr;
+  if (capacity < 1 || capacity > (1 << 29)) return fail(h, VSS_E_INVALID_ARG, "pool: capacity must be in [1, 2^29]");
+  if (h->cfg.model_h < 3 || h->cfg.model_w < 3) return fail(h, VSS_E_UNSUPPORTED, "mask too small for post");
+  vss_post_config c;
+  if (cfg) c = *cfg;
+  else vss_post_config_default(&c);
+  if (!(c.sigma_spatial > 0) || !(c.sigma_range > 0)) return fail(h, VSS_E_INVALID_ARG, "sigmas must be > 0");
+  HIP_TRY(h, hipSetDevice(h->device));
+  vss_post_pool* p = new vss_post_pool();
+  p->h = h;
+  p->cfg = c;
+  p->capacity = capacity;
+  p->seen.assign(capacity, 0);
+  p->cur.assign(capacity, 0);
+  p->stamp.assign(capacity, 0);
+  const size_t P = (size_t)h->cfg.model_h * h->cfg.model_w;
+  int rc = counted_alloc(h, &p->planes, &p->planes_bytes, (size_t)capacity * 2 * P * 4);
+  if (!rc) rc = counted_alloc(h, &p->rtab, &p->rtab_bytes, (size_t)kRangeTab * 8);
+  if (!rc && hipEventCreateWithFlags(&p->last, hipEventDisableTiming) != hipSuccess)
+    rc = fail(h, VSS_E_HIP, "pool: hipEventCreate failed");
+  if (!rc && !post_tables_for(p->cfg, p->sw, p->rtab, &p->tab_sigma))
+    rc = fail(h, VSS_E_HIP, "pool: table upload failed");
+  if (rc) {
+    vss_post_pool_destroy(p);
+    return rc;
+  }
+  *out = p;
+  return VSS_OK;
+}
+
+void vss_post_pool_destroy(vss_post_pool* p) {
+  if (!p) return;
+  (void)pool_quiesce(p);
+  (void)counted_alloc(p->h, &p->planes, &p->planes_bytes, 0);
+  (void)counted_alloc(p->h, &p->rtab, &p->rtab_bytes, 0);
+  if (p->last) (void)hipEventDestroy(p->last);
+  delete p;
+}
+
+int vss_post_pool_set_config(vss_post_pool* p, const vss_post_config* cfg) {
+  if (!p) return fail(nullptr, VSS_E_INVALID_ARG, "null pool");
+  if (!cfg) return fail(p->h, VSS_E_INVALID_ARG, "pool: null config");
+  if (!(cfg->sigma_spatial > 0) || !(cfg->sigma_range > 0)) return fail(p->h, VSS_E_INVALID_ARG, "sigmas must be > 0");
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (int rc = pool_quiesce(p)) return rc;  // the table may be rewritten
+  p->cfg = *cfg;
+  if (!post_tables_for(p->cfg, p->sw, p->rtab, &p->tab_sigma)) return fail(p->h, VSS_E_HIP, "pool: table upload failed");
+  return VSS_OK;
+}
+
+int vss_post_pool_reset(vss_post_pool* p, int stream_id) {
+  if (!p) return fail(nullptr, VSS_E_INVALID_ARG, "null pool");
+  if (stream_id < -1 || stream_id >= p->capacity)
+    return fail(p->h, VSS_E_INVALID_ARG, "pool: stream id " + std::to_string(stream_id) + " outside [0, " +
+                                             std::to_string(p->capacity) + ") and not -1");
+  std::lock_guard<std::mutex> lk(p->mu);
+  // host state only: the stream's next frame is told that it is the first
+  if (stream_id < 0) std::fill(p->seen.begin(), p->seen.end(), 0);
+  else p->seen[stream_id] = 0;
+  return VSS_OK;
+}
+
+int vss_post_pool_process_device(vss_post_pool* p, const int* stream_ids, int n, const uint8_t* d_frames, int height,
+                                 int width, int channels, size_t row_stride, size_t frame_stride, const float* d_masks,
+                                 const vss_face_frame* d_faces, float* d_alpha, uint8_t* d_alpha_u8, void* stream) {
+  if (!p) return fail(nullptr, VSS_E_INVALID_ARG, "null pool");
+  vss_handle* h = p->h;
+  if (!d_masks) return fail(h, VSS_E_INVALID_ARG, "pool: null masks");
+  std::lock_guard<std::mutex> lk(p->mu);
+  int rc = pool_check(p, stream_ids, n, d_frames, height, width, channels, row_stride, frame_stride,
+                      std::max(h->cfg.max_batch, h->user_max_batch));
+  if (rc) return rc;
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  return pool_enqueue(p, stream_ids, n, d_frames, height, width, channels, row_stride, frame_stride, d_masks,
+                      reinterpret_cast<const FaceFrame*>(d_faces), d_alpha, d_alpha_u8, s);
+}
+
+int vss_segment_post_pool(vss_handle* h, vss_post_pool* p, const int* stream_ids, const uint8_t* frames, int n,
+                          int height, int width, int channels, size_t row_stride, float* alpha_out,
+                          uint8_t* alpha_u8_out) {
+  if (!h || !p || p->h != h) return fail(h, VSS_E_INVALID_ARG, "handle / post pool mismatch");
+  if (!alpha_out && !alpha_u8_out) return fail(h, VSS_E_INVALID_ARG, "no output requested");
+  if (!frames) return fail(h, VSS_E_INVALID_ARG, "null frames");
+  std::lock_guard<std::mutex> pl(h->post_mu);
+  std::lock_guard<std::mutex> ql(p->mu);
+  int rc = pool_check(p, stream_ids, n, frames, height, width, channels, row_stride, row_stride * (size_t)height,
+                      h->cfg.max_batch);
+  if (rc) return rc;
+  std::unique_lock<std::mutex> lk(h->mu);
+  int k = 0;
+  rc = seam_on_stream(h, lk, frames, n, height, width, channels, row_stride, &k);
+  if (rc) return rc;
+  Slot& s = h->slots[k];
+  const size_t P = (size_t)h->cfg.model_h * h->cfg.model_w;
+  float* d_alpha = alpha_out ? h->d_post_alpha : nullptr;
+  uint8_t* d_u8 = alpha_u8_out ? h->d_post_u8 : nullptr;
+  rc = pool_enqueue(p, stream_ids, n, s.d_frames, height, width, channels, row_stride, row_stride * (size_t)height,
+                    s.d_masks, nullptr, d_alpha, d_u8, h->stream);
+  hipError_t e = hipSuccess;
+  if (!rc && alpha_out) e = hipMemcpyAsync(alpha_out, d_alpha, (size_t)n * P * 4, hipMemcpyDeviceToHost, h->stream);
+  if (!rc && e == hipSuccess && alpha_u8_out)
+    e = hipMemcpyAsync(alpha_u8_out, d_u8, (size_t)n * P, hipMemcpyDeviceToHost, h->stream);
+  if (!rc && e != hipSuccess) rc = fail(h, VSS_E_HIP, std::string("D2H: ") + hipGetErrorString(e));
+  return finish_seam(h, lk, k, rc);
 }
 
 }  // extern "C"

@@ -525,6 +525,21 @@ struct PostFilterParams {
   uint8_t* alpha_u8;     // [n][H][W] (may be null)
 };
 
+// The post chain over many streams (k_post_pool): frame t of the launch is the
+// next frame of one stream; its EMA is computed in the filter's tile load from
+// the raw mask and the stream's prevAlpha plane, and stored to the stream's
+// other plane.  The per-frame table travels by value: no device flag, no host
+// wait, nothing read from the caller's memory after the launch.
+constexpr int kPoolFrames = 64;  // frames per launch
+struct PostPoolParams {
+  PostFilterParams f;    // ema unused; faces, frames, alpha, alpha_u8 point at the launch's first frame
+  const float* masks;    // [n][H][W] raw seam masks
+  float* planes;         // [capacity][2][H][W] prevAlpha, double-buffered per stream
+  double a;              // config.EMA
+  unsigned entry[kPoolFrames];  // per frame: stream id << 2 | current plane << 1 | the stream has seen a frame
+};
+void launch_post_pool(const PostPoolParams& p, int n, hipStream_t s);
+
 // Source taps of output index o of the half-pixel bilinear (scale = in / out):
 // shared by the compositing alpha, the frame-resolution masks and the
 // background image's scaling (vss_post.hip, vss_background.hip).

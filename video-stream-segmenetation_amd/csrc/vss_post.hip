@@ -19,6 +19,8 @@
 //                   (halo 3, the 1-px image border left 0), the guide, the
 //                   joint bilateral (weights from a host-built exp table),
 //                   refine, u8 alpha.
+//   k_post_pool   : the same tile for one frame of each of many streams, the
+//                   EMA fused into its tile load (include/vss_pool.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -161,8 +163,13 @@ __device__ __forceinline__ unsigned guide_rgb(const uint8_t* f, long rs, int fc,
 // (morphologicalClosingInPrior :743-787) after the opening, and the prior's
 // clamp in refine; the tile then needs a halo of 5 (erosion, dilation,
 // dilation, erosion, bilateral).
-template <int TH, int TW, bool FACE>
-__global__ __launch_bounds__(256) void k_post_filter(PostFilterParams p) {
+//
+// The stages of one tile, shared by k_post_filter and k_post_pool, which differ
+// only in where the EMA tile comes from: fill(yy, xx, own) returns the EMA value
+// of image pixel (yy, xx); own = the cell is one of the tile's own pixels (not
+// its halo, inside the image), each visited exactly once over the grid.
+template <int TH, int TW, bool FACE, class Fill>
+__device__ __forceinline__ void post_tile(const PostFilterParams& p, Fill fill) {
 #pragma clang fp contract(off)
   constexpr int HE = FACE ? 5 : 3;                                       // halo of the EMA tile
   constexpr int EH = TH + 2 * HE, EW = TW + 2 * HE;                      // EMA        (halo HE)
@@ -180,7 +187,6 @@ __global__ __launch_bounds__(256) void k_post_filter(PostFilterParams p) {
   const int tid = threadIdx.x, t = blockIdx.z;
   const int y0 = blockIdx.y * TH, x0 = blockIdx.x * TW;
   const int H = p.H, W = p.W;
-  const float* e = p.ema + (long)t * H * W;
   bool has_prior = false;
   Prior q{};
   if constexpr (FACE) {
@@ -190,8 +196,10 @@ __global__ __launch_bounds__(256) void k_post_filter(PostFilterParams p) {
   // EMA values on the halo region (outside the image: never read as data)
   for (int i = tid; i < EH * EW; i += 256) {
     const int ly = i / EW, lx = i % EW;
-    const int yy = min(max(y0 - HE + ly, 0), H - 1), xx = min(max(x0 - HE + lx, 0), W - 1);
-    E[ly][lx] = e[(long)yy * W + xx];
+    const int uy = y0 - HE + ly, ux = x0 - HE + lx;
+    const int yy = min(max(uy, 0), H - 1), xx = min(max(ux, 0), W - 1);
+    const bool own = ly >= HE && ly < HE + TH && lx >= HE && lx < HE + TW && uy < H && ux < W;
+    E[ly][lx] = fill(yy, xx, own);
   }
   // guide on the halo-1 region
   if (p.use_bilateral) {
@@ -333,6 +341,69 @@ __global__ __launch_bounds__(256) void k_post_filter(PostFilterParams p) {
   }
 }
 
+template <int TH, int TW, bool FACE>
+__global__ __launch_bounds__(256) void k_post_filter(PostFilterParams p) {
+  const float* e = p.ema + (long)blockIdx.z * p.H * p.W;
+  const int W = p.W;
+  post_tile<TH, TW, FACE>(p, [&](int yy, int xx, bool) { return e[(long)yy * W + xx]; });
+}
+
+// One frame of each of n streams (include/vss_pool.h).  With one frame per
+// stream a call has no recurrence, so the EMA of k_post_ema / k_post_face_ema
+// (the same doubles, contraction off) is computed where the filter loads its
+// tile, halo included, and never makes the [n][P] round trip through HBM.  The
+// tile's own pixels store it as the stream's new prevAlpha — to the stream's
+// OTHER plane, always: a neighbouring tile's halo and every warped tap read
+// prevAlpha at pixels another workgroup owns.
+template <int TH, int TW, bool FACE>
+__global__ __launch_bounds__(256) void k_post_pool(PostPoolParams p) {
+#pragma clang fp contract(off)
+  const int t = blockIdx.z, W = p.f.W, H = p.f.H;
+  const long P = (long)H * W;
+  const unsigned en = p.entry[t];
+  const bool seen = (en & 1u) != 0;  // prevAlpha exists
+  const long cur = (long)(en >> 2) * 2 + ((en >> 1) & 1u);
+  const float* prev = p.planes + cur * P;
+  float* next = p.planes + (cur ^ 1) * P;
+  const float* mask = p.masks + (long)t * P;
+  const double a = p.a;
+  bool warp = false;
+  double ia11 = 0, ia12 = 0, itx = 0, ia21 = 0, ia22 = 0, ity = 0;
+  if constexpr (FACE) {
+    const FaceFrame& f = p.f.faces[t];
+    warp = f.has_affine && seen;
+    if (warp) {  // invertAffine (:323-333)
+      const double a11 = f.affine[0], a12 = f.affine[1], tx = f.affine[2];
+      const double a21 = f.affine[3], a22 = f.affine[4], ty = f.affine[5];
+      const double det = a11 * a22 - a12 * a21;
+      const double d = det != 0.0 ? det : 1e-6;
+      ia11 = a22 / d;
+      ia12 = -a12 / d;
+      ia21 = -a21 / d;
+      ia22 = a11 / d;
+      itx = -(ia11 * tx + ia12 * ty);
+      ity = -(ia21 * tx + ia22 * ty);
+    }
+  }
+  post_tile<TH, TW, FACE>(p.f, [&](int yy, int xx, bool own) {
+#pragma clang fp contract(off)
+    const long i = (long)yy * W + xx;
+    float base = mask[i];
+    if constexpr (FACE) {
+      if (warp) {  // warpAffineNearest(prevAlpha) blended 0.3 / 0.7 into the mask
+        const double sx = ia11 * xx + ia12 * yy + itx, sy = ia21 * xx + ia22 * yy + ity;
+        const double xi = js_round(sx), yi = js_round(sy);
+        const float w = (xi >= 0 && xi < W && yi >= 0 && yi < H) ? prev[(long)yi * W + (long)xi] : 0.f;
+        base = (float)((double)w * 0.3 + (double)base * (1.0 - 0.3));
+      }
+    }
+    // temporalEMA: a stream's first frame passes through and seeds prevAlpha
+    const float e = seen ? (float)(a * (double)prev[i] + (1.0 - a) * (double)base) : base;
+    if (own) next[i] = e;
+    return e;
+  });
+}
+
 // destination-in compositing (frameProcessorTest.ts:170-178, output canvas =
 // the video's size, main.ts:43-44): the frame's colour, alpha = the half-pixel
 // bilinear of the mask's u8 alpha at frame resolution, rounded half up; colour
@@ -426,6 +497,14 @@ void launch_post_filter(const PostFilterParams& p, int n, hipStream_t s) {
     hipLaunchKernelGGL((k_post_filter<kPostTH, kPostTW, true>), grid, dim3(256), 0, s, p);
   else
     hipLaunchKernelGGL((k_post_filter<kPostTH, kPostTW, false>), grid, dim3(256), 0, s, p);
+}
+
+void launch_post_pool(const PostPoolParams& p, int n, hipStream_t s) {
+  const dim3 grid((p.f.W + kPostTW - 1) / kPostTW, (p.f.H + kPostTH - 1) / kPostTH, n);
+  if (p.f.faces)
+    hipLaunchKernelGGL((k_post_pool<kPostTH, kPostTW, true>), grid, dim3(256), 0, s, p);
+  else
+    hipLaunchKernelGGL((k_post_pool<kPostTH, kPostTW, false>), grid, dim3(256), 0, s, p);
 }
 
 }  // namespace vss

@@ -35,6 +35,10 @@
 //       -> Promise<{alpha: Float32Array, alphaU8: Uint8Array}>   (processFrame :78-169)
 //   segmentComposite(handle, post, frames, n, height, width, channels, rowStride)
 //       -> Promise<Uint8Array>   RGBA output canvases, n * height * width * 4 (:78-178)
+//   poolCreate(handle, capacity, config?) -> pool   the post chain over many streams (vss_pool.h)
+//   poolSetConfig(pool, config), poolReset(pool, id) (id -1: every stream), poolDestroy(pool)
+//   segmentPostPool(handle, pool, ids: number[], frames, n, height, width, channels, rowStride)
+//       -> Promise<{alpha, alphaU8}>   frame t = the next frame of stream ids[t]
 //   backgroundCreate(handle) -> background   what goes behind the person (include/vss.h, virtual
 //       backgrounds); the colour (32, 32, 32) until a setter is called (u2FrameProc.ts:89)
 //   backgroundSetColor(background, r, g, b)
@@ -99,6 +103,7 @@ namespace {
 std::atomic<bool> g_env_closing{false};
 
 struct Post;
+struct Pool;
 struct Bg;
 struct Vid;
 struct Submitter;
@@ -107,7 +112,8 @@ struct Handle {
   vss_handle* h = nullptr;
   int mask_h = 0, mask_w = 0;
   std::vector<Post*> posts;  // destroyed before the handle, whatever order the GC finalizes in
-  std::vector<Bg*> bgs;      // the same for the backgrounds
+  std::vector<Pool*> pools;  // the same for the post pools
+  std::vector<Bg*> bgs;      // ... the backgrounds
   std::vector<Vid*> vids;    // ... and the NV12 video objects
   // Queued batches whose libuv work still holds h (JS thread only): destroy()
   // or the GC finalizer while some are pending defers vss_destroy to the last
@@ -123,6 +129,11 @@ void stop_submitter(Handle* hd);  // (pending == 0: joins the thread, releases t
 struct Post {
   Handle* hd = nullptr;
   vss_post_state* st = nullptr;
+};
+
+struct Pool {
+  Handle* hd = nullptr;
+  vss_post_pool* p = nullptr;
 };
 
 struct Bg {
@@ -144,6 +155,12 @@ void release_handle(Handle* hd) {
     p->hd = nullptr;
   }
   hd->posts.clear();
+  for (Pool* q : hd->pools) {
+    if (q->p) vss_post_pool_destroy(q->p);
+    q->p = nullptr;
+    q->hd = nullptr;
+  }
+  hd->pools.clear();
   for (Bg* b : hd->bgs) {
     if (b->bg) vss_background_destroy(b->bg);
     b->bg = nullptr;
@@ -187,6 +204,19 @@ void finalize_post(napi_env, void* data, void*) {
   Post* p = static_cast<Post*>(data);
   release_post(p);
   delete p;
+}
+
+void release_pool(Pool* q) {
+  if (q->p) vss_post_pool_destroy(q->p);
+  q->p = nullptr;
+  if (q->hd) q->hd->pools.erase(std::remove(q->hd->pools.begin(), q->hd->pools.end(), q), q->hd->pools.end());
+  q->hd = nullptr;
+}
+
+void finalize_pool(napi_env, void* data, void*) {
+  Pool* q = static_cast<Pool*>(data);
+  release_pool(q);
+  delete q;
 }
 
 void release_bg(Bg* b) {
@@ -523,6 +553,83 @@ napi_value PostDestroy(napi_env env, napi_callback_info info) {
   NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
   void* p = nullptr;
   if (argc >= 1 && napi_get_value_external(env, argv[0], &p) == napi_ok && p) release_post(static_cast<Post*>(p));
+  return nullptr;
+}
+
+// ---- the post chain over many streams (include/vss_pool.h) ----------------------
+Pool* get_pool(napi_env env, napi_value v) {
+  void* p = nullptr;
+  if (napi_get_value_external(env, v, &p) != napi_ok || !p) {
+    napi_throw_type_error(env, nullptr, "expected a vss post pool");
+    return nullptr;
+  }
+  Pool* q = static_cast<Pool*>(p);
+  if (!q->p) {
+    napi_throw_error(env, nullptr, "vss post pool already destroyed");
+    return nullptr;
+  }
+  return q;
+}
+
+napi_value PoolCreate(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Handle* hd = argc >= 2 ? get_handle(env, argv[0]) : nullptr;
+  if (!hd) return nullptr;
+  int capacity = 0;
+  napi_get_value_int32(env, argv[1], &capacity);
+  vss_post_config cfg;
+  vss_post_config_default(&cfg);
+  if (argc >= 3) read_post_config(env, argv[2], &cfg);
+  vss_post_pool* pp = nullptr;
+  const int rc = vss_post_pool_create(hd->h, &cfg, capacity, &pp);
+  if (rc != VSS_OK) {
+    throw_vss(env, "vss_post_pool_create", rc, vss_last_error(hd->h));
+    return nullptr;
+  }
+  Pool* q = new Pool();
+  q->hd = hd;
+  q->p = pp;
+  hd->pools.push_back(q);
+  napi_value ext;
+  NAPI_OK(env, napi_create_external(env, q, finalize_pool, nullptr, &ext));
+  return ext;
+}
+
+napi_value PoolSetConfig(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Pool* q = argc >= 2 ? get_pool(env, argv[0]) : nullptr;
+  if (!q) return nullptr;
+  vss_post_config cfg;
+  vss_post_config_default(&cfg);
+  read_post_config(env, argv[1], &cfg);
+  const int rc = vss_post_pool_set_config(q->p, &cfg);
+  if (rc != VSS_OK) throw_vss(env, "vss_post_pool_set_config", rc, vss_last_error(q->hd->h));
+  return nullptr;
+}
+
+napi_value PoolReset(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Pool* q = argc >= 1 ? get_pool(env, argv[0]) : nullptr;
+  if (!q) return nullptr;
+  int id = -1;
+  if (argc >= 2) napi_get_value_int32(env, argv[1], &id);
+  const int rc = vss_post_pool_reset(q->p, id);
+  if (rc != VSS_OK) throw_vss(env, "vss_post_pool_reset", rc, vss_last_error(q->hd->h));
+  return nullptr;
+}
+
+napi_value PoolDestroy(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  void* p = nullptr;
+  if (argc >= 1 && napi_get_value_external(env, argv[0], &p) == napi_ok && p) release_pool(static_cast<Pool*>(p));
   return nullptr;
 }
 
@@ -1256,6 +1363,8 @@ struct SegmentWork {
   Handle* hd = nullptr;                  // pending counted until SegmentComplete
   vss_handle* h = nullptr;
   vss_post_state* post = nullptr;        // segmentPost / segmentComposite
+  vss_post_pool* pool = nullptr;         // segmentPostPool: one frame of each of these streams
+  std::vector<int> ids;
   bool composite = false;                // segmentComposite: out_u8 holds the RGBA canvases
   vss_background* bg = nullptr;          // segmentBackground: ... composited over this
   const uint8_t* frames = nullptr;
@@ -1269,7 +1378,10 @@ struct SegmentWork {
 
 void SegmentExecute(napi_env, void* data) {  // libuv worker thread: no JS calls here
   SegmentWork* w = static_cast<SegmentWork*>(data);
-  if (w->bg)
+  if (w->pool)
+    w->rc = vss_segment_post_pool(w->h, w->pool, w->ids.data(), w->frames, w->n, w->height, w->width, w->channels,
+                                  w->row_stride, w->out, w->out_u8);
+  else if (w->bg)
     w->rc = vss_segment_background(w->h, w->post, w->bg, w->frames, w->n, w->height, w->width, w->channels,
                                    w->row_stride, w->out_u8);
   else if (w->composite)
@@ -1293,7 +1405,7 @@ void SegmentComplete(napi_env env, napi_status, void* data) {
   } else if (w->rc == VSS_OK) {
     napi_value arr;
     napi_create_typedarray(env, napi_float32_array, w->out_count, ab, 0, &arr);
-    if (w->post) {
+    if (w->post || w->pool) {
       napi_value ab8 = nullptr, arr8, o;
       napi_get_reference_value(env, w->u8_ref, &ab8);
       napi_create_typedarray(env, napi_uint8_array, w->out_count, ab8, 0, &arr8);
@@ -1306,8 +1418,9 @@ void SegmentComplete(napi_env env, napi_status, void* data) {
     }
   } else {
     napi_value msg, code, e;
-    const std::string m = std::string(w->bg ? "vss_segment_background"
-                                            : (w->composite ? "vss_segment_composite" : "vss_segment_post")) + " failed (" +
+    const std::string m = std::string(w->pool ? "vss_segment_post_pool"
+                                      : w->bg ? "vss_segment_background"
+                                              : (w->composite ? "vss_segment_composite" : "vss_segment_post")) + " failed (" +
                           std::to_string(w->rc) + "): " + w->err;
     napi_create_string_utf8(env, m.c_str(), m.size(), &msg);
     napi_create_string_utf8(env, std::to_string(w->rc).c_str(), NAPI_AUTO_LENGTH, &code);
@@ -1323,22 +1436,49 @@ void SegmentComplete(napi_env env, napi_status, void* data) {
   work_done(hd);
 }
 
-// segmentPost(handle, post, frames, ...), segmentComposite(handle, post, frames, ...) and
-// segmentBackground(handle, post, frames, ..., background)
+// segmentPost(handle, post, frames, ...), segmentComposite(handle, post, frames, ...),
+// segmentBackground(handle, post, frames, ..., background) and (pooled)
+// segmentPostPool(handle, pool, ids, frames, ...)
 napi_value SegmentImpl(napi_env env, napi_callback_info info, bool with_post, bool composite = false,
-                       bool background = false) {
+                       bool background = false, bool pooled = false) {
   size_t argc = 9;
   napi_value all[9];
   NAPI_OK(env, napi_get_cb_info(env, info, &argc, all, nullptr, nullptr));
-  const size_t need = with_post ? 8 : 7;
+  const size_t need = pooled ? 9 : with_post ? 8 : 7;
   if (argc < need) {
     napi_throw_type_error(env, nullptr,
-                          with_post ? "segmentPost(handle, post, frames, n, height, width, channels, rowStride)"
-                                    : "segment(handle, frames, n, height, width, channels, rowStride)");
+                          pooled ? "segmentPostPool(handle, pool, ids, frames, n, height, width, channels, rowStride)"
+                          : with_post ? "segmentPost(handle, post, frames, n, height, width, channels, rowStride)"
+                                      : "segment(handle, frames, n, height, width, channels, rowStride)");
     return nullptr;
   }
   Handle* hd = get_handle(env, all[0]);
   if (!hd) return nullptr;
+  Pool* pl = nullptr;
+  std::vector<int> ids;
+  if (pooled) {
+    pl = get_pool(env, all[1]);
+    if (!pl) return nullptr;
+    if (pl->hd != hd) {
+      napi_throw_error(env, nullptr, "post pool belongs to another handle");
+      return nullptr;
+    }
+    bool is_arr = false;
+    uint32_t cnt = 0;
+    if (napi_is_array(env, all[2], &is_arr) != napi_ok || !is_arr || napi_get_array_length(env, all[2], &cnt) != napi_ok) {
+      napi_throw_type_error(env, nullptr, "segmentPostPool: ids must be an array of stream ids, one per frame");
+      return nullptr;
+    }
+    ids.resize(cnt);
+    for (uint32_t k = 0; k < cnt; ++k) {
+      napi_value e;
+      napi_get_element(env, all[2], k, &e);
+      if (napi_get_value_int32(env, e, &ids[k]) != napi_ok) {
+        napi_throw_type_error(env, nullptr, "segmentPostPool: ids must be an array of stream ids, one per frame");
+        return nullptr;
+      }
+    }
+  }
   Post* ps = nullptr;
   if (with_post) {
     ps = get_post(env, all[1]);
@@ -1362,7 +1502,7 @@ napi_value SegmentImpl(napi_env env, napi_callback_info info, bool with_post, bo
       return nullptr;
     }
   }
-  napi_value* argv = with_post ? all + 1 : all;
+  napi_value* argv = pooled ? all + 2 : with_post ? all + 1 : all;
   bool is_ta = false;
   napi_is_typedarray(env, argv[1], &is_ta);
   if (!is_ta) {
@@ -1391,10 +1531,17 @@ napi_value SegmentImpl(napi_env env, napi_callback_info info, bool with_post, bo
     napi_throw_range_error(env, nullptr, "frames buffer smaller than n * height * rowStride");
     return nullptr;
   }
+  if (pooled && ids.size() != (size_t)w->n) {
+    delete w;
+    napi_throw_range_error(env, nullptr, "segmentPostPool: one stream id per frame");
+    return nullptr;
+  }
   w->h = hd->h;
+  w->pool = pl ? pl->p : nullptr;
+  w->ids = std::move(ids);
   w->post = ps ? ps->st : nullptr;
   w->frames = static_cast<const uint8_t*>(data);
-  if (!with_post && argc >= 8) napi_get_value_int32(env, argv[7], &w->out_mode);
+  if (!with_post && !pooled && argc >= 8) napi_get_value_int32(env, argv[7], &w->out_mode);  // segment()'s outMode
   w->out_count = w->out_mode == VSS_OUT_FRAME ? (size_t)w->n * w->height * w->width
                                               : (size_t)w->n * hd->mask_h * hd->mask_w;
   napi_value ab;
@@ -1403,7 +1550,7 @@ napi_value SegmentImpl(napi_env env, napi_callback_info info, bool with_post, bo
   w->out = static_cast<float*>(out);
   w->composite = composite;
   w->bg = bgp ? bgp->bg : nullptr;
-  if (ps) {
+  if (ps || pl) {
     napi_value ab8;
     void* out8 = nullptr;
     const size_t bytes8 = composite ? (size_t)w->n * w->height * w->width * 4 : w->out_count;
@@ -1424,6 +1571,9 @@ napi_value SegmentImpl(napi_env env, napi_callback_info info, bool with_post, bo
 }
 
 napi_value SegmentPost(napi_env env, napi_callback_info info) { return SegmentImpl(env, info, true); }
+napi_value SegmentPostPool(napi_env env, napi_callback_info info) {
+  return SegmentImpl(env, info, false, false, false, true);
+}
 napi_value SegmentComposite(napi_env env, napi_callback_info info) { return SegmentImpl(env, info, true, true); }
 napi_value SegmentBackground(napi_env env, napi_callback_info info) { return SegmentImpl(env, info, true, true, true); }
 
@@ -2139,6 +2289,11 @@ napi_value Init(napi_env env, napi_value exports) {
       {"postDestroy", nullptr, PostDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"postSetFaces", nullptr, PostSetFaces, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"segmentPost", nullptr, SegmentPost, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"poolCreate", nullptr, PoolCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"poolSetConfig", nullptr, PoolSetConfig, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"poolReset", nullptr, PoolReset, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"poolDestroy", nullptr, PoolDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"segmentPostPool", nullptr, SegmentPostPool, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"segmentComposite", nullptr, SegmentComposite, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"backgroundCreate", nullptr, BackgroundCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"backgroundSetColor", nullptr, BackgroundSetColor, nullptr, nullptr, nullptr, napi_default, nullptr},
