@@ -91,12 +91,13 @@ def block_lds_bytes(mode, stride, th, tw, cin, cskip, chid, cout, stem_in=False)
     f += r4(cout * (chid + 8) // 2) + r4(9 * chid) + r4(chid) if mode != 0 else 0
     f += r4(cout)
     f += r4(2 * cin) if mode == 2 else 0
-    f += 4 * p_in_pad if mode == 2 and (th % 2 or tw % 2) else 0  # the decoder's upsample tap records (L.uc; odd tiles)
-    # work: expand scratch / slabs / (decoder) the low-res src region; the
-    # decoder's slabs go into xt when they fit (its stats scratch then in work)
+    dec_odd = mode == 2 and bool(th % 2 or tw % 2)  # even decoder tiles upsample from registers (dec_quads)
+    f += 4 * p_in_pad if dec_odd else 0  # the decoder's upsample tap records (L.uc; odd tiles)
+    # work: expand scratch / slabs / (odd decoder tiles) the low-res src region;
+    # the decoder's slabs go into xt when they fit (its stats scratch then in work)
     slab_in_xt = mode == 2 and cs * p_out * rs <= xt_floats
     f += max(hid if mode == 0 else 1024, 0 if slab_in_xt else cs * p_out * rs,
-             r4(sr * sc * cin) if mode == 2 else 0, stem_in_lds(ih, iw) if stem_in else 0)
+             r4(sr * sc * cin) if dec_odd else 0, stem_in_lds(ih, iw) if stem_in else 0)
     return f * 4, nacc
 
 

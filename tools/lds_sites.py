@@ -103,10 +103,11 @@ class Lds:
         slab_in_xt = mode == 2 and self.CS * self.slab_stride <= xt_floats
         self.work = self.lr = o
         stem = r4(3 * (2 * self.IH + 1) * (2 * self.IW + 2)) + 27 * 16 + 16 if stem_in else 0
-        o += max(4 * self.P_in_pad * self.HSD if mode == 0 else 1024, 0 if slab_in_xt else self.CS * self.slab_stride,
-                 r4(self.SR * self.SC * cin) if mode == 2 else 0, stem)
-        self.nrm = o; o += r4(2 * cin) if mode == 2 else 0
+        # even decoder tiles upsample from tap registers: no low-res src region (dec_quads)
         self.quads = quads and TH % 2 == 0 and TW % 2 == 0
+        o += max(4 * self.P_in_pad * self.HSD if mode == 0 else 1024, 0 if slab_in_xt else self.CS * self.slab_stride,
+                 r4(self.SR * self.SC * cin) if (mode == 2 and not self.quads) else 0, stem)
+        self.nrm = o; o += r4(2 * cin) if mode == 2 else 0
         self.uc = o; o += 4 * self.P_in_pad if (mode == 2 and not self.quads) else 0
         self.slab = self.xt if slab_in_xt else self.work
         self.stt = self.work if slab_in_xt else self.xt
@@ -159,7 +160,7 @@ class Lds:
         self.work = self.lr = o
         stem = r4(3 * (2 * self.IH + 1) * self.xwp) + 27 * 16 + 16 if self.stem_in else 0
         o += max((16 * self.HPL if self.hqm else 4 * self.P_in_pad * self.HSD) if mode == 0 else 1024, 0 if slab_in_xt else self.CS * self.slab_stride,
-                 r4(self.SR * self.SC * self.cin) if mode == 2 else 0, stem)
+                 r4(self.SR * self.SC * self.cin) if (mode == 2 and not self.quads) else 0, stem)
         self.nrm = o; o += r4(2 * self.cin) if mode == 2 else 0
         self.uc = o; o += 4 * self.P_in_pad if (mode == 2 and not self.quads) else 0
         self.slab = self.xt if slab_in_xt else self.work
@@ -240,18 +241,8 @@ def sites(L, tile, img, stem_geo=None):
         for w in range(4):
             emit("dec: scale/shift writes (w32)", "w32", w, lambda t: L.nrm + t if t < CL else None)
             emit("dec: scale/shift writes (w32)", "w32", w, lambda t: L.nrm + CL + t if t < CL else None)
-        # lr commit (float4 j -> lane j % 256): lr[4 * item + k] = lr f4 index j
-        tot = 4 * SR * SC * GL
-        for u in range((tot + 255) // 256):
-            for w in range(4):
-                emit("dec: src region commit (w128)", "w128", w,
-                     lambda t, u=u: L.lr + 4 * (t + 256 * u) if t + 256 * u < tot else None)
-            # norm scale/shift reads on commit (two f4 per item, by channel group)
-            for w in range(4):
-                for base in (0, CL):
-                    emit("dec: commit scale/shift (r128)", "r128", w,
-                         lambda t, u=u, base=base: L.nrm + base + 4 * (((t + 256 * u) >> 2) % GL * 4 + ((t + 256 * u) & 3))
-                         if t + 256 * u < tot else None)
+        # (even tiles: no src region in LDS — every (quad, channel quad) item
+        # takes its four taps from global memory into registers)
         tot = 4 * L.P_in_pad * GS
         for u in range((tot + 255) // 256):
             for w in range(4):
@@ -272,9 +263,6 @@ def sites(L, tile, img, stem_geo=None):
         assert L.quads
         QH, QW = L.IH // 2, IW // 2
         NQI = QH * QW * C4L
-        sy0, sx0 = max(0, (oy0 - 1) // 2 - 1), max(0, (ox0 - 1) // 2 - 1)
-        j0, i0 = (iy0 - 1) // 2 if iy0 >= 1 else -1, (ix0 - 1) // 2 if ix0 >= 1 else -1
-        jr, ic = j0 - sy0, i0 - sx0
         for k in range((NQI + 255) // 256):
             def quad(t, k=k):
                 it = t + 256 * k
@@ -283,16 +271,10 @@ def sites(L, tile, img, stem_geo=None):
                 c4, qq = it % C4L, it // C4L
                 return c4, qq % QW, qq // QW
             for w in range(4):
-                for dr, dc in ((0, 0), (0, 1), (1, 0), (1, 1)):
-                    def rd(t, dr=dr, dc=dc):
-                        q = quad(t)
-                        if q is None:
-                            return None
-                        c4, qx, qy = q
-                        ra = min(max(qy + jr + dr, 0), SR - 1)
-                        ca = min(max(qx + ic + dc, 0), SC - 1)
-                        return L.lr + ra * (SC * CL) + 4 * c4 + ca * CL
-                    emit("dec: upsample tap reads (r128)", "r128", w, rd)
+                # the src norm's scale / shift of the item's channel quad (its four taps share them)
+                for base in (0, CL):
+                    emit("dec: tap scale/shift (r128)", "r128", w,
+                         lambda t, base=base: None if quad(t) is None else L.nrm + base + 4 * quad(t)[0])
                 for dy, dx in ((0, 0), (0, 1), (1, 0), (1, 1)):
                     def wr(t, dy=dy, dx=dx):
                         q = quad(t)

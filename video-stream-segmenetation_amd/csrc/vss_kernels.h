@@ -225,23 +225,28 @@ __host__ __device__ constexpr BlockLds block_lds(int mode, int stride, int TH, i
   // per-wave scratch during the main loop (expand: each wave's hidden chunk
   // over the input tile), reused as the accumulator slabs after it.  The
   // decoder's main loop needs no scratch: its slabs go into the input tile
-  // xt (dead once the main loop is done) when they fit, and its low-res src
-  // region (read only in the prologue) then shares the work region with the
-  // epilogue's stats scratch (int64 pairs, 1024 floats); the decoder stages
-  // the src's norm slots in xt before the input tile is committed.  (Slabs in
-  // xt: d2 50 -> 39 KB of LDS, four workgroups per CU instead of three.)
+  // xt (dead once the main loop is done) when they fit, and the work region
+  // is then the epilogue's stats scratch (int64 pairs, 1024 floats); the
+  // decoder stages the src's norm slots in xt before the input tile is
+  // committed.  (Slabs in xt: d2 50 -> 39 KB of LDS, four workgroups per CU
+  // instead of three.)  Decoder tiles with an odd side also keep their
+  // low-res src region (read only in the prologue) in the work region; even
+  // tiles upsample from registers (dec_quads) and have none: d3's 6x16 tile
+  // 44,736 -> 40,384 B (3 -> 4 workgroups per CU), d1's 4x8 55,360 -> 50,496 B
+  // (2 -> 3).
   const bool slab_in_xt = mode == 2 && L.CS * L.slab_stride <= xt_floats;
+  const bool dec_quads = mode == 2 && VSS_QUADS && TH % 2 == 0 && TW % 2 == 0;
   L.work = o;
   L.lr = o;
   const int hid_floats = L.HPL ? 4 * 4 * L.HPL : 4 * L.P_in_pad * hid_stride(stride);  // 4 waves
   o += cmax(cmax(cmax(mode == 0 ? hid_floats : 1024, slab_in_xt ? 0 : L.CS * L.slab_stride),
-                 mode == 2 ? r4(L.SR * L.SC * cin) : 0),
+                 mode == 2 && !dec_quads ? r4(L.SR * L.SC * cin) : 0),
             stem_in ? stem_in_lds(L.IH, L.IW) : 0);
   L.nrm = o; o += mode == 2 ? r4(2 * cin) : 0;
   // decoder: per input-tile pixel, its 2x-upsample taps (four lr offsets as
   // u16 pairs, ly1, lx1), built while the prologue loads are in flight — only
   // for tiles with an odd side; even tiles upsample by 2x2 quads (dec_quads)
-  L.uc = o;  o += (mode == 2 && (!VSS_QUADS || TH % 2 || TW % 2)) ? 4 * L.P_in_pad : 0;
+  L.uc = o;  o += (mode == 2 && !dec_quads) ? 4 * L.P_in_pad : 0;
   L.slab = slab_in_xt ? L.xt : L.work;
   L.stt = slab_in_xt ? L.work : L.xt;
   L.total = o;

@@ -739,7 +739,16 @@ __device__ __forceinline__ void block_body(const BlockParams& p, int bx, int by,
     if constexpr (NORM_IN) st_slots.issue([&](int i) { return g_slots.ld(4L * i); });
     static_assert(CL % 16 == 0 && CSKIP % 16 == 0, "16-channel staging items");
     constexpr int GL = CL / 16, GS = CSKIP / 16;  // 16-channel items per pixel
-    Staged16<SR * SC * GL, XP, VSS_STAGE16_DEC> st_lr;
+    // even tiles start at an odd row and column of the output (iy0 = TH*by - 1),
+    // so their input tile is whole 2x2 quads that share one 2x2 source window:
+    // the upsample runs per quad, from the window's four taps, which every
+    // (quad, channel quad) item loads straight into registers — no low-res
+    // region in LDS (L.lr), no per-pixel tap records (L.uc).  Tiles with an odd
+    // side stage the region in LDS and upsample per pixel from tap records.
+    constexpr bool QUADS = VSS_QUADS && TH % 2 == 0 && TW % 2 == 0;
+    constexpr int QH = L.IH / 2, QW = IW / 2, NQI = QH * QW * C4L, NQ = QUADS ? (NQI + 255) / 256 : 0;
+    Staged16<QUADS ? 0 : SR * SC * GL, XP, VSS_STAGE16_DEC> st_lr;
+    f4 tap[XP][NQ > 0 ? NQ : 1][4];  // [part][item][taa, tab, tba, tbb]
     Staged16<P_IN_PAD * GS, SP, VSS_STAGE16_DEC> st_sk;
     // The skip commit's 16-B stores go 8 lanes at a time (32 banks) over two
     // items; with one item per pixel and a pixel stride of 2 mod 4 quads (the
@@ -753,11 +762,33 @@ __device__ __forceinline__ void block_body(const BlockParams& p, int bx, int by,
       const float* xb[XP];
 #pragma unroll
       for (int q = 0; q < XP; ++q) xb[q] = xn + q * p.x_part_stride;
-      st_lr.issue(xb, [&](int i) {
-        const int pr = i / GL, gq = i - pr * GL;
-        const int yy = min(h - 1, sy0 + pr / SC), xx = min(w - 1, sx0 + pr % SC);
-        return (unsigned)((yy * w + xx) * CL + 16 * gq);
-      });
+      if constexpr (QUADS) {
+        // Quad (qy, qx) of the input tile covers output rows iy0 + 2 qy, + 1 and
+        // lies between source rows j0 + qy, j0 + qy + 1 (columns alike), clamped
+        // to the source: row / column -1 -> 0 and h -> h - 1, w -> w - 1, where
+        // both weights of the lerp hit the same value.
+        const int j0 = (iy0 - 1) / 2, i0 = (ix0 - 1) / 2;  // iy0, ix0 odd: exact (-1 -> -1)
+#pragma unroll
+        for (int k = 0; k < NQ; ++k) {
+          const int it = min(tid + 256 * k, NQI - 1);
+          const int c4 = it % C4L, qq = it / C4L, qx = qq % QW, qy = qq / QW;
+          const int ya = min(max(j0 + qy, 0), h - 1), yb = min(max(j0 + qy + 1, 0), h - 1);
+          const int ca = min(max(i0 + qx, 0), w - 1), cb = min(max(i0 + qx + 1, 0), w - 1);
+          const unsigned o[4] = {(unsigned)((ya * w + ca) * CL + 4 * c4), (unsigned)((ya * w + cb) * CL + 4 * c4),
+                                 (unsigned)((yb * w + ca) * CL + 4 * c4), (unsigned)((yb * w + cb) * CL + 4 * c4)};
+#pragma unroll
+          for (int q = 0; q < XP; ++q)
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+              tap[q][k][t] = *reinterpret_cast<const f4*>(reinterpret_cast<const char*>(xb[q]) + (o[t] << 2));
+        }
+      } else {
+        st_lr.issue(xb, [&](int i) {
+          const int pr = i / GL, gq = i - pr * GL;
+          const int yy = min(h - 1, sy0 + pr / SC), xx = min(w - 1, sx0 + pr % SC);
+          return (unsigned)((yy * w + xx) * CL + 16 * gq);
+        });
+      }
       const float* sb[SP];
 #pragma unroll
       for (int q = 0; q < SP; ++q) sb[q] = sn + q * p.skip_part_stride;
@@ -775,10 +806,6 @@ __device__ __forceinline__ void block_body(const BlockParams& p, int bx, int by,
     // integers — o = 0 -> (0, 0); odd o -> ((o - 1) / 2, 0.25); even o > 0 ->
     // (o / 2 - 1, 0.75), the same floats the float formula gives
     static_assert(SR * SC * CL < 65536, "tap offsets are u16");
-    // even tiles start at an odd row and column of the output (iy0 = TH*by - 1),
-    // so their input tile is whole 2x2 quads that share one 2x2 source window:
-    // the upsample below runs per quad and needs no per-pixel tap records
-    constexpr bool QUADS = VSS_QUADS && TH % 2 == 0 && TW % 2 == 0;
     unsigned* uc = reinterpret_cast<unsigned*>(smem + L.uc);
     if constexpr (!QUADS)
     for (int pix = tid; pix < P_IN_PAD; pix += 256) {
@@ -817,32 +844,6 @@ __device__ __forceinline__ void block_body(const BlockParams& p, int bx, int by,
       __syncthreads();
       VSS_STAMP(5);
     }
-    // the low-res src region; with norm_in, relu(src * scale + shift) applied
-    // once per element as it is committed
-    st_lr.commit_sum([&](int i, int k, f4 v) {
-      // item i = (region pixel, 16-channel group): its floats are contiguous in lr
-      if constexpr (NORM_IN) {
-        const int c4 = (i % GL) * 4 + k;
-        v = reluv(v * *reinterpret_cast<const f4*>(nrm + 4 * c4) + *reinterpret_cast<const f4*>(nrm + CL + 4 * c4));
-      }
-      reinterpret_cast<f4*>(lr)[4 * i + k] = v;
-    });
-    // the skip channels: zero outside the image (tiles at its edge only; the
-    // loads were clamped to real pixels, and padding pixels are never read)
-    const bool sk_interior = iy0 >= 0 && iy0 + L.IH <= Ho && ix0 >= 0 && ix0 + IW <= Wo;
-    st_sk.commit_sum([&](int i, int k, f4 v) {
-      const int pix = skip_pix(i / GS), gq = i - (i / GS) * GS;
-      if (!sk_interior) {
-        const int py = pix / IW, yy = iy0 + py, xx = ix0 + pix - py * IW;
-        const bool valid = ((unsigned)yy < (unsigned)Ho) & ((unsigned)xx < (unsigned)Wo);
-        v = valid ? v : f4{0.f, 0.f, 0.f, 0.f};
-      }
-      *reinterpret_cast<f4*>(xt + xq(pix, CL / 4 + 4 * gq + k)) = v;
-    });
-    st_w.commit([&](int i, f4 v) { wdst[i] = v; });
-    VSS_STAMP(4);
-    dma_wait<WDMA>();
-    __syncthreads();
     // upsampled channels: PyTorch upsample_bilinear2d(scale 2, align_corners=False)
     // of relu(src * scale + shift) (the src's instance norm, applied per tap)
     if constexpr (QUADS) {
@@ -852,14 +853,13 @@ __device__ __forceinline__ void block_body(const BlockParams& p, int bx, int by,
       // H1 = fma(0.25, R, 0.75 L) (column 2i+1) and H2 = fma(0.75, R, 0.25 L)
       // (column 2i+2), then each output = fma(ly1, H[j+1], ly0 H[j]) — exactly
       // the per-pixel form's operations (top / bot lerps, then the vertical
-      // one), shared by the quad: the same floats with 4 tap reads per 4
-      // pixels instead of 16.  At the image's edges the source index clamps
-      // (row / column -1 -> 0, h -> h - 1), where both weights hit the same
-      // value and the FMA returns it exactly — as the per-pixel form's
-      // weight-0 taps do.  Outputs outside the image are zero (halo).
-      constexpr int QH = L.IH / 2, QW = IW / 2, NQI = QH * QW * C4L, NQ = (NQI + 255) / 256;
-      const int j0 = (iy0 - 1) / 2, i0 = (ix0 - 1) / 2;  // iy0, ix0 odd: exact (-1 -> -1)
-      const int jr = j0 - sy0, ic = i0 - sx0;             // the quads' first source row / column in the region
+      // one), shared by the quad: the same floats with 4 taps per 4 pixels
+      // instead of 16.  At the image's edges the source index clamps (row /
+      // column -1 -> 0, h -> h - 1), where both weights hit the same value and
+      // the FMA returns it exactly — as the per-pixel form's weight-0 taps do.
+      // Outputs outside the image are zero (halo).  Each tap is the parts' sum
+      // in part order, then relu(v * scale + shift) — what the per-pixel form
+      // applies as it commits the region.
       const bool interior = iy0 >= 0 && iy0 + L.IH <= Ho && ix0 >= 0 && ix0 + IW <= Wo;
       const f4 c25 = {0.25f, 0.25f, 0.25f, 0.25f}, c75 = {0.75f, 0.75f, 0.75f, 0.75f};
 #pragma unroll
@@ -867,18 +867,17 @@ __device__ __forceinline__ void block_body(const BlockParams& p, int bx, int by,
         const int it = tid + 256 * k;
         if (NQI % 256 == 0 || it < NQI) {
           const int c4 = it % C4L, qq = it / C4L, qx = qq % QW, qy = qq / QW;
-          // the source window's rows / columns, clamped to the region: the
-          // region's rows (columns) past the source's last one were loaded
-          // clamped, i.e. they hold that last row (column), and a row above
-          // (left of) the source only occurs where the region starts at 0
-          const int ra = min(max(qy + jr, 0), SR - 1), rb = min(max(qy + jr + 1, 0), SR - 1);
-          const int ca = min(max(qx + ic, 0), SC - 1), cb = min(max(qx + ic + 1, 0), SC - 1);
-          const float* la = lr + ra * (SC * CL) + 4 * c4;
-          const float* lb = lr + rb * (SC * CL) + 4 * c4;
-          const f4 taa = *reinterpret_cast<const f4*>(la + ca * CL);
-          const f4 tab = *reinterpret_cast<const f4*>(la + cb * CL);
-          const f4 tba = *reinterpret_cast<const f4*>(lb + ca * CL);
-          const f4 tbb = *reinterpret_cast<const f4*>(lb + cb * CL);
+          f4 t[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            f4 v = tap[0][k][u];
+#pragma unroll
+            for (int q = 1; q < XP; ++q) v = v + tap[q][k][u];
+            if constexpr (NORM_IN)
+              v = reluv(v * *reinterpret_cast<const f4*>(nrm + 4 * c4) + *reinterpret_cast<const f4*>(nrm + CL + 4 * c4));
+            t[u] = v;
+          }
+          const f4 taa = t[0], tab = t[1], tba = t[2], tbb = t[3];
           const f4 h1a = __builtin_elementwise_fma(c25, tab, c75 * taa), h2a = __builtin_elementwise_fma(c75, tab, c25 * taa);
           const f4 h1b = __builtin_elementwise_fma(c25, tbb, c75 * tba), h2b = __builtin_elementwise_fma(c75, tbb, c25 * tba);
           f4 o00 = __builtin_elementwise_fma(c25, h1b, c75 * h1a), o01 = __builtin_elementwise_fma(c25, h2b, c75 * h2a);
@@ -902,6 +901,35 @@ __device__ __forceinline__ void block_body(const BlockParams& p, int bx, int by,
         }
       }
     } else {
+      // odd tiles: the low-res src region to LDS; with norm_in, relu(src *
+      // scale + shift) applied once per element as it is committed
+      st_lr.commit_sum([&](int i, int k, f4 v) {
+        // item i = (region pixel, 16-channel group): its floats are contiguous in lr
+        if constexpr (NORM_IN) {
+          const int c4 = (i % GL) * 4 + k;
+          v = reluv(v * *reinterpret_cast<const f4*>(nrm + 4 * c4) + *reinterpret_cast<const f4*>(nrm + CL + 4 * c4));
+        }
+        reinterpret_cast<f4*>(lr)[4 * i + k] = v;
+      });
+    }
+    // the skip channels: zero outside the image (tiles at its edge only; the
+    // loads were clamped to real pixels, and padding pixels are never read)
+    const bool sk_interior = iy0 >= 0 && iy0 + L.IH <= Ho && ix0 >= 0 && ix0 + IW <= Wo;
+    st_sk.commit_sum([&](int i, int k, f4 v) {
+      const int pix = skip_pix(i / GS), gq = i - (i / GS) * GS;
+      if (!sk_interior) {
+        const int py = pix / IW, yy = iy0 + py, xx = ix0 + pix - py * IW;
+        const bool valid = ((unsigned)yy < (unsigned)Ho) & ((unsigned)xx < (unsigned)Wo);
+        v = valid ? v : f4{0.f, 0.f, 0.f, 0.f};
+      }
+      *reinterpret_cast<f4*>(xt + xq(pix, CL / 4 + 4 * gq + k)) = v;
+    });
+    st_w.commit([&](int i, f4 v) { wdst[i] = v; });
+    VSS_STAMP(4);
+    if constexpr (!QUADS) {
+    // odd tiles: the upsample per pixel, from the region in LDS by tap records
+    dma_wait<WDMA>();
+    __syncthreads();
     // Every read of this thread's items is issued before any of its writes:
     // with a read -> write chain per item (the compiler cannot move an item's
     // LDS reads above the previous item's write into the same array) the
