@@ -470,6 +470,116 @@ def conv_up():
                    [(a, [2, 24, 18, 34]), (c, [2, 16, 22, 26]), (d, [2, 70, 22, 26])])
 
 
+def conv_tile_matrix():
+    """The plain k_conv_tile forms (vso_conv.hip) at sizes the planner's knobs
+    can steer onto every tile (tests/test_gpu_conv_tile_matrix.py).  Every
+    convolution reads a graph input (or a Concat of two), so 16-bit operand
+    rounding is the oracle's exactly; batch 2 (work items cross the batch
+    index), odd planes (the last tile row and column are partial), each
+    convolution above the f32 sessions' 8e6 MACs.
+      wide   x [2, 72, 37, 70]: five 8-row tile rows (the last of 5 rows),
+             three 32-pixel columns (the last of 6 pixels); 72 channels = 3
+             chunks, the last of 8 real channels.  3x3 to 16 / 24 (Relu) / 70
+             (Clip; two 64-channel tiles, the last partial), 5x5 to 16 / 32
+             (Sigmoid) / 70, 3x3 stride 2 to 24 (19x35), and a 3x3 to 24 over
+             Concat(a: 32, b: 13 channels) — the Concat's last input read in
+             place by the convolution (ConvTileParams.x2)
+      narrow xn [2, 72, 21, 27] (Wo < 32: 16-pixel tile columns): 3x3 to 16
+             and to 70 + residual Add (a graph input), 5x5 to 24, 3x3 stride 2
+             to 48 (11x14)
+      deep   xd [1, 520, 6, 40]: 17 chunks, the last partial; 5x5 to 48 — the
+             16-bit deep tile (4x32 with a K split)
+      x2     [2, 200, 9, 16] as in conv_tiles: 5x5 + 3x3 to 48, Add, Relu in
+             the split reduction's epilogue
+      and, for the channel tiles those leave out: narrow 3x3 to 24 and 5x5 to
+      16, wide stride 2 to 16 and 70, and xs [2, 72, 27, 61] stride 2 to 16
+      and 24 (14x31: the narrow stride-2 tile)."""
+    b = Builder(31)
+    clip = lambda t, v: b.op("Clip", [t, b.const(np.array(-v, np.float32)), b.const(np.array(v, np.float32))])
+    outs = []
+    for k, ms, tag in ((3, (16, 24, 70), "w3"), (5, (16, 32, 70), "w5")):
+        for m in ms:
+            y = b.conv("x", 72, m, k)
+            if (k, m) == (3, 24):
+                y = b.op("Relu", [y])
+            elif (k, m) == (3, 70):
+                y = clip(y, 2.5)
+            elif (k, m) == (5, 32):
+                y = b.op("Sigmoid", [y])
+            outs.append((y, [2, m, 37, 70]))
+    outs.append((b.conv("x", 72, 24, 3, stride=2), [2, 24, 19, 35]))
+    cat = b.op("Concat", ["a", "b"], axis=1)                                # [2, 45, 37, 70]
+    outs.append((b.op("Relu", [b.conv(cat, 45, 24, 3)]), [2, 24, 37, 70]))
+    outs.append((b.conv("xn", 72, 16, 3), [2, 16, 21, 27]))
+    outs.append((b.op("Add", [b.conv("xn", 72, 70, 3), "rn"]), [2, 70, 21, 27]))
+    outs.append((clip(b.conv("xn", 72, 24, 5), 3.0), [2, 24, 21, 27]))
+    outs.append((b.conv("xn", 72, 48, 3, stride=2), [2, 48, 11, 14]))
+    outs.append((b.conv("xd", 520, 48, 5), [1, 48, 6, 40]))
+    k1 = b.conv("x2", 200, 48, 5)
+    k2 = b.conv("x2", 200, 48, 3)
+    outs.append((b.op("Relu", [b.op("Add", [k1, k2])]), [2, 48, 9, 16]))
+    # the channel tiles the cases above leave out
+    outs.append((b.conv("xn", 72, 24, 3), [2, 24, 21, 27]))
+    outs.append((b.conv("xn", 72, 16, 5), [2, 16, 21, 27]))
+    outs.append((b.conv("x", 72, 16, 3, stride=2), [2, 16, 19, 35]))
+    outs.append((b.op("Relu", [b.conv("x", 72, 70, 3, stride=2)]), [2, 70, 19, 35]))
+    outs.append((b.conv("xs", 72, 16, 3, stride=2), [2, 16, 14, 31]))
+    outs.append((b.conv("xs", 72, 24, 3, stride=2), [2, 24, 14, 31]))
+    return b.model([(n, list(s)) for n, s in CONV_TILE_MATRIX_FEEDS.items()], outs)
+
+
+# (xs: 27x61, stride 2 to 14x31 — 16-pixel tile columns with enough pixels
+# for 16- and 32-channel stride-2 tiles above the f32 MAC threshold)
+CONV_TILE_MATRIX_FEEDS = {"x": (2, 72, 37, 70), "a": (2, 32, 37, 70), "b": (2, 13, 37, 70), "xn": (2, 72, 21, 27),
+                          "rn": (2, 70, 21, 27), "xd": (1, 520, 6, 40), "x2": (2, 200, 9, 16), "xs": (2, 72, 27, 61)}
+# (output index -> a short case name, in conv_tile_matrix's output order)
+CONV_TILE_MATRIX_CASES = ("w3_16", "w3_24", "w3_70", "w5_16", "w5_32", "w5_70", "ws2_24", "wcat_24", "n3_16", "n3_70",
+                          "n5_24", "ns2_48", "d5_48", "k_48", "n3_24", "n5_16", "ws2_16", "ws2_70", "xs2_16", "xs2_24")
+
+
+def conv_up_matrix():
+    """The fused-upsample forms (k_conv_tile_up; 16-bit sessions): conv_up's
+    two (a wide 3x3 through a Concat with a skip input, a narrow 5x5 by sizes)
+    plus a wide 5x5 to 32 channels (13x21 -> 26x42), a narrow 3x3 to 16
+    (11x13 -> 22x26) and a wide 3x3 to 48 channels, fused only on the
+    64-channel upsample tile (VSO_UP_BM64=1; else its Resize keeps a launch);
+    then the remaining channel tiles: wide 3x3 and 5x5 to 16, narrow 3x3 to 24
+    and to 48 (the narrow 64-channel tiles) and narrow 5x5 to 24.
+    Upsampled ranges of 32 / 64 channels, odd low-resolution sizes (the edge
+    clamps fall inside tiles), batch 2."""
+    b = Builder(32)
+    x2 = lambda t: b.op("Resize", [t, "", b.const(np.array([1, 1, 2, 2], np.float32))], mode="linear",
+                        coordinate_transformation_mode="half_pixel")
+    cat = b.op("Concat", [x2("lo"), "skip"], axis=1)                        # [2, 69, 18, 34]
+    ua = b.op("Relu", [b.conv(cat, 69, 24, 3)])
+    up2 = b.op("Resize", ["lo2", "", "", b.const(np.array([2, 32, 22, 26], np.int64))], mode="linear",
+               coordinate_transformation_mode="pytorch_half_pixel")
+    uc = b.conv(up2, 32, 16, 5)
+    uw = b.conv(x2("lo3"), 32, 32, 5)
+    un = b.op("Relu", [b.conv(x2("lo2"), 32, 16, 3)])
+    u48 = b.conv(x2("lo"), 64, 48, 3)
+    # the channel tiles the cases above leave out (each Resize feeds one convolution: fused)
+    uw3 = b.conv(x2("lo3"), 32, 16, 3)
+    un24 = b.conv(x2("lo2"), 32, 24, 3)
+    un48 = b.conv(x2("lo2"), 32, 48, 3)
+    uw16 = b.conv(x2("lo3"), 32, 16, 5)
+    un5 = b.op("Relu", [b.conv(x2("lo2"), 32, 24, 5)])
+    return b.model([(n, list(s)) for n, s in CONV_UP_MATRIX_FEEDS.items()],
+                   [(ua, [2, 24, 18, 34]), (uc, [2, 16, 22, 26]), (uw, [2, 32, 26, 42]), (un, [2, 16, 22, 26]),
+                    (u48, [2, 48, 18, 34]), (uw3, [2, 16, 26, 42]), (un24, [2, 24, 22, 26]), (un48, [2, 48, 22, 26]),
+                    (uw16, [2, 16, 26, 42]), (un5, [2, 24, 22, 26])])
+
+
+CONV_UP_MATRIX_FEEDS = {"lo": (2, 64, 9, 17), "skip": (2, 5, 18, 34), "lo2": (2, 32, 11, 13), "lo3": (2, 32, 13, 21)}
+CONV_UP_MATRIX_CASES = ("ua_24", "uc_16", "uw5_32", "un3_16", "u48", "uw3_16", "un3_24", "un3_48", "uw5_16", "un5_24")
+
+
+def matrix_feeds(shapes, seed):
+    """Standard-normal feeds for conv_tile_matrix / conv_up_matrix."""
+    rng = np.random.default_rng(seed)
+    return {k: rng.standard_normal(s).astype(np.float32) for k, s in shapes.items()}
+
+
 def ir_chain():
     """MobileNetV2 inverted residuals (1x1 expand -> Clip -> 3x3 depthwise ->
     Clip -> 1x1 project [+ input]) of every k_ir form (vso_ir.hip): stride 1

@@ -38,6 +38,90 @@ def test_conv_matches_torch(k, s, pads, g, d):
     assert np.abs(got - want).max() <= 1e-5 * max(1.0, np.abs(want).max())
 
 
+@pytest.mark.parametrize("model", ["conv_tile_matrix", "conv_up_matrix"])
+def test_tile_matrix_models_evaluate(model):
+    """The k_conv_tile matrix models (tests/test_gpu_conv_tile_matrix.py) load
+    and evaluate in the oracle, and every Conv of theirs — 520 channels at
+    5x5, the 45-channel Concat input, stride 2 on the odd 37x70 and 21x27
+    planes, the upsampled inputs — equals torch.nn.functional.conv2d in
+    float64 on the same input, within one float32 rounding of the result
+    (both sum in float64, in different orders, and round once)."""
+    torch = _torch()
+    F = torch.nn.functional
+    shapes = {"conv_tile_matrix": M.CONV_TILE_MATRIX_FEEDS, "conv_up_matrix": M.CONV_UP_MATRIX_FEEDS}[model]
+    m = R.load(getattr(M, model)())
+    feeds = M.matrix_feeds(shapes, 7)
+    out = R.run(m, feeds)
+    assert len(out) == len(m.outputs)
+    for (name, _, dims), v in zip(m.outputs, out.values()):
+        assert v.dtype == np.float32 and list(v.shape) == list(dims) and np.isfinite(v).all(), name
+        assert np.abs(v).max() > 0, name
+    half = R.run(m, feeds, conv_operands="bf16")  # the 16-bit sessions' oracle: rounds, so differs
+    assert all(np.isfinite(v).all() for v in half.values())
+    assert any(not np.array_equal(half[k], out[k]) for k in out)
+    convs = [nd for nd in m.nodes if nd["op"] == "Conv"]
+    assert len(convs) == (21 if model == "conv_tile_matrix" else 10)
+    vals = R.run(m, feeds, want=[nd["inputs"][0] for nd in convs] + [nd["outputs"][0] for nd in convs])
+    seen = set()
+    for nd in convs:
+        x, w, b = vals[nd["inputs"][0]], m.inits[nd["inputs"][1]], m.inits[nd["inputs"][2]]
+        a = nd["attrs"]
+        seen.add((x.shape[1], w.shape[2], a["strides"][0]))
+        pt, pl, pb, pr = a["pads"]
+        xt = F.pad(torch.from_numpy(x).double(), (pl, pr, pt, pb))
+        want = F.conv2d(xt, torch.from_numpy(w).double(), torch.from_numpy(b).double(),
+                        stride=a["strides"][0]).float().numpy()
+        got = vals[nd["outputs"][0]]
+        assert got.shape == want.shape
+        assert (np.abs(got.astype(np.float64) - want) <= 2.0 ** -23 * np.maximum(1.0, np.abs(want))).all(), nd["outputs"]
+    if model == "conv_tile_matrix":
+        assert {(520, 5, 1), (45, 3, 1), (72, 3, 2), (200, 5, 1)} <= seen
+
+
+def test_round_operand_matches_torch():
+    """onnx_ref.round_operand (the 16-bit sessions' operand rounding in the
+    oracle) is bitwise torch's float32 -> bfloat16 / float16 -> float32:
+    random values over the exponent range, exact ties of both parities, values
+    that round up into the next binade, subnormals of the 16-bit type and of
+    float32, +-0, the largest finite values (float32's rounds to inf in both
+    types), +-inf.  NaN is not compared: float16 keeps it a NaN (numpy's
+    cast); the bfloat16 integer rounding keeps a NaN whose low 16 bits do not
+    carry out of the mantissa (the default quiet NaN among them) and turns one
+    that does — mantissa bits all set — into a zero.  No convolution operand
+    of the tests is a NaN."""
+    torch = _torch()
+    rng = np.random.default_rng(3)
+    rnd = (rng.standard_normal(4096) * 10.0 ** rng.integers(-42, 38, 4096)).astype(np.float32)
+    f32 = lambda bits: np.array(bits, np.uint32).view(np.float32)
+    # bf16 keeps the top 16 bits: ties are low halves of exactly 0x8000
+    bf_ties = f32([0x3F808000, 0x3F818000, 0xBF808000, 0xBF818000, 0x3F807FFF, 0x3F808001, 0x3F818001,
+                   0x3FFF8000, 0x3FFFFFFF, 0x407F8000,          # up into the next binade
+                   0x00008000, 0x00018000, 0x00000001, 0x007F8000, 0x007FFFFF, 0x80008000,  # float32 subnormals
+                   0x7F7F0000, 0x7F7F7FFF, 0x7F7F8000, 0x7F7FFFFF, 0xFF7FFFFF])
+    # f16 has 10 mantissa bits: ties at 2^-11 steps of [1, 2); subnormals below 2^-14, spaced 2^-24
+    h_ties = np.array([1 + 2.0 ** -11, 1 + 3 * 2.0 ** -11, -(1 + 2.0 ** -11), -(1 + 3 * 2.0 ** -11),
+                       1 + 2.0 ** -11 + 2.0 ** -23, 2 - 2.0 ** -11, 2 - 2.0 ** -12, 4 - 2.0 ** -10,
+                       2.0 ** -24, 2.0 ** -25, 3 * 2.0 ** -25, 2.0 ** -25 + 2.0 ** -40, 5 * 2.0 ** -25, 2.0 ** -14,
+                       2.0 ** -14 - 2.0 ** -25, 2.0 ** -14 - 2.0 ** -26, 6.1e-5, 1e-8, -2.0 ** -25,
+                       65504.0, 65519.0, 65519.996, 65520.0, -65520.0, 70000.0], np.float32)
+    edge = np.array([0.0, -0.0, np.inf, -np.inf, np.finfo(np.float32).max, np.finfo(np.float32).tiny], np.float32)
+    v = np.concatenate([rnd, bf_ties, h_ties, edge])
+    assert np.isfinite(rnd).all() and not np.isnan(v).any()
+    for mode, dt in (("bf16", torch.bfloat16), ("f16", torch.float16)):
+        got = R.round_operand(v, mode)
+        want = torch.from_numpy(v).to(dt).float().numpy()
+        assert got.dtype == np.float32
+        bad = np.nonzero(got.view(np.uint32) != want.view(np.uint32))[0]
+        assert bad.size == 0, (mode, v[bad][:8], got[bad][:8], want[bad][:8])
+        # and rounding did something: ties went to even, the largest float32 overflowed
+        assert np.isinf(got[np.abs(v) == np.finfo(np.float32).max]).all()
+    assert R.round_operand(f32([0x3F808000, 0x3F818000]), "bf16").view(np.uint32).tolist() == [0x3F800000, 0x3F820000]
+    assert R.round_operand(np.array([1 + 2.0 ** -11, 1 + 3 * 2.0 ** -11], np.float32), "f16").tolist() == \
+        [1.0, 1 + 2.0 ** -9]
+    assert np.isnan(R.round_operand(np.array([np.nan], np.float32), "bf16")).all()  # (the default quiet NaN stays one)
+    assert np.isnan(R.round_operand(np.array([np.nan], np.float32), "f16")).all()
+
+
 def test_pool_resize_norm_match_torch():
     torch = _torch()
     F = torch.nn.functional

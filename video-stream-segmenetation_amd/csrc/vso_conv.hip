@@ -1061,11 +1061,18 @@ void launch_conv_tile_prec(const ConvTileParams& p, const ConvTileShape& t, hipS
 // forms (conv_tile_persist; VSO_CONV_PERSIST=0: off) as many as are resident
 // at once — the kernel's occupancy per CU x the CUs, rounded down to a
 // multiple of 8 (XCDs) — each running its items software-pipelined
+// (VSO_CONV_GRID=<n>, n > 0: at most n workgroups — a test knob that puts many
+// items on each workgroup at small shapes; no workgroup waits for another,
+// the K split's hand-off is one fetch_add, so any n >= 1 completes)
 template <class K>
 static void launch_items(K kern, const ConvTileParams& p, long items, hipStream_t s) {
   static const bool persist = conv_tile_persist(VSO_CONV_PREC) && [] {
     const char* e = std::getenv("VSO_CONV_PERSIST");
     return !e || std::atoi(e) != 0;
+  }();
+  static const long grid_cap = [] {
+    const char* e = std::getenv("VSO_CONV_GRID");
+    return e ? std::atol(e) : 0L;
   }();
   ConvTileParams q = p;
   q.items = (int)items;
@@ -1078,6 +1085,7 @@ static void launch_items(K kern, const ConvTileParams& p, long items, hipStream_
       const long resident = (long)per_cu * cus / 8 * 8;
       if (resident > 0) grid = std::min(grid, resident);
     }
+    if (grid_cap > 0) grid = std::min(grid, grid_cap);
   }
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), 0, s, q);
 }
