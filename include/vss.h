@@ -607,5 +607,6 @@ int vss_segment_background(vss_handle* h, vss_post_state* st, vss_background* bg
 #include "vss_matte.h"
 #include "vss_video.h"
 #include "vss_pool.h"
+#include "vss_layers.h"
 
 #endif /* VSS_H_ */

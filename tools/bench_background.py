@@ -28,6 +28,16 @@ vss_background_composite_device as before NV12 existed (rgba_path).
 nv12_overhead_us is video_process - rgba_path: both conversions and the RGBA
 round trip through the scratch.
 
+--layers (opt-in) adds, in the same interleaved rounds, the three modes under
+the branding layers of the reference's `corporate__rect` template
+(tests/golden/branding_templates.json) at privacy level 3, every text line and
+image a stub sprite (colour_layers, image_layers, blur_layers): colour and image
+run k_bg_composite<IMAGE> over the baked plate, so they are compared with
+`image`; blur reads the overlay plate, 4 more bytes per pixel, and is compared
+with `blur`.  plate_build_us is the one-off cost, for information: the median
+of vss_background_overlay_device right after a privacy change (the whole plate
+rebuilt, plus one device copy of it).
+
 Needs a GPU: there is no fall-back.
 """
 import argparse
@@ -69,6 +79,27 @@ def refined_extra_bytes(n, fh, fw, fc, H, W):
     """What refinement adds: the guide pass reads the frame once more; per mask pixel L out and in,
     p in, (a_q, b_q) out and in, (abar, bbar) out and in, in place of nothing (the alpha bytes stay)."""
     return n * fh * fw * fc + n * H * W * (1 + 1 + 1 + 8 + 8 + 8 + 8)
+
+
+def template_stub_layers(pkg):
+    """The corporate__rect template with stub sprites: a translucent block per text line, opaque icons."""
+    with open(os.path.join(ROOT, "tests", "golden", "branding_templates.json"), encoding="utf-8") as f:
+        template = json.load(f)["templates"]["corporate__rect"]
+    fields = {"full_name": "Name Surname", "position": "Senior engineer", "department": "Department",
+              "company": "Company", "office_location": "City, street 1", "email": "name@example.com",
+              "telegram": "@name", "slogan": "A slogan of some length"}
+    rng = np.random.default_rng(7)
+
+    def rasterize(text, font, color):
+        size = int(font.replace("bold ", "").split("px")[0])
+        px = np.zeros((size, max(1, size * len(text) // 2), 4), np.uint8)
+        px[..., :3] = color[:3]
+        px[..., 3] = rng.integers(0, 256, px.shape[:2], dtype=np.uint8)
+        return px, int(size * 0.8)
+
+    images = {k: rng.integers(0, 256, (128, 128, 4), dtype=np.uint8)
+              for k in ("email_icon", "telegram_icon", "qr_code", "company_logo")}
+    return pkg.template_layers(template, fields, images, rasterize)
 
 
 def nv12_leg(pkg, torch, s, a, n, H, W):
@@ -164,6 +195,7 @@ def main():
     ap.add_argument("--calls", type=int, default=8, help="timed calls per mode and round")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--refine", default=None, metavar="R,EPS", help="also time the edge-aware matte (opt-in)")
+    ap.add_argument("--layers", action="store_true", help="also time the modes under branding layers (opt-in)")
     ap.add_argument("--nv12", action="store_true", help="also time the NV12 video I/O at 8 x 1080p (opt-in)")
     a = ap.parse_args()
     if a.rounds * a.calls < 20:
@@ -206,6 +238,15 @@ def main():
                 for m in ("colour_refined", "image_refined", "blur_refined", "alpha_refined"):
                     bgs[m].set_refine(*refine)
                 dal = torch.empty((n, fh, fw), dtype=torch.uint8, device="cuda")
+            if a.layers:
+                for m in ("colour", "image", "blur"):
+                    bgs[m + "_layers"] = pkg.Background(s)
+                bgs["image_layers"].set_image(rng.integers(0, 256, (720, 1280, 3), dtype=np.uint8))
+                bgs["blur_layers"].set_blur(a.radius, a.sigma)
+                stub = template_stub_layers(pkg)
+                for m in ("colour_layers", "image_layers", "blur_layers"):
+                    bgs[m].set_layers(stub)
+                    bgs[m].set_privacy("high")
 
             def call(mode):
                 if mode == "composite":
@@ -220,6 +261,8 @@ def main():
             modes = ("composite", "colour", "image", "blur")
             if refine:  # the default modes stay first and warm up last-but-these, so `check` below is still blur's
                 modes = ("colour_refined", "image_refined", "blur_refined", "alpha_plain", "alpha_refined") + modes
+            if a.layers:
+                modes = ("colour_layers", "image_layers", "blur_layers") + modes
             for m in modes:
                 for _ in range(a.warmup):
                     call(m)
@@ -249,7 +292,10 @@ def main():
                 if m.startswith("alpha_"):
                     by = n * fh * fw + n * H * W + (n * fh * fw * fc if m == "alpha_refined" else 0)
                 else:
-                    by = algorithmic_bytes(m.replace("_refined", ""), n, fh, fw, fc, H, W)
+                    by = algorithmic_bytes({"colour_layers": "image"}.get(m, m.replace("_refined", "").replace(
+                        "_layers", "")), n, fh, fw, fc, H, W)
+                if m == "blur_layers":
+                    by += n * fh * fw * 4  # the overlay plate, read per frame (L2 may serve the batch's repeats)
                 if m.endswith("_refined"):
                     by += refined_extra_bytes(n, fh, fw, fc, H, W)
                 rounds = [statistics.median(rr) for rr in times[m]]
@@ -265,6 +311,28 @@ def main():
                     rm["ratio_to_unrefined"] = round(rm["median_us"] / out[m]["median_us"], 3)
                     rm["bytes_ratio_to_unrefined"] = round(rm["bytes"] / out[m]["bytes"], 3)
                     rm["spread"] = round(max(rm["round_medians_us"]) / min(rm["round_medians_us"]) - 1, 4)
+            if a.layers:
+                for m, ref_mode in (("colour_layers", "image"), ("image_layers", "image"), ("blur_layers", "blur")):
+                    lm = out[m]
+                    lm["ratio_to_" + ref_mode] = round(lm["median_us"] / out[ref_mode]["median_us"], 3)
+                    lm["bytes_ratio_to_" + ref_mode] = round(lm["bytes"] / out[ref_mode]["bytes"], 3)
+                    lm["spread"] = round(max(lm["round_medians_us"]) / min(lm["round_medians_us"]) - 1, 4)
+                for m in ("image", "blur"):
+                    out[m]["spread"] = round(max(out[m]["round_medians_us"]) / min(out[m]["round_medians_us"]) - 1, 4)
+                plate = torch.empty((fh, fw, 4), dtype=torch.uint8, device="cuda")
+                builds = []
+                for k in range(7):
+                    bgs["blur_layers"].set_privacy(1 + k % 2)
+                    bgs["blur_layers"].set_privacy(3)  # the level changed: the next call rebuilds the plate
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(st)
+                    pkg._check(pkg.lib().vss_background_overlay_device(s._h, bgs["blur_layers"]._bg, fh, fw,
+                                                                       plate.data_ptr(), fw * 4, stream), s._h)
+                    e1.record(st)
+                    torch.cuda.synchronize()
+                    builds.append(e0.elapsed_time(e1) * 1e3)
+                out["plate_build_us"] = round(statistics.median(builds[2:]), 2)
+                out["layers"] = len(stub)
             if refine:
                 out["matte_stage_us"] = round(out["alpha_refined"]["median_us"] - out["alpha_plain"]["median_us"], 2)
             result["sizes"][f"{fw}x{fh}"] = out

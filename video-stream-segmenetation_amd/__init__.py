@@ -88,6 +88,16 @@ class PostConfig(ctypes.Structure):
         return c
 
 
+class _Layer(ctypes.Structure):
+    """vss_layer (include/vss_layers.h)."""
+    _fields_ = [("type", ctypes.c_int), ("privacy", ctypes.c_int), ("x", ctypes.c_int), ("y", ctypes.c_int),
+                ("width", ctypes.c_int), ("height", ctypes.c_int), ("radius", ctypes.c_int),
+                ("color", ctypes.c_uint8 * 4), ("pixels", ctypes.c_void_p), ("src_h", ctypes.c_int),
+                ("src_w", ctypes.c_int), ("row_stride", ctypes.c_size_t), ("has_shadow", ctypes.c_int),
+                ("shadow_color", ctypes.c_uint8 * 4), ("shadow_blur", ctypes.c_int), ("shadow_dx", ctypes.c_int),
+                ("shadow_dy", ctypes.c_int)]
+
+
 CALLBACK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int)
 _lib = None
 _lock = threading.Lock()
@@ -184,6 +194,10 @@ def lib() -> ctypes.CDLL:
                 "vss_background_set_refine": ([P, I, ctypes.c_double], I),
                 "vss_background_alpha_device": ([P, P, P, I, I, I, I, S, S, P, P, S, S, P], I),
                 "vss_background_alpha_device_at": ([P, P, P, I, I, I, I, S, S, P, I, I, P, S, S, P], I),
+                "vss_layers_map": ([I, I, I], I),
+                "vss_background_set_layers": ([P, ctypes.POINTER(_Layer), I, I, I], I),
+                "vss_background_set_privacy": ([P, I], I),
+                "vss_background_overlay_device": ([P, P, I, I, P, S, P], I),
                 "vss_blur_weights": ([I, ctypes.c_double, P], I),
                 "vss_background_composite_device": ([P, P, P, I, I, I, I, S, S, P, P, S, S, P], I),
                 "vss_segment_background": ([P, P, P, P, I, I, I, I, S, P], I),
@@ -257,6 +271,7 @@ class Session:
         self.device_bytes = info.device_bytes
         self.n_gpus, self.queue_depth, self.rccl = info.n_gpus, info.queue_depth, bool(info.rccl)
         self.dtype, self.max_batch = dtype, max_batch
+        self.device_id = int(device_ids[0]) if device_ids else int(device_id)
         self._pending = []
         self._tickets = {}
         self._posts = []
@@ -764,6 +779,137 @@ class Background:
         the frame's luma, radius 1..8 mask pixels, eps in [1, 65025]; radius 0 = off
         (the default).  Independent of the mode; from the next composite."""
         _check(lib().vss_background_set_refine(self._bg, int(radius), float(eps)), self.session._h)
+
+    def set_layers(self, layers, canvas=(1920, 1080)):
+        """Branding layers (include/vss_layers.h): a list of Layer drawn in order between
+        the background and the person, on a design canvas (width, height).  Replaces
+        the previous layers; an empty list removes them.  Sprites are copied to the
+        GPU before the call returns."""
+        layers = list(layers)
+        arr = (_Layer * max(len(layers), 1))()
+        keep = []  # the sprites' arrays, alive until the call returns
+        for c, l in zip(arr, layers):
+            c.type = LAYER_TYPES[l.type] if isinstance(l.type, str) else int(l.type)
+            c.privacy = PRIVACY_LEVELS[l.privacy] if isinstance(l.privacy, str) else int(l.privacy)
+            c.x, c.y, c.width, c.height, c.radius = int(l.x), int(l.y), int(l.width), int(l.height), int(l.radius)
+            c.color = (ctypes.c_uint8 * 4)(*[int(v) for v in l.color])
+            if l.pixels is not None:
+                a = np.asarray(l.pixels)
+                if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 4:
+                    raise VssError(VSS_E_INVALID_ARG, "a layer's pixels must be uint8 [h,w,4]")
+                if a.size and (a.strides[2] != 1 or a.strides[1] != 4 or a.strides[0] < a.shape[1] * 4):
+                    a = np.ascontiguousarray(a)
+                keep.append(a)
+                c.pixels = a.ctypes.data if a.size else None
+                c.src_h, c.src_w = a.shape[0], a.shape[1]
+                c.row_stride = a.strides[0] if a.size else 0
+            if l.shadow is not None:
+                c.has_shadow = 1
+                c.shadow_color = (ctypes.c_uint8 * 4)(*[int(v) for v in l.shadow["color"]])
+                c.shadow_blur = int(l.shadow["blur"])
+                c.shadow_dx, c.shadow_dy = int(l.shadow["dx"]), int(l.shadow["dy"])
+        _check(lib().vss_background_set_layers(self._bg, arr if layers else None, len(layers), int(canvas[0]),
+                                               int(canvas[1])), self.session._h)
+
+    def set_privacy(self, level):
+        """'low' / 'medium' / 'high' or 1..3: layers with privacy <= level are drawn
+        ('medium' until set, customization.ts:28)."""
+        lv = PRIVACY_LEVELS[level] if isinstance(level, str) else int(level)
+        _check(lib().vss_background_set_privacy(self._bg, lv), self.session._h)
+
+    def overlay(self, fh: int, fw: int) -> np.ndarray:
+        """The overlay plate O for a frame fh x fw: premultiplied RGBA uint8 [fh,fw,4]."""
+        import torch
+        out = torch.empty((int(fh), int(fw), 4), dtype=torch.uint8, device=f"cuda:{self.session.device_id}")
+        _check(lib().vss_background_overlay_device(self.session._h, self._bg, int(fh), int(fw), out.data_ptr(),
+                                                   int(fw) * 4, None), self.session._h)
+        self.session.synchronize()
+        return out.cpu().numpy()
+
+
+VSS_LAYER_IMAGE, VSS_LAYER_ROUNDED_RECT, VSS_MAX_LAYERS = 0, 1, 32
+LAYER_TYPES = {"image": VSS_LAYER_IMAGE, "rect": VSS_LAYER_ROUNDED_RECT}
+PRIVACY_LEVELS = {"low": 1, "medium": 2, "high": 3}  # customization.ts:38
+
+
+class Layer:
+    """One branding layer (vss_layer): type 'image' (pixels: RGBA uint8 [h,w,4], not
+    premultiplied) or 'rect' (color r, g, b, a and a corner radius); privacy 1..3 or
+    'low' / 'medium' / 'high'; x, y, width, height in canvas units; shadow: None or
+    {"color": (r, g, b, a), "blur": int, "dx": int, "dy": int}."""
+
+    def __init__(self, type, privacy, x, y, width, height, radius=0, color=(0, 0, 0, 0), pixels=None, shadow=None):
+        self.type, self.privacy = type, privacy
+        self.x, self.y, self.width, self.height, self.radius = x, y, width, height, radius
+        self.color, self.pixels, self.shadow = tuple(color), pixels, shadow
+
+    def __repr__(self):
+        return (f"Layer({self.type!r}, privacy={self.privacy}, x={self.x}, y={self.y}, width={self.width}, "
+                f"height={self.height}, shadow={self.shadow is not None})")
+
+
+def layers_map(v: int, canvas: int, frame: int) -> int:
+    """Canvas coordinate -> frame pixel (vss_layers_map).  Host-only: no GPU needed."""
+    return int(lib().vss_layers_map(int(v), int(canvas), int(frame)))
+
+
+def parse_color(text: str):
+    """'#RRGGBB' or 'rgba(r, g, b, a)' (a in 0..1) -> (r, g, b, a) bytes, a = floor(a*255 + 0.5)."""
+    import math
+    t = text.strip()
+    if t.startswith("#") and len(t) == 7:
+        return int(t[1:3], 16), int(t[3:5], 16), int(t[5:7], 16), 255
+    if t.startswith("rgba(") and t.endswith(")"):
+        r, g, b, a = (p.strip() for p in t[5:-1].split(","))
+        return int(r), int(g), int(b), int(math.floor(float(a) * 255 + 0.5))
+    raise VssError(VSS_E_INVALID_ARG, f"colour must be '#RRGGBB' or 'rgba(r,g,b,a)', got {text!r}")
+
+
+def template_layers(template: dict, fields: dict, images: dict, rasterize) -> list:
+    """One template of the reference's data.json -> a list of Layer, following
+    updateCanvas (customization.ts:44-77).  fields: the employee's text by content
+    key; images: RGBA uint8 [h,w,4] by content key (an absent key is skipped, :69);
+    rasterize(text, font, color) -> (rgba [h,w,4], ascent): the host's font engine
+    (there is none here), the sprite placed with its baseline at the layer's y.
+    Text is split on newlines, one layer per line at y + i*lineHeight (:80);
+    'department_and_company' is two lines (:59).  Shadows apply to text only
+    (:53).  Defaults: colour #FFFFFF, align left, font '24px Rubik' (:48-50),
+    line height 40 (:60)."""
+    import math
+    out = []
+    for t in template["layers"]:
+        privacy = PRIVACY_LEVELS[t["privacy"]]
+        kind = t["type"]
+        if kind == "roundedRect":
+            out.append(Layer("rect", privacy, t["x"], t["y"], t["width"], t["height"], radius=t.get("radius", 0),
+                             color=parse_color(t["color"])))
+        elif kind == "image":
+            img = images.get(t["content"])
+            if img is not None:
+                out.append(Layer("image", privacy, t["x"], t["y"], t["width"], t["height"], pixels=img))
+        elif kind == "text":
+            if t["content"] == "department_and_company":
+                text = f"{fields.get('department', '')}\n{fields.get('company', '')}"
+            else:
+                text = fields.get(t["content"])
+            if not text:
+                continue
+            color = parse_color(t.get("color") or "#FFFFFF")
+            shadow = None
+            if t.get("shadow"):
+                sh = t["shadow"]
+                shadow = {"color": parse_color(sh["color"]), "blur": int(sh["blur"]), "dx": int(sh["offsetX"]),
+                          "dy": int(sh["offsetY"])}
+            align = t.get("align") or "left"
+            for i, line in enumerate(text.split("\n")):
+                rgba, ascent = rasterize(line, t.get("font") or "24px Rubik", color)
+                rgba = np.asarray(rgba)
+                h, w = rgba.shape[:2]
+                x = t["x"] - w if align == "right" else t["x"] - w / 2 if align == "center" else t["x"]
+                y = t["y"] + i * (t.get("lineHeight") or 40) - ascent
+                out.append(Layer("image", privacy, int(math.floor(x + 0.5)), int(math.floor(y + 0.5)), w, h,
+                                 pixels=rgba, shadow=shadow))
+    return out
 
 
 def background_composite_device(session: Session, bg: Background, frames_ptr: int, n: int, h: int, w: int, c: int,

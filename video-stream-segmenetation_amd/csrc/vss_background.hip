@@ -82,7 +82,11 @@ constexpr int kBlurTW = 64, kBlurTH = 32;  // k_bg_composite<BLUR>'s tile: 16 x 
 
 }  // namespace
 
-template <int MODE, bool REFINE>
+// LAYERS (BLUR only): the overlay plate O goes between the blurred frame and
+// the person, bg' = O over bg (under_overlay, vss_kernels.h), one 16-B load of
+// O's 4 pixels per thread row.  COLOR / IMAGE with layers run the IMAGE form
+// over a plate that holds bg' already (k_bg_bake, vss_layers.hip).
+template <int MODE, bool REFINE, bool LAYERS = false>
 __global__ __launch_bounds__(256) void k_bg_composite(BgCompositeParams p) {
   const CompositeParams& c = p.c;
   const int t = blockIdx.z;
@@ -145,6 +149,14 @@ __global__ __launch_bounds__(256) void k_bg_composite(BgCompositeParams p) {
       uint32_t bg[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) bg[k] = (acc[k][0] >> 16) | ((acc[k][1] >> 16) << 8) | ((acc[k][2] >> 16) << 16);
+      if constexpr (LAYERS) {
+        // x0 is a multiple of 4 below fw, the plate's rows are whole quads: in bounds and 16-B aligned
+        const uint4 o = *reinterpret_cast<const uint4*>(p.overlay + (long)y * layer_pitch(c.fw) + x0);
+        bg[0] = under_overlay(bg[0], o.x);
+        bg[1] = under_overlay(bg[1], o.y);
+        bg[2] = under_overlay(bg[2], o.z);
+        bg[3] = under_overlay(bg[3], o.w);
+      }
       blend_quad<REFINE>(c, m, t, y, x0, bg);
     }
   }
@@ -220,7 +232,12 @@ void launch_bg_composite(const BgCompositeParams& p, int mode, int n, hipStream_
   } else {
     const size_t lds = ((size_t)(kBlurTH + 2 * p.radius) * kBlurTW + p.radius + 1) * 4;
     const dim3 bgrid((p.c.fw + kBlurTW - 1) / kBlurTW, (p.c.fh + kBlurTH - 1) / kBlurTH, n);
-    if (refine)
+    if (p.overlay) {
+      if (refine)
+        hipLaunchKernelGGL((k_bg_composite<kBgBlur, true, true>), bgrid, dim3(256), lds, s, p);
+      else
+        hipLaunchKernelGGL((k_bg_composite<kBgBlur, false, true>), bgrid, dim3(256), lds, s, p);
+    } else if (refine)
       hipLaunchKernelGGL((k_bg_composite<kBgBlur, true>), bgrid, dim3(256), lds, s, p);
     else
       hipLaunchKernelGGL((k_bg_composite<kBgBlur, false>), bgrid, dim3(256), lds, s, p);

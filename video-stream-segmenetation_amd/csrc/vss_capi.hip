@@ -3230,6 +3230,25 @@ struct vss_background {
   double refine_eps = 0.0;
   uint8_t* d_matte = nullptr;    // its planes for n frames: (abar, bbar), (a_q, b_q), L; grown on demand
   size_t matte_bytes = 0;
+  // branding layers (include/vss_layers.h)
+  struct Layer {
+    vss_layer l;                 // pixels = null: the sprite lives in d_sprites
+    size_t sprite_off;           // IMAGE: byte offset of its premultiplied copy
+  };
+  std::vector<Layer> layers;
+  int canvas_w = 1920, canvas_h = 1080;  // customization.ts:37
+  int level = 2;                 // 'medium', customization.ts:28
+  uint8_t* d_sprites = nullptr;  // every IMAGE layer's sprite, premultiplied RGBA, tight rows
+  size_t sprites_bytes = 0;
+  uint32_t* d_plate = nullptr;   // the overlay O at plate_fh x plate_fw (0: not built), rows of layer_pitch dwords
+  int plate_fh = 0, plate_fw = 0;
+  size_t plate_bytes = 0;
+  uint8_t* d_shadow = nullptr;   // the shadows' two u8 planes, [2][fh][layer_pitch]
+  size_t shadow_bytes = 0;
+  int img_mode = -1;             // what d_img holds: the mode it was built for,
+  bool img_layered = false;      // whether O is baked into it,
+  uint32_t img_color = 0;        // and (COLOR) from which colour
+  bool img_for_image = false;    // d_img has served image mode (else it exists for a colour under layers only)
   hipEvent_t last = nullptr;     // recorded after every composite
   hipStream_t last_stream = nullptr;
   bool used = false;
@@ -3344,6 +3363,97 @@ int matte_enqueue(vss_handle* h, vss_background* bg, const uint8_t* d_frames, in
   return VSS_OK;
 }
 
+// map(v, canvas, frame) of include/vss_layers.h: round half up with true floor division
+long layers_map(long v, long canvas, long frame) {
+  const long num = 2 * v * frame + canvas, den = 2 * canvas;
+  long q = num / den;
+  if (num % den < 0) --q;
+  return q;
+}
+
+bool layers_visible(const vss_background* bg) {
+  for (const auto& L : bg->layers)
+    if (L.l.privacy <= bg->level) return true;
+  return false;
+}
+
+int clip(long v, int hi) { return (int)std::min<long>(std::max<long>(v, 0), hi); }
+
+// bg->mu held; some layer is visible.  The overlay plate O for a frame fh x fw,
+// rebuilt on s when the layers, the level or the frame size changed.
+int plate_enqueue(vss_handle* h, vss_background* bg, int fh, int fw, hipStream_t s) {
+  if (bg->plate_fh == fh && bg->plate_fw == fw) return VSS_OK;
+  const int pitch = layer_pitch(fw);
+  const size_t need = (size_t)pitch * fh * 4;
+  bool shadows = false;
+  for (const auto& L : bg->layers) shadows |= L.l.privacy <= bg->level && L.l.has_shadow;
+  const size_t need_sh = shadows ? (size_t)pitch * fh * 2 : 0;
+  if (need > bg->plate_bytes || need_sh > bg->shadow_bytes) {
+    int rc = bg_quiesce(bg);
+    if (!rc && need > bg->plate_bytes) rc = bg_alloc(bg, &bg->d_plate, &bg->plate_bytes, need);
+    if (!rc && need_sh > bg->shadow_bytes) rc = bg_alloc(bg, &bg->d_shadow, &bg->shadow_bytes, need_sh);
+    if (rc) return rc;
+  }
+  bg->plate_fh = bg->plate_fw = 0;
+  HIP_TRY(h, hipMemsetAsync(bg->d_plate, 0, need, s));
+  const long cw = bg->canvas_w, ch = bg->canvas_h;
+  for (const auto& L : bg->layers) {
+    const vss_layer& l = L.l;
+    if (l.privacy > bg->level) continue;
+    LayerGeom g{};
+    g.type = l.type;
+    g.X0 = layers_map(l.x, cw, fw);
+    g.X1 = layers_map((long)l.x + l.width, cw, fw);
+    g.Y0 = layers_map(l.y, ch, fh);
+    g.Y1 = layers_map((long)l.y + l.height, ch, fh);
+    if (g.X1 <= g.X0 || g.Y1 <= g.Y0) continue;
+    if (l.type == VSS_LAYER_ROUNDED_RECT) {
+      g.R = std::min(layers_map(l.radius, cw, fw), std::min((g.X1 - g.X0) / 2, (g.Y1 - g.Y0) / 2));
+      g.color = (uint32_t)l.color[0] | ((uint32_t)l.color[1] << 8) | ((uint32_t)l.color[2] << 16) |
+                ((uint32_t)l.color[3] << 24);
+    } else {
+      g.sprite = bg->d_sprites + L.sprite_off;
+      g.sh = l.src_h; g.sw = l.src_w;
+      g.sy = (float)l.src_h / (float)(g.Y1 - g.Y0);
+      g.sx = (float)l.src_w / (float)(g.X1 - g.X0);
+    }
+    if (l.has_shadow) {
+      ShadowParams sp{};
+      sp.g = g;
+      sp.dx = layers_map(l.shadow_dx, cw, fw);
+      sp.dy = layers_map(l.shadow_dy, ch, fh);
+      const double sigma = (double)l.shadow_blur * (double)fw / (2.0 * (double)cw);
+      int r = 3.0 * sigma >= (double)kBlurMaxRadius ? kBlurMaxRadius : (int)std::ceil(3.0 * sigma);
+      uint16_t w[2 * kBlurMaxRadius + 1];
+      std::string why;
+      if (r < 1 || blur_weights(r, sigma, w, &why)) r = 0;  // B = P
+      for (int k = 0; k <= r; ++k) sp.w[k] = w[r + k];
+      sp.radius = r;
+      sp.x0 = clip(g.X0 + sp.dx - r, fw); sp.x1 = clip(g.X1 + sp.dx + r, fw);
+      sp.y0 = clip(g.Y0 + sp.dy - r, fh); sp.y1 = clip(g.Y1 + sp.dy + r, fh);
+      sp.P = bg->d_shadow;
+      sp.Hb = bg->d_shadow + (size_t)pitch * fh;
+      sp.pitch = pitch;
+      sp.color = (uint32_t)l.shadow_color[0] | ((uint32_t)l.shadow_color[1] << 8) |
+                 ((uint32_t)l.shadow_color[2] << 16) | ((uint32_t)l.shadow_color[3] << 24);
+      sp.plate = bg->d_plate;
+      launch_layer_shadow(sp, s);
+    }
+    LayerDrawParams d{};
+    d.g = g;
+    d.x0 = clip(g.X0, fw); d.x1 = clip(g.X1, fw);
+    d.y0 = clip(g.Y0, fh); d.y1 = clip(g.Y1, fh);
+    d.plate = bg->d_plate;
+    d.pitch = pitch;
+    launch_layer_draw(d, s);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(h, VSS_E_HIP, std::string("layer launch: ") + hipGetErrorString(e));
+  bg->plate_fh = fh;
+  bg->plate_fw = fw;
+  return VSS_OK;
+}
+
 void composite_params(CompositeParams* c, const uint8_t* d_frames, int fh, int fw, int fc, size_t rs, size_t fs,
                       const uint8_t* d_alpha, int H, int W, uint8_t* d_out, size_t ors, size_t ofs) {
   c->frames = d_frames;
@@ -3375,27 +3485,54 @@ int bg_enqueue(vss_handle* h, vss_background* bg, const uint8_t* d_frames, int n
     const int rc = matte_enqueue(h, bg, d_frames, n, fh, fw, fc, rs, fs, d_alpha, p.c.H, p.c.W, s, &p.ab);
     if (rc) return rc;
   }
-  if (bg->mode == VSS_BG_IMAGE) {
-    if (bg->img_fh != fh || bg->img_fw != fw) {  // (re)build the cached scaled image
+  // branding layers: the overlay plate O, rebuilt here (outside anything captured or replayed) when it is stale
+  const bool layered = layers_visible(bg);
+  if (layered) {
+    const int rc = plate_enqueue(h, bg, fh, fw, s);
+    if (rc) return rc;
+  }
+  int mode = bg->mode;
+  if (mode == VSS_BG_IMAGE || (mode == VSS_BG_COLOR && layered)) {
+    // the cached plate: the scaled image, or with layers bg' = O over the image or the colour
+    if (bg->img_fh != fh || bg->img_fw != fw || bg->img_mode != mode || bg->img_layered != layered ||
+        (mode == VSS_BG_COLOR && bg->img_color != bg->color)) {
       const size_t need = (size_t)bg_image_stride(fw) * fh;
       if (need > bg->img_bytes) {
         int rc = bg_quiesce(bg);
         if (!rc) rc = bg_alloc(bg, &bg->d_img, &bg->img_bytes, need);
         if (rc) return rc;
       }
-      BgResizeParams r{};
-      r.src = bg->d_src;
-      r.sh = bg->sh; r.sw = bg->sw; r.sc = bg->sc;
-      r.sy = (float)bg->sh / (float)fh;
-      r.sx = (float)bg->sw / (float)fw;
-      r.out = bg->d_img;
-      r.fh = fh; r.fw = fw;
-      launch_bg_resize(r, s);
+      bg->img_fh = bg->img_fw = 0;
+      if (mode == VSS_BG_IMAGE) {
+        BgResizeParams r{};
+        r.src = bg->d_src;
+        r.sh = bg->sh; r.sw = bg->sw; r.sc = bg->sc;
+        r.sy = (float)bg->sh / (float)fh;
+        r.sx = (float)bg->sw / (float)fw;
+        r.out = bg->d_img;
+        r.fh = fh; r.fw = fw;
+        launch_bg_resize(r, s);
+        bg->img_for_image = true;
+      }
+      if (layered) {
+        BgBakeParams b{};
+        b.image = bg->d_img;
+        b.overlay = bg->d_plate;
+        b.fh = fh; b.fw = fw;
+        b.from_color = mode == VSS_BG_COLOR;
+        b.color = bg->color;
+        launch_bg_bake(b, s);
+      }
       bg->img_fh = fh;
       bg->img_fw = fw;
+      bg->img_mode = mode;
+      bg->img_layered = layered;
+      bg->img_color = bg->color;
     }
     p.image = bg->d_img;
+    mode = VSS_BG_IMAGE;  // a colour under layers is a plate too
   } else if (bg->mode == VSS_BG_BLUR) {
+    if (layered) p.overlay = bg->d_plate;
     const size_t need = (size_t)n * fh * fw * 4;
     if (need > bg->hblur_bytes) {
       int rc = bg_quiesce(bg);
@@ -3415,7 +3552,7 @@ int bg_enqueue(vss_handle* h, vss_background* bg, const uint8_t* d_frames, int n
     p.radius = bg->radius;
     std::copy(bg->w, bg->w + kBlurMaxRadius + 1, p.w);
   }
-  launch_bg_composite(p, bg->mode, n, s);
+  launch_bg_composite(p, mode, n, s);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(h, VSS_E_HIP, std::string("background launch: ") + hipGetErrorString(e));
   HIP_TRY(h, hipEventRecord(bg->last, s));
@@ -3427,6 +3564,7 @@ int bg_enqueue(vss_handle* h, vss_background* bg, const uint8_t* d_frames, int n
 }  // namespace
 
 static_assert(VSS_BG_COLOR == kBgColor && VSS_BG_IMAGE == kBgImage && VSS_BG_BLUR == kBgBlur, "modes mirror vss.h");
+static_assert(VSS_LAYER_IMAGE == kLayerImage && VSS_LAYER_ROUNDED_RECT == kLayerRect, "layer types mirror vss_layers.h");
 
 extern "C" {
 
@@ -3459,6 +3597,9 @@ void vss_background_destroy(vss_background* bg) {
   (void)bg_alloc(bg, &bg->d_img, &bg->img_bytes, 0);
   (void)bg_alloc(bg, &bg->d_hblur, &bg->hblur_bytes, 0);
   (void)bg_alloc(bg, &bg->d_matte, &bg->matte_bytes, 0);
+  (void)bg_alloc(bg, &bg->d_sprites, &bg->sprites_bytes, 0);
+  (void)bg_alloc(bg, &bg->d_plate, &bg->plate_bytes, 0);
+  (void)bg_alloc(bg, &bg->d_shadow, &bg->shadow_bytes, 0);
   if (bg->last) (void)hipEventDestroy(bg->last);
   delete bg;
 }
@@ -3531,6 +3672,124 @@ int vss_background_set_refine(vss_background* bg, int radius, double eps) {
   std::lock_guard<std::mutex> lk(bg->mu);
   bg->refine_radius = radius;
   bg->refine_eps = radius ? eps : 0.0;
+  return VSS_OK;
+}
+
+// ---- branding layers (include/vss_layers.h) ----
+int vss_layers_map(int v, int canvas, int frame) {
+  if (canvas < 1) return 0;
+  const long q = layers_map(v, canvas, frame);
+  return (int)std::min<long>(std::max<long>(q, INT_MIN), INT_MAX);
+}
+
+int vss_background_set_layers(vss_background* bg, const vss_layer* layers, int n, int canvas_w, int canvas_h) {
+  if (!bg) return fail(nullptr, VSS_E_INVALID_ARG, "null background");
+  vss_handle* h = bg->h;
+  if (n < 0 || n > VSS_MAX_LAYERS) return fail(h, VSS_E_INVALID_ARG, "layer count must be in [0, 32]");
+  if (canvas_w < 1 || canvas_h < 1) return fail(h, VSS_E_INVALID_ARG, "canvas size must be >= 1 x 1");
+  if (n > 0 && !layers) return fail(h, VSS_E_INVALID_ARG, "null layer array");
+  size_t total = 0;
+  for (int i = 0; i < n; ++i) {
+    const vss_layer& l = layers[i];
+    const std::string at = "layer " + std::to_string(i) + ": ";
+    if (l.type != VSS_LAYER_IMAGE && l.type != VSS_LAYER_ROUNDED_RECT)
+      return fail(h, VSS_E_INVALID_ARG, at + "unknown type");
+    if (l.privacy < 1 || l.privacy > 3) return fail(h, VSS_E_INVALID_ARG, at + "privacy must be in [1, 3]");
+    if (l.width < 0 || l.height < 0) return fail(h, VSS_E_INVALID_ARG, at + "width and height must be >= 0");
+    if (l.radius < 0) return fail(h, VSS_E_INVALID_ARG, at + "radius must be >= 0");
+    if (l.shadow_blur < 0) return fail(h, VSS_E_INVALID_ARG, at + "shadow_blur must be >= 0");
+    if (l.type == VSS_LAYER_IMAGE) {
+      if (!l.pixels) return fail(h, VSS_E_INVALID_ARG, at + "null sprite");
+      if (l.src_h < 1 || l.src_h > VSS_LAYER_MAX_SPRITE || l.src_w < 1 || l.src_w > VSS_LAYER_MAX_SPRITE)
+        return fail(h, VSS_E_INVALID_ARG, at + "sprite sides must be in [1, 4096]");
+      if (l.row_stride < (size_t)l.src_w * 4) return fail(h, VSS_E_INVALID_ARG, at + "row_stride < 4 * src_w");
+      total += (size_t)l.src_h * l.src_w * 4;
+    }
+  }
+  // the sprites, premultiplied once: c' = (c*a + 127) / 255
+  std::vector<uint8_t> host(total);
+  std::vector<vss_background::Layer> fresh((size_t)n);
+  size_t off = 0;
+  for (int i = 0; i < n; ++i) {
+    fresh[i].l = layers[i];
+    fresh[i].l.pixels = nullptr;
+    fresh[i].sprite_off = off;
+    if (layers[i].type != VSS_LAYER_IMAGE) continue;
+    const vss_layer& l = layers[i];
+    for (int y = 0; y < l.src_h; ++y) {
+      const uint8_t* src = l.pixels + (size_t)y * l.row_stride;
+      uint8_t* dst = host.data() + off + (size_t)y * l.src_w * 4;
+      for (int x = 0; x < l.src_w; ++x) {
+        const unsigned a = src[4 * x + 3];
+        for (int c = 0; c < 3; ++c) dst[4 * x + c] = (uint8_t)((src[4 * x + c] * a + 127u) / 255u);
+        dst[4 * x + 3] = (uint8_t)a;
+      }
+    }
+    off += (size_t)l.src_h * l.src_w * 4;
+  }
+  std::lock_guard<std::mutex> lk(bg->mu);
+  int rc = bg_quiesce(bg);  // a composite may still read the old sprites and plates
+  if (rc) return rc;
+  bg->layers.clear();
+  bg->plate_fh = bg->plate_fw = 0;  // O and what is baked from it: rebuilt by the next composite
+  bg->img_fh = bg->img_fw = 0;
+  rc = bg_alloc(bg, &bg->d_sprites, &bg->sprites_bytes, total);
+  if (!rc && total) {
+    const hipError_t e = hipMemcpy(bg->d_sprites, host.data(), total, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      (void)bg_alloc(bg, &bg->d_sprites, &bg->sprites_bytes, 0);
+      rc = fail(h, VSS_E_HIP, std::string("sprite upload: ") + hipGetErrorString(e));
+    }
+  }
+  if (rc) n = 0;  // out of memory or a failed upload: no layers, as after n = 0
+  if (n == 0) {
+    (void)bg_alloc(bg, &bg->d_plate, &bg->plate_bytes, 0);
+    (void)bg_alloc(bg, &bg->d_shadow, &bg->shadow_bytes, 0);
+    // a plate that only a colour under layers needed
+    if (!bg->img_for_image) (void)bg_alloc(bg, &bg->d_img, &bg->img_bytes, 0);
+    bg->img_mode = -1;
+    return rc;
+  }
+  bg->layers = std::move(fresh);
+  bg->canvas_w = canvas_w;
+  bg->canvas_h = canvas_h;
+  return VSS_OK;
+}
+
+int vss_background_set_privacy(vss_background* bg, int level) {
+  if (!bg) return fail(nullptr, VSS_E_INVALID_ARG, "null background");
+  if (level < 1 || level > 3) return fail(bg->h, VSS_E_INVALID_ARG, "privacy level must be in [1, 3]");
+  std::lock_guard<std::mutex> lk(bg->mu);
+  if (level == bg->level) return VSS_OK;
+  bg->level = level;
+  bg->plate_fh = bg->plate_fw = 0;
+  bg->img_fh = bg->img_fw = 0;
+  return VSS_OK;
+}
+
+int vss_background_overlay_device(vss_handle* h, vss_background* bg, int height, int width, uint8_t* d_out,
+                                  size_t row_stride, void* stream) {
+  if (!h) return fail(nullptr, VSS_E_INVALID_ARG, "null handle");
+  if (!bg || bg->h != h) return fail(h, VSS_E_INVALID_ARG, "handle / background mismatch");
+  if (!d_out) return fail(h, VSS_E_INVALID_ARG, "null device pointer");
+  if (height < 1 || width < 1 || height > 16384 || width > 16384)
+    return fail(h, VSS_E_INVALID_ARG, "overlay size must be in [1, 16384]");
+  if (row_stride < (size_t)width * 4) return fail(h, VSS_E_INVALID_ARG, "row_stride < 4 * width");
+  HIP_TRY(h, hipSetDevice(h->device));
+  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  std::lock_guard<std::mutex> lk(bg->mu);
+  if (bg->used && bg->last_stream != s) HIP_TRY(h, hipStreamWaitEvent(s, bg->last, 0));
+  if (layers_visible(bg)) {
+    const int rc = plate_enqueue(h, bg, height, width, s);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemcpy2DAsync(d_out, row_stride, bg->d_plate, (size_t)layer_pitch(width) * 4, (size_t)width * 4,
+                                height, hipMemcpyDeviceToDevice, s));
+  } else {
+    HIP_TRY(h, hipMemset2DAsync(d_out, row_stride, 0, (size_t)width * 4, height, s));
+  }
+  HIP_TRY(h, hipEventRecord(bg->last, s));
+  bg->last_stream = s;
+  bg->used = true;
   return VSS_OK;
 }
 

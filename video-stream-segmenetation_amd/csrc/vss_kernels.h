@@ -659,6 +659,7 @@ struct BgCompositeParams {
   const uint32_t* hblur;   // BLUR: [n][fh][fw] RGBX, the horizontal pass
   int radius;              // BLUR
   uint16_t w[kBlurMaxRadius + 1];  // BLUR: taps 0 (centre) .. radius, 16-bit fixed point
+  const uint32_t* overlay; // BLUR with visible layers: the plate O [fh][layer_pitch(fw)] premultiplied RGBA; else null
 };
 void launch_bg_composite(const BgCompositeParams& p, int mode, int n, hipStream_t s);
 
@@ -680,6 +681,69 @@ struct BgResizeParams {
   int fh, fw;
 };
 void launch_bg_resize(const BgResizeParams& p, hipStream_t s);
+
+// Branding layers (vss_layers.hip; the definition: include/vss_layers.h).  The
+// overlay plate O is premultiplied RGBA, one dword per pixel (r | g << 8 |
+// b << 16 | a << 24), rows padded to whole quads so that k_bg_composite's
+// threads load their 4 pixels as one 16-B word.
+constexpr int kLayerImage = 0, kLayerRect = 1;
+__host__ __device__ constexpr int layer_pitch(int fw) { return (fw + 3) / 4 * 4; }
+// bg' = min(255, O.c + (bg.c*(255 - O.a) + 127) / 255) on a packed r | g << 8 | b << 16
+__device__ __forceinline__ uint32_t under_overlay(uint32_t bg, uint32_t o) {
+  const uint32_t ia = 255u - (o >> 24);
+  uint32_t out = 0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const uint32_t v = ((o >> (8 * c)) & 255u) + ((((bg >> (8 * c)) & 255u) * ia + 127u) / 255u);
+    out |= min(v, 255u) << (8 * c);
+  }
+  return out;
+}
+
+// One layer at one frame size: its unclipped destination rectangle in frame
+// pixels (64-bit: x, y and the sizes are free on the canvas).
+struct LayerGeom {
+  int type;                // kLayerImage / kLayerRect
+  long X0, Y0, X1, Y1;
+  long R;                  // ROUNDED_RECT: the clamped corner radius, frame pixels
+  uint32_t color;          // ROUNDED_RECT: r | g << 8 | b << 16 | a << 24, not premultiplied
+  const uint8_t* sprite;   // IMAGE: [sh][sw][4] premultiplied RGBA, tight rows
+  int sh, sw;
+  float sy, sx;            // (float)sh / (Y1 - Y0), (float)sw / (X1 - X0)
+};
+// the layer's sample source-over into O, over the clipped rectangle [x0, x1) x [y0, y1)
+struct LayerDrawParams {
+  LayerGeom g;
+  int x0, y0, x1, y1;
+  uint32_t* plate;         // [fh][pitch]
+  int pitch;
+};
+void launch_layer_draw(const LayerDrawParams& p, hipStream_t s);
+// The drop shadow over the region [x0, x1) x [y0, y1): the shifted rectangle
+// grown by the radius and clipped to the frame.  P and Hb are u8 planes
+// [fh][pitch], written and read inside the region only (0 outside it).
+struct ShadowParams {
+  LayerGeom g;
+  long dx, dy;             // the shift, frame pixels
+  int x0, y0, x1, y1;
+  uint8_t* P;              // the shifted alpha
+  uint8_t* Hb;             // its horizontal pass
+  int pitch;
+  int radius;              // 0: B = P, no passes
+  uint16_t w[kBlurMaxRadius + 1];
+  uint32_t color;          // r | g << 8 | b << 16 | a << 24, not premultiplied
+  uint32_t* plate;         // [fh][pitch]
+};
+void launch_layer_shadow(const ShadowParams& p, hipStream_t s);
+// colour and image modes: bg' baked into the RGB plate k_bg_composite<IMAGE> reads
+struct BgBakeParams {
+  uint8_t* image;          // [fh][bg_image_stride(fw)] RGB, in place (from_color: written only)
+  const uint32_t* overlay; // [fh][layer_pitch(fw)]
+  int fh, fw;
+  int from_color;          // bg = color everywhere instead of the image's pixels
+  uint32_t color;
+};
+void launch_bg_bake(const BgBakeParams& p, hipStream_t s);
 
 // Edge-aware matte (vss_matte.hip; the definition: include/vss.h): a guided
 // filter of the alpha bytes by the frame's luma.  The mask-resolution stage —

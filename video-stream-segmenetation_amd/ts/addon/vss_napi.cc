@@ -45,6 +45,8 @@
 //   backgroundSetImage(background, pixels: Uint8Array, height, width, channels, rowStride)
 //   backgroundSetBlur(background, radius, sigma), backgroundDestroy(background)
 //   backgroundSetRefine(background, radius, eps)   the edge-aware alpha; radius 0 = off
+//   backgroundSetLayers(background, layers: flat layer objects (segment.ts), canvasWidth, canvasHeight)
+//   backgroundSetPrivacy(background, level)
 //   segmentBackground(handle, post, frames, n, height, width, channels, rowStride, background)
 //   videoCreate(handle, std) / videoSetStandard(video, std) / videoDestroy(video)   NV12 I/O (vss_video.h)
 //   videoProcess(handle, video, post, background, y, uv, n, height, width) -> Promise<{y, uv}>
@@ -740,6 +742,94 @@ napi_value BackgroundSetRefine(napi_env env, napi_callback_info info) {
   napi_get_value_double(env, argv[2], &eps);
   const int rc = vss_background_set_refine(b->bg, radius, eps);
   if (rc != VSS_OK) throw_vss(env, "vss_background_set_refine", rc, vss_last_error(b->hd->h));
+  return nullptr;
+}
+
+// one int32 property of a flat layer object (segment.ts flattens BrandLayer); absent or not a number: 0
+int layer_int(napi_env env, napi_value obj, const char* name) {
+  napi_value v;
+  int out = 0;
+  if (napi_get_named_property(env, obj, name, &v) == napi_ok) napi_get_value_int32(env, v, &out);
+  return out;
+}
+
+napi_value BackgroundSetLayers(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Bg* b = argc >= 4 ? get_bg(env, argv[0]) : nullptr;
+  if (!b) return nullptr;
+  bool is_arr = false;
+  napi_is_array(env, argv[1], &is_arr);
+  uint32_t n = 0;
+  if (is_arr) napi_get_array_length(env, argv[1], &n);
+  if (!is_arr || n > VSS_MAX_LAYERS) {
+    napi_throw_range_error(env, nullptr, "layers must be an array of at most 32 layers");
+    return nullptr;
+  }
+  std::vector<vss_layer> layers(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    napi_value o;
+    NAPI_OK(env, napi_get_element(env, argv[1], i, &o));
+    vss_layer& l = layers[i];
+    l = vss_layer{};
+    l.type = layer_int(env, o, "type");
+    l.privacy = layer_int(env, o, "privacy");
+    l.x = layer_int(env, o, "x");
+    l.y = layer_int(env, o, "y");
+    l.width = layer_int(env, o, "width");
+    l.height = layer_int(env, o, "height");
+    l.radius = layer_int(env, o, "radius");
+    const char* rgba[4] = {"r", "g", "b", "a"};
+    const char* srgba[4] = {"sr", "sg", "sb", "sa"};
+    for (int k = 0; k < 4; ++k) {
+      l.color[k] = (uint8_t)layer_int(env, o, rgba[k]);
+      l.shadow_color[k] = (uint8_t)layer_int(env, o, srgba[k]);
+    }
+    l.has_shadow = layer_int(env, o, "hasShadow");
+    l.shadow_blur = layer_int(env, o, "blur");
+    l.shadow_dx = layer_int(env, o, "dx");
+    l.shadow_dy = layer_int(env, o, "dy");
+    if (l.type != VSS_LAYER_IMAGE) continue;
+    l.src_h = layer_int(env, o, "srcHeight");
+    l.src_w = layer_int(env, o, "srcWidth");
+    napi_value px;
+    bool is_ta = false;
+    if (napi_get_named_property(env, o, "pixels", &px) == napi_ok) napi_is_typedarray(env, px, &is_ta);
+    napi_typedarray_type tt = napi_int8_array;
+    size_t len = 0, off = 0;
+    void* data = nullptr;
+    napi_value buf;
+    if (is_ta) NAPI_OK(env, napi_get_typedarray_info(env, px, &tt, &len, &data, &buf, &off));
+    if (!is_ta || (tt != napi_uint8_array && tt != napi_uint8_clamped_array)) {
+      napi_throw_type_error(env, nullptr, "an image layer's pixels must be a Uint8Array or Uint8ClampedArray");
+      return nullptr;
+    }
+    if (l.src_h < 1 || l.src_w < 1 || len < (size_t)l.src_h * (size_t)l.src_w * 4) {
+      napi_throw_range_error(env, nullptr, "pixels buffer smaller than srcHeight * srcWidth * 4");
+      return nullptr;
+    }
+    l.pixels = static_cast<const uint8_t*>(data);
+    l.row_stride = (size_t)l.src_w * 4;
+  }
+  int cw = 0, ch = 0;
+  napi_get_value_int32(env, argv[2], &cw);
+  napi_get_value_int32(env, argv[3], &ch);
+  const int rc = vss_background_set_layers(b->bg, layers.data(), (int)n, cw, ch);
+  if (rc != VSS_OK) throw_vss(env, "vss_background_set_layers", rc, vss_last_error(b->hd->h));
+  return nullptr;
+}
+
+napi_value BackgroundSetPrivacy(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_OK(env, napi_get_cb_info(env, info, &argc, argv, nullptr, nullptr));
+  Bg* b = argc >= 2 ? get_bg(env, argv[0]) : nullptr;
+  if (!b) return nullptr;
+  int level = 0;
+  napi_get_value_int32(env, argv[1], &level);
+  const int rc = vss_background_set_privacy(b->bg, level);
+  if (rc != VSS_OK) throw_vss(env, "vss_background_set_privacy", rc, vss_last_error(b->hd->h));
   return nullptr;
 }
 
@@ -2300,6 +2390,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"backgroundSetImage", nullptr, BackgroundSetImage, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"backgroundSetBlur", nullptr, BackgroundSetBlur, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"backgroundSetRefine", nullptr, BackgroundSetRefine, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"backgroundSetLayers", nullptr, BackgroundSetLayers, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"backgroundSetPrivacy", nullptr, BackgroundSetPrivacy, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"backgroundDestroy", nullptr, BackgroundDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"segmentBackground", nullptr, SegmentBackground, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"videoCreate", nullptr, VideoCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
