@@ -142,6 +142,32 @@ def test_blur_bitexact(pkg, torch_cuda, oracle, blur_inputs, radius, sigma, gi):
     _same(f"blur r={radius}", got, want)
 
 
+def test_blur_two_gpu_streams_without_a_host_wait(pkg, torch_cuda, oracle, blur_inputs):
+    """One frame on one GPU stream, then two frames on another, nothing waited for in
+    between: the horizontal pass's buffer has to grow for the second call while the
+    first may still read it, and the second call's stream is ordered after the first's."""
+    torch = torch_cuda
+    _, fh, fw, c, _, _ = BLUR_GEOMS[2]
+    frames, alpha = blur_inputs[2]
+    w = pkg.blur_weights(7, 2.5)
+    dev = [(torch.from_numpy(frames[:n]).cuda(), torch.from_numpy(alpha[:n]).cuda(),
+            torch.zeros((n, fh, fw, 4), dtype=torch.uint8, device="cuda")) for n in (1, 2)]
+    gpu_streams = (torch.cuda.Stream(), torch.cuda.Stream())
+    with pkg.Session(model_h=48, model_w=64, dtype="f32", max_batch=4, autotune=False) as s:
+        bg = pkg.Background(s)
+        bg.set_blur(7, 2.5)
+        torch.cuda.synchronize()
+        for (df, da, do), st in zip(dev, gpu_streams):
+            n = df.shape[0]
+            pkg.background_composite_device(s, bg, df.data_ptr(), n, fh, fw, c, fw * c, fh * fw * c, da.data_ptr(),
+                                            do.data_ptr(), fw * 4, fh * fw * 4, st.cuda_stream)
+        torch.cuda.synchronize()
+        got = [do.cpu().numpy() for _, _, do in dev]
+    for n, g in zip((1, 2), got):
+        _same(f"blur, {n} frame(s) on their own GPU stream", g,
+              ref.composite(oracle, frames[:n], alpha[:n], ref.blur(frames[:n], w)))
+
+
 def test_replace_background_end_to_end(pkg, torch_cuda, synthetic, oracle):
     """Seam + post chain + background in one call == oracle.post on the GPU's own
     masks, then the reference composite; two calls of one stream per mode."""

@@ -228,6 +228,33 @@ def test_reset_without_a_wait(pkg, torch_cuda, sessions, stream_data, oracle):
         _cmp("after reset()", a, u, *_want(oracle, fresh, ids, fc, mc))
 
 
+def test_two_gpu_streams_without_a_host_wait(pkg, torch_cuda, sessions, stream_data, oracle):
+    """The same stream ids on one GPU stream, then on another, nothing waited for in
+    between: the second call reads the prevAlpha planes the first one writes, so the
+    pool itself has to order the two streams."""
+    torch = torch_cuda
+    H, W = 48, 80
+    s, data = sessions(H, W), stream_data(H, W)
+    states = {i: oracle.PostState(H, W) for i in LIVE}
+    used = dict.fromkeys(LIVE, 0)
+    ids = list(LIVE)
+    host = [_take(data, LIVE, ids, used) for _ in range(2)]
+    dev = [(torch.from_numpy(np.ascontiguousarray(f)).cuda(),
+            torch.from_numpy(np.ascontiguousarray(m, np.float32)).cuda(),
+            torch.full((3, H, W), -1.0, dtype=torch.float32, device="cuda"),
+            torch.zeros((3, H, W), dtype=torch.uint8, device="cuda")) for f, m in host]
+    gpu_streams = (torch.cuda.Stream(), torch.cuda.Stream())
+    with pkg.PostPool(s, 5) as pool:
+        torch.cuda.synchronize()
+        for (df, dm, da, du), st in zip(dev, gpu_streams):
+            pool.process_device(ids, df.data_ptr(), 3, FH, FW, 3, FW * 3, FH * FW * 3, dm.data_ptr(), da.data_ptr(),
+                                du.data_ptr(), st.cuda_stream)
+        torch.cuda.synchronize()
+        for k, ((f, m), (_, _, da, du)) in enumerate(zip(host, dev)):
+            _cmp(f"call {k} on its own GPU stream", da.cpu().numpy(), du.cpu().numpy(),
+                 *_want(oracle, states, ids, f, m))
+
+
 def test_many_streams(pkg, torch_cuda, sessions, synthetic, oracle):
     """Capacity 64 at max_batch 8: two rounds of 8 calls, each round over all 64 ids
     in a shuffled order (plane index and parity bookkeeping beyond n)."""

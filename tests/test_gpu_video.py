@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import background_ref as bg_ref  # noqa: E402
 import video_ref as ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -251,6 +252,43 @@ def test_stream_state_carries_across_calls(pkg, torch_cuda, sess, synthetic):
     c = _process_device(torch, v, fresh, bg, y[2:], uv[2:])
     assert not (np.array_equal(c[0], b[0]) and np.array_equal(c[1], b[1]))
     for o in (v, one, two, fresh, bg):
+        o.close()
+
+
+def test_two_gpu_streams_without_a_host_wait(pkg, torch_cuda, sess, synthetic, oracle):
+    """One frame on one GPU stream, then the stream's next two frames on another,
+    nothing waited for in between: the RGBA scratch has to grow for the second call
+    while the first may still use it, and the post state's prevAlpha goes from the
+    first call to the second.  Against pack(composite(unpack(in))) on the CPU, the
+    alpha from the oracle's post chain over the seam's masks of the unpacked frames."""
+    torch = torch_cuda
+    std, colour = ref.BT709_LIMITED, (10, 200, 90)
+    fh, fw = 100, 150
+    y, uv = _video_frames(synthetic, 3, fh, fw, std, 50)
+    rgba = ref.unpack(std, y, uv)
+    d_rgba = torch.from_numpy(rgba).cuda()
+    d_masks = torch.empty((3, sess.mask_h, sess.mask_w), dtype=torch.float32, device="cuda")
+    sess.segment_device(d_rgba.data_ptr(), 3, fh, fw, 4, fw * 4, fh * fw * 4, d_masks.data_ptr(), _stream(torch))
+    calls = (slice(0, 1), slice(1, 3))
+    dev = [(torch.from_numpy(y[c]).cuda(), torch.from_numpy(uv[c]).cuda(),
+            torch.zeros(y[c].shape, dtype=torch.uint8, device="cuda"),
+            torch.zeros(uv[c].shape, dtype=torch.uint8, device="cuda")) for c in calls]
+    gpu_streams = (torch.cuda.Stream(), torch.cuda.Stream())
+    bg, chain, v = pkg.Background(sess), pkg.PostChain(sess), pkg.Video(sess, std)
+    bg.set_color(*colour)
+    torch.cuda.synchronize()
+    for (dy, duv, oy, ouv), st in zip(dev, gpu_streams):
+        v.process_device(chain, bg, dy.data_ptr(), fw, fw * fh, duv.data_ptr(), fw, fw * fh // 2, dy.shape[0], fh, fw,
+                         oy.data_ptr(), fw, fw * fh, ouv.data_ptr(), fw, fw * fh // 2, st.cuda_stream)
+    torch.cuda.synchronize()
+    masks = d_masks.cpu().numpy()
+    state = oracle.PostState(sess.mask_h, sess.mask_w)
+    for c, (_, _, oy, ouv) in zip(calls, dev):
+        _, alpha = oracle.post(masks[c], rgba[c], state)
+        want_y, want_uv = ref.pack(std, bg_ref.composite(oracle, rgba[c], alpha, np.array(colour)))
+        _same(f"frames {c.start}..{c.stop - 1} Y", oy.cpu().numpy(), want_y)
+        _same(f"frames {c.start}..{c.stop - 1} UV", ouv.cpu().numpy(), want_uv)
+    for o in (v, chain, bg):
         o.close()
 
 

@@ -1,4 +1,7 @@
-// vss_capi.hip — the C ABI (include/vss.h) over the gfx950 kernels.
+// vss_capi.hip — the C ABI (include/vss.h) over the gfx950 kernels: the engine.
+// The post-processing, background and video objects' calls are in
+// vss_capi_post.hip, vss_capi_background.hip and vss_capi_video.hip; what they
+// share with the engine is in vss_engine.h.
 //
 // One engine per GPU mirrors one ORT InferenceSession
 // (/root/reference/client/src/core/model.ts:12-29): it parses the weights
@@ -16,30 +19,17 @@
 // concurrent slots never share one); one-GPU-per-process callers join a
 // clique with vss_comm_init_rank instead.
 #include <hip/hip_ext.h>
-#include <hip/hip_runtime.h>
 #include <immintrin.h>
-#include <rccl/rccl.h>
 
-#include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cmath>
-#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
 #include <fstream>
-#include <map>
 #include <memory>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <tuple>
-#include <vector>
 
-#include "../../include/vss.h"
-#include "vss_kernels.h"
+#include "vss_engine.h"
 
 namespace vss {
 void (*stem_kernel16())(StemParams);
@@ -48,6 +38,9 @@ void (*prep_kernel())(PrepParams);
 }  // namespace vss
 
 using namespace vss;
+using namespace vss_engine;
+
+thread_local std::string vss_engine::g_tls_error;
 
 namespace {
 
@@ -57,117 +50,6 @@ enum { F_EXPAND = 1, F_RESIDUAL = 2 };
 enum { O_W1, O_B1, O_WDW, O_BDW, O_W2, O_B2, O_GAMMA, O_BETA };
 constexpr int kDefaultQueueDepth = 4, kMaxQueueDepth = 16, kDefaultStagingThreads = 8;
 
-struct Rec {
-  uint32_t kind, cin, chid, cout, stride, flags, src, skip, off[8];
-};
-
-struct LayerPlan {
-  Rec rec{};
-  int C = 0, H = 0, W = 0;     // output shape
-  int inH = 0, inW = 0;        // shape of rec.src's output (x)
-  int mode = -1, stride = 1, chid = 0;
-  int TH = 0, TW = 0, tiles_x = 0, tiles_y = 0;
-  int flags = 0;
-  int ks = 1, xp = 1, sp = 1;  // hidden split of this layer, parts of its x / skip (block_flags)
-  size_t part_stride = 0;      // floats between the parts of an activation
-  long wimg_stride = 0;        // floats between the slices' weight images
-  size_t lds = 0;
-  const BlockEntry* entry = nullptr;  // compiled shape (registry)
-  const BlockEntry* small = nullptr;  // the autotuner's batch-1 pick, for forwards of <= small_tile_n frames
-  bool fused = false;          // computed inside its only consumer's prologue (no launch of its own)
-  int acc_off = -1;            // DEC: offset of its [kAccSlots][2][C] norm accumulator in a frame's row
-  const float* wimg = nullptr;  // LDS weight image (block_lds regions w1..b2)
-  const char* wfrag = nullptr;  // expand layers: the chunks' fragment records (expand_frag), slice after slice
-  long wfrag_stride = 0;        // bytes between the slices' records
-  const float *gamma = nullptr, *beta = nullptr;
-  const float *stem_w = nullptr, *stem_b = nullptr, *head_w = nullptr;
-  float head_b = 0.f;
-};
-
-// One kernel launch of the forward: function, grid, LDS and its parameter
-// block (every kernel takes one parameter struct by value).
-struct Launch {
-  const void* fn = nullptr;
-  dim3 grid;
-  int threads = kThreads;
-  size_t lds = 0;
-  int layer = 0;
-  union Prm {
-    StemParams stem;
-    BlockParams block;
-    HeadParams head;
-  } prm;
-};
-
-// A forward's executable graphs per (slot, shape): up to kExecPerShape
-// executables, each bound to the caller buffers (frames, masks) it last ran
-// with.  A call whose buffers match one replays it as is; otherwise a new
-// executable is built while the set has room, and after that the least
-// recently used one is patched (hipGraphExecKernelNodeSetParams on the kernel
-// nodes whose parameters differ — the first layer reads the frames, the head
-// writes the masks) once ITS last launch is done (its own event: the wait is
-// normally over already, since three newer launches were issued after it).
-// So callers rotating up to kExecPerShape buffer pairs through a slot never
-// patch in steady state, and no caller ever waits for the slot's latest work
-// here (the round-3 single executable waited on every call of a
-// caller rotating 3 buffers over 4 slots, holding the handle's lock).
-using GraphKey = std::tuple<int, int, int, int, size_t, size_t>;  // n, fh, fw, fc, row / frame stride
-constexpr int kExecPerShape = 4;
-struct GraphEntry {
-  hipGraph_t graph = nullptr;
-  hipGraphExec_t exec = nullptr;
-  hipEvent_t last = nullptr;          // recorded after this executable's latest launch
-  bool launched = false;
-  unsigned long long tick = 0;        // LRU clock of its latest launch
-  std::vector<hipGraphNode_t> nodes;  // one kernel node per launch, in order
-  std::vector<Launch> launches;       // the parameters the executable graph holds now
-};
-
-// The rows of an fh-row frame that the tfjs-legacy resize to the model's rows
-// reads (prep_tap's y0 / y1, the same float arithmetic), for the queued host
-// path's row staging (vss_stage.hip).
-struct RowPlan {
-  std::vector<int> rows;                    // sorted, distinct
-  std::vector<std::pair<int, int>> runs;    // [first, last + 1) runs of consecutive rows
-  int* d_rows = nullptr;                    // device copy of rows
-};
-
-// One batch in flight on one GPU: everything a forward writes.
-struct Slot {
-  std::vector<float*> act;            // per layer: [ks][max_batch][H][W][C]
-  unsigned long long* acc = nullptr;  // decoder instance-norm accumulators [max_batch][acc_stride]
-  float* d_masks = nullptr;           // [max_batch][P]: host paths' masks (the all-gather's send buffer)
-  float* d_gather = nullptr;          // RCCL handles: [nranks * max_batch][P]
-  hipStream_t stream = nullptr;       // the slot's stream (queued host calls)
-  hipEvent_t done = nullptr;          // recorded after the slot's latest work (host or device call)
-  hipStream_t done_stream = nullptr;  // the stream `done` was last recorded on
-  hipEvent_t host_done = nullptr;     // engine 0: recorded after the latest host batch's D2H
-  bool used = false;
-  // Host-side state of the slot's latest host batch (guarded by the handle's mu):
-  bool leased = false;                // reserved by vss_staging_acquire for its holder's next call
-  bool host_busy = false;             // a host batch whose completion (copy / callback /
-                                      // synchronous wait) has not finished; the slot's pinned
-                                      // buffers belong to it until then
-  int status = VSS_OK;                // of the latest host batch
-  vss_ticket ticket = ~0ull;          // latest host ticket that ran in this slot (device calls
-                                      // take no ticket and leave it alone)
-  bool stem_stored = false;           // the latest forward stored the fused stem (VSS_OPT_KEEP_STEM)
-  std::map<GraphKey, std::vector<GraphEntry>> graphs;
-  std::map<GraphKey, unsigned long long> shape_tick;  // per shape: graph_tick of its latest use
-  unsigned long long graph_tick = 0;
-#ifdef VSS_TRACE
-  std::vector<unsigned long long*> trace;  // per layer, [workgroups][16] stamps of this slot's latest forward
-#endif
-  ncclComm_t comm = nullptr;          // this GPU's communicator of the slot (RCCL handles)
-  // host-path staging, allocated on the slot's first host call
-  uint8_t* d_frames = nullptr;
-  uint8_t* h_frames = nullptr;        // pinned
-  float* h_masks = nullptr;           // pinned [max_batch][P] (engine 0: the whole batch)
-  float* d_fmasks = nullptr;          // VSS_OUT_FRAME: [max_batch][frame] masks
-  float* h_fmasks = nullptr;
-};
-
-thread_local std::string g_tls_error;
 // The handle whose completion thread this is (null on every other thread): a
 // callback runs there, and only that thread clears host_busy, so a call from a
 // callback that would wait for a host_busy slot returns VSS_E_BUSY instead of
@@ -217,7 +99,9 @@ static void staging_copy(void* dst, const void* src, size_t len) {
   else std::memcpy(dst, src, len);
 }
 
-class CopyPool {
+}  // namespace
+
+class vss_engine::CopyPool {
  public:
   explicit CopyPool(int threads) {
     for (int i = 0; i < threads; ++i) workers_.emplace_back([this] { loop(); });
@@ -320,129 +204,18 @@ class CopyPool {
   bool stop_ = false;
 };
 
-}  // namespace
-
-constexpr long kDefaultKsplitPixels = 256;
-
-struct vss_handle {
-  vss_config cfg{};            // this engine's config (max_batch = its share of the handle's)
-  std::string weights_path;
-  // the last error: written by any thread that fails a call (several may
-  // submit at once) and by the completion thread; read by vss_last_error,
-  // which copies it under err_mu into the caller's thread-local buffer
-  std::string err;
-  mutable std::mutex err_mu;
-  int device = 0;
-  hipStream_t stream = nullptr;          // NULL-stream device calls, post / composite, autotune
-  std::vector<Rec> recs;
-  std::vector<float> hdata;
-  float eps = 1e-5f;
-  std::vector<LayerPlan> L;
-  int acc_stride = 0;
-  std::vector<void*> dev_allocs;
-  std::vector<void*> host_allocs;
-  size_t dev_bytes = 0;
-  size_t frame_cap = 0;        // staging bytes per slot
-  std::vector<Slot> slots;
-  int last_slot = -1;          // slot of the latest forward (vss_read_layer)
-  std::map<int, RowPlan> row_plans;  // by frame height
-  int row_fetch = 1;           // VSS_OPT_ROW_FETCH
-#ifdef VSS_TRACE
-  std::vector<int> trace_wgs;              // workgroups of the layer's last launch
-#endif
-  uint8_t* d_comp = nullptr;      // vss_segment_composite / _background output, allocated on first use
-  std::atomic<size_t> bg_bytes{0};  // device buffers of the handle's vss_background and vss_video objects
-  float* d_post_alpha = nullptr;  // vss_segment_post outputs [max_batch][P]
-  uint8_t* d_post_u8 = nullptr;
-  int use_graph = 1;
-  int profile = 0;
-  int fuse_stem = 1;              // env VSS_FUSE_STEM=0: launch the stem on its own
-  int keep_stem = 0;              // VSS_OPT_KEEP_STEM: the fused stem also stores its activation
-  // expand layers with at most this many output pixels per frame split their
-  // hidden channels over ks_max() workgroups (env VSS_KSPLIT_PIXELS overrides)
-  long ksplit_pixels = kDefaultKsplitPixels;
-  // The hidden-channel split (KS workgroups per tile of a deep low-res expand
-  // layer, consumers summing the parts) buys latency with one batch in flight
-  // and costs throughput with four: measured round 4 (profiles/r04a/session.txt,
-  // two interleaved pairs): headline 206.9 / 206.1k without against 194.7 /
-  // 203.7k with, batch sweep at 4 in flight +4 % (b8), +7.5 % (b32), +6 % (b64),
-  // at 1 in flight -3 % (b8).  Off by default; env VSS_KSPLIT=1 turns it on.
-  bool ksplit_on = false;
-  // profiling: ring of event pairs per layer
-  static constexpr int kProfRing = 32;
-  std::vector<hipEvent_t> ev;  // [ring][layer][2]
-  std::vector<int> ring_pending;
-  int prof_next = 0;
-  std::vector<double> prof_sum;
-  int prof_count = 0;
-  int last_n = 0;
-  // ---- the handle (engine 0 only) ----
-  std::vector<vss_handle*> peers;  // engines 1..R-1 (device_ids[1..])
-  int user_max_batch = 0;          // the handle's max_batch (all GPUs)
-  bool rccl = false;               // host calls all-gather over RCCL (device_ids given)
-  int nranks = 1, rank = 0;        // vss_comm_init_rank clique (one GPU per process)
-  // set (release) once every communicator of the clique exists: the lock-free
-  // vss_comm_status reads the communicators only after seeing it (acquire)
-  std::atomic<bool> clique{false};
-  // VSS_OPT_GATHER_FORM, fixed at vss_comm_init_rank.  VSS_GATHER_ORDERED (the
-  // default): the clique's all-gathers on one communicator (slot 0's, the only
-  // one created) and one stream, events ordering each gather after its forward
-  // and the caller's stream after the gather — one total order of collectives
-  // per rank.  VSS_GATHER_CONCURRENT: each slot's own communicator on the
-  // slot's stream (vss_segment_gather_device)
-  int gather_form = VSS_GATHER_ORDERED;
-  std::vector<hipEvent_t> gather_ev;  // the ordered form's gather-done events, a ring of 2 x depth (call % size)
-  // Submissions (slot choice, staging, enqueue) are serialised by mu; no
-  // thread holds it while it waits for the GPU (waiters drop it first).
-  std::mutex mu;
-  std::condition_variable slot_cv;   // a slot's host_busy went false
-  std::mutex post_mu;              // the synchronous post / composite calls share scratch
-  vss_ticket next_ticket = 0;      // host batches (vss_submit*, vss_segment*)
-  unsigned long long device_calls = 0;  // vss_segment_device: slot = count % depth
-  int small_tile_n = 0;            // forwards of at most this many frames use LayerPlan::small
-  std::atomic<unsigned long long> gather_calls{0};  // vss_segment_gather_device: slot = count % depth
-                                                   // (atomic: vss_comm_status reads it lock-free)
-  long graph_builds = 0, graph_patches = 0;  // VSS_OPT_GRAPH_BUILDS / _PATCHES
-  CopyPool* pool = nullptr;
-  // The completion thread (started on the first host batch that needs one):
-  // waits for the queued host batches in ticket order, copies their masks
-  // from the slot's pinned buffer into the caller's memory, fires callbacks.
-  struct Completion {
-    vss_ticket ticket;
-    int slot;
-    float* out;          // null: the D2H already went to the caller's pinned block
-    const float* src;
-    size_t bytes;
-    vss_callback cb;
-    void* user;
-  };
-  std::thread done_thread;
-  std::mutex done_mu;
-  std::condition_variable done_cv;
-  std::deque<Completion> done_q;
-  bool done_stop = false;
-};
-
-namespace {
-
-void set_err(vss_handle* h, const std::string& msg) {
+void vss_engine::set_err(vss_handle* h, const std::string& msg) {
   std::lock_guard<std::mutex> lk(h->err_mu);
   h->err = msg;
 }
 
-int fail(vss_handle* h, int code, const std::string& msg) {
+int vss_engine::fail(vss_handle* h, int code, const std::string& msg) {
   if (h) set_err(h, msg);
   else g_tls_error = msg;
   return code;
 }
 
-#define HIP_TRY(h, expr)                                                                  \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess)                                                                 \
-      return fail((h), e_ == hipErrorOutOfMemory ? VSS_E_OOM : VSS_E_HIP,                \
-                  std::string(#expr) + ": " + hipGetErrorString(e_));                     \
-  } while (0)
+namespace {
 
 #define NCCL_TRY(h, expr)                                                                 \
   do {                                                                                    \
@@ -465,18 +238,6 @@ int comm_healthy(vss_handle* h, ncclComm_t c, int slot) {
   if (ae != ncclSuccess && ae != ncclInProgress)
     return fail(h, VSS_E_RCCL, "communicator of slot " + std::to_string(slot) + ": asynchronous error " +
                                    ncclGetErrorString(ae));
-  return VSS_OK;
-}
-
-template <class T>
-int dalloc(vss_handle* h, T** p, size_t bytes) {
-  void* q = nullptr;
-  bytes = std::max<size_t>(bytes, 16);
-  hipError_t e = hipMalloc(&q, bytes);
-  if (e != hipSuccess) return fail(h, VSS_E_OOM, "hipMalloc(" + std::to_string(bytes) + ") failed");
-  h->dev_allocs.push_back(q);
-  h->dev_bytes += bytes;
-  *p = static_cast<T*>(q);
   return VSS_OK;
 }
 
@@ -879,14 +640,14 @@ int ensure_staging(vss_handle* h, Slot& s) {
   if ((rc = dalloc(h, &s.d_frames, h->frame_cap))) return rc;
   if ((rc = halloc(h, &s.h_frames, h->frame_cap))) return rc;
   // engine 0 receives the whole batch's masks (gathered from every GPU)
-  const size_t nm = (size_t)std::max(h->cfg.max_batch, h->user_max_batch);
+  const size_t nm = (size_t)max_frames(h);
   if ((rc = halloc(h, &s.h_masks, nm * P * 4))) return rc;
   return VSS_OK;
 }
 
 int ensure_frame_masks(vss_handle* h, Slot& s) {
   if (s.h_fmasks) return VSS_OK;
-  const size_t cap = (size_t)std::max(h->cfg.max_batch, h->user_max_batch) * h->cfg.max_frame_h * h->cfg.max_frame_w;
+  const size_t cap = (size_t)max_frames(h) * h->cfg.max_frame_h * h->cfg.max_frame_w;
   int rc;
   if ((rc = dalloc(h, &s.d_fmasks, cap * 4))) return rc;
   if ((rc = halloc(h, &s.h_fmasks, cap * 4))) return rc;
@@ -925,7 +686,9 @@ int row_plan(vss_handle* h, int fh, const RowPlan** out) {
 }
 #pragma clang fp contract(on)
 
-int check_frames(vss_handle* h, int n, int fh, int fw, int fc, size_t rs, size_t fs, int max_n) {
+}  // namespace
+
+int vss_engine::check_frames(vss_handle* h, int n, int fh, int fw, int fc, size_t rs, size_t fs, int max_n) {
   if (n < 1 || n > max_n) return fail(h, VSS_E_INVALID_ARG, "n must be in [1, max_batch]");
   if (fh < 1 || fw < 1) return fail(h, VSS_E_INVALID_ARG, "bad frame size");
   if (fc != 3 && fc != 4) return fail(h, VSS_E_INVALID_ARG, "channels must be 3 or 4");
@@ -933,6 +696,8 @@ int check_frames(vss_handle* h, int n, int fh, int fw, int fc, size_t rs, size_t
   if (fs < rs * (size_t)fh) return fail(h, VSS_E_INVALID_ARG, "frame_stride < height*row_stride");
   return VSS_OK;
 }
+
+namespace {
 
 // The stem's parameters for this call's frames (frames point at frame 0 of the call).
 StemParams stem_params(const vss_handle* h, const Slot& s, int li, const uint8_t* frames, size_t rs, size_t fs,
@@ -2081,12 +1846,39 @@ void destroy_engine(vss_handle* h) {
   delete h;
 }
 
-
 }  // namespace
 
-static inline int segment_device_on(vss_handle* h, int* slot, const uint8_t* d_frames, int n, int height, int width,
-                                    int channels, size_t row_stride, size_t frame_stride, float* d_masks, void* stream)
-    __attribute__((always_inline));
+// vss_segment_device; slot != null: *slot < 0 takes the next slot of the
+// round-robin and returns it, *slot >= 0 runs on that slot (a caller that keeps
+// one buffer pair, vss_video, stays on one slot's executable graph).
+// always_inline (vss_engine.h): vss_segment_device keeps a body of its own; as
+// a call into a shared function the bench line read 1.7 % lower in three
+// alternating A/B pairs against the parent.
+int vss_engine::segment_device_on(vss_handle* h, int* slot, const uint8_t* d_frames, int n, int height, int width,
+                                  int channels, size_t row_stride, size_t frame_stride, float* d_masks,
+                                  void* stream) {
+  if (!h) return fail(nullptr, VSS_E_INVALID_ARG, "null handle");
+  if (!d_frames || !d_masks) return fail(h, VSS_E_INVALID_ARG, "null device pointer");
+  g_device_clock.begin();
+  int rc = check_frames(h, n, height, width, channels, row_stride, frame_stride, h->cfg.max_batch);
+  if (rc) return rc;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HIP_TRY(h, hipSetDevice(h->device));
+  g_device_clock.mark(1);
+  hipStream_t s = stream_or(h, stream);
+  // round-robin slots, ordered on the device (no host wait): consecutive
+  // calls on different streams run concurrently.  Device calls take no
+  // ticket: a host batch in the same slot keeps its ticket and completion.
+  const int k = slot && *slot >= 0 ? *slot : (int)(h->device_calls++ % h->slots.size());
+  if (slot) *slot = k;
+  Slot& sl = h->slots[k];
+  if ((rc = claim_slot(h, sl, s))) return rc;
+  g_device_clock.mark(2);
+  rc = forward(h, k, d_frames, n, height, width, channels, row_stride, frame_stride, d_masks, s);
+  const int rr = release_slot(h, sl, s);  // also after a failed enqueue: the next user orders after it
+  g_device_clock.mark(7);
+  return rc ? rc : rr;
+}
 
 extern "C" {
 
@@ -2351,38 +2143,6 @@ int vss_host_free(void* ptr) {
   return hipHostFree(ptr) == hipSuccess ? VSS_OK : VSS_E_HIP;
 }
 
-// vss_segment_device; slot != null: *slot < 0 takes the next slot of the
-// round-robin and returns it, *slot >= 0 runs on that slot (a caller that keeps
-// one buffer pair, vss_video, stays on one slot's executable graph).
-// always_inline: vss_segment_device keeps a body of its own; as a call into a
-// shared function the bench line read 1.7 % lower in three alternating A/B
-// pairs against the parent.
-static inline int segment_device_on(vss_handle* h, int* slot, const uint8_t* d_frames, int n, int height, int width,
-                                    int channels, size_t row_stride, size_t frame_stride, float* d_masks,
-                                    void* stream) {
-  if (!h) return fail(nullptr, VSS_E_INVALID_ARG, "null handle");
-  if (!d_frames || !d_masks) return fail(h, VSS_E_INVALID_ARG, "null device pointer");
-  g_device_clock.begin();
-  int rc = check_frames(h, n, height, width, channels, row_stride, frame_stride, h->cfg.max_batch);
-  if (rc) return rc;
-  std::lock_guard<std::mutex> lk(h->mu);
-  HIP_TRY(h, hipSetDevice(h->device));
-  g_device_clock.mark(1);
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  // round-robin slots, ordered on the device (no host wait): consecutive
-  // calls on different streams run concurrently.  Device calls take no
-  // ticket: a host batch in the same slot keeps its ticket and completion.
-  const int k = slot && *slot >= 0 ? *slot : (int)(h->device_calls++ % h->slots.size());
-  if (slot) *slot = k;
-  Slot& sl = h->slots[k];
-  if ((rc = claim_slot(h, sl, s))) return rc;
-  g_device_clock.mark(2);
-  rc = forward(h, k, d_frames, n, height, width, channels, row_stride, frame_stride, d_masks, s);
-  const int rr = release_slot(h, sl, s);  // also after a failed enqueue: the next user orders after it
-  g_device_clock.mark(7);
-  return rc ? rc : rr;
-}
-
 int vss_segment_device(vss_handle* h, const uint8_t* d_frames, int n, int height, int width, int channels,
                        size_t row_stride, size_t frame_stride, float* d_masks, void* stream) {
   return segment_device_on(h, nullptr, d_frames, n, height, width, channels, row_stride, frame_stride, d_masks, stream);
@@ -2452,7 +2212,7 @@ int vss_segment_gather_device(vss_handle* h, const uint8_t* d_frames, int n, int
   if (rc) return rc;
   std::lock_guard<std::mutex> lk(h->mu);
   HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  hipStream_t s = stream_or(h, stream);
   // round-robin over the gather calls alone (a counter of their own), so every
   // rank uses the same slot's communicator for its i-th gather whatever other
   // device calls it interleaves
@@ -2505,7 +2265,7 @@ int vss_mask_to_frame_device(vss_handle* h, const float* d_masks, int n, int fra
   if (n < 1 || n > h->user_max_batch || frame_h < 1 || frame_w < 1)
     return fail(h, VSS_E_INVALID_ARG, "n must be 1..max_batch and the frame size positive");
   HIP_TRY(h, hipSetDevice(h->device));
-  enqueue_upmask(h, d_masks, n, frame_h, frame_w, d_out, stream ? static_cast<hipStream_t>(stream) : h->stream);
+  enqueue_upmask(h, d_masks, n, frame_h, frame_w, d_out, stream_or(h, stream));
   HIP_TRY(h, hipGetLastError());
   return VSS_OK;
 }
@@ -2517,7 +2277,7 @@ int vss_preprocess_device(vss_handle* h, const uint8_t* d_frames, int n, int hei
   int rc = check_frames(h, n, height, width, channels, row_stride, frame_stride, h->user_max_batch);
   if (rc) return rc;
   HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
+  hipStream_t s = stream_or(h, stream);
   PrepParams p{};
   p.frames = d_frames; p.row_stride = (long)row_stride; p.frame_stride = (long)frame_stride;
   p.fh = height; p.fw = width; p.fc = channels; p.Hm = h->cfg.model_h; p.Wm = h->cfg.model_w;
@@ -2798,136 +2558,13 @@ int vss_profile_read(vss_handle* h, double* ms_per_layer, int cap, int* count) {
 
 }  // extern "C"
 
-// ---- post-processing chain (vss_post.hip) ----------------------------------
-struct vss_post_state {
-  vss_handle* h = nullptr;
-  vss_post_config cfg{};
-  float* state = nullptr;   // [P] prevAlpha
-  int* valid = nullptr;     // device flag: 0 before the stream's first frame
-  float* ema = nullptr;     // [max_batch][P]
-  float* state2 = nullptr;  // [P] the other prevAlpha buffer (the stabilised EMA reads one, writes the other)
-  FaceFrame* d_faces = nullptr;       // [max_batch] face inputs set by vss_post_set_faces
-  const FaceFrame* faces = nullptr;   // the next call's face inputs (d_faces or a caller's device array)
-  int faces_n = 0;                    // ... for this many frames (0: none)
-  double* rtab = nullptr;   // exp(-r / (2 sigma_r^2)), r in [0, 3*255^2]
-  double sw[3] = {0, 0, 0};
-  double tab_sigma = -1.0;
-  std::string err;
-};
-
-namespace {
-
-constexpr int kRangeTab = 3 * 255 * 255 + 1;
-
-int post_fail(vss_post_state* st, int code, const std::string& msg) {
-  st->err = msg;
-  if (st->h) set_err(st->h, msg);
-  return code;
-}
-
-// Bilateral weights as the reference computes them (Math.exp of the same
-// double quotients); built on the host so they are the exact doubles the
-// oracle's libm produces.
-// sw and (when sigma_range changed: *tab_sigma) the device table rtab; false: the upload failed
-bool post_tables_for(const vss_post_config& c, double* sw, double* rtab, double* tab_sigma) {
-  const double ts2 = 2.0 * c.sigma_spatial * c.sigma_spatial, tr2 = 2.0 * c.sigma_range * c.sigma_range;
-  for (int k = 0; k < 3; ++k) sw[k] = std::exp(-(double)k / ts2);
-  if (*tab_sigma != c.sigma_range) {
-    std::vector<double> t(kRangeTab);
-    for (int r = 0; r < kRangeTab; ++r) t[r] = std::exp(-(double)r / tr2);
-    if (hipMemcpy(rtab, t.data(), t.size() * 8, hipMemcpyHostToDevice) != hipSuccess) return false;
-    *tab_sigma = c.sigma_range;
-  }
-  return true;
-}
-
-int post_tables(vss_post_state* st) {
-  if (!post_tables_for(st->cfg, st->sw, st->rtab, &st->tab_sigma))
-    return post_fail(st, VSS_E_HIP, "post: table upload failed");
-  return VSS_OK;
-}
-
-// the filter's parameters that do not depend on where the EMA comes from
-void post_filter_params(PostFilterParams* pf, const vss_handle* h, const vss_post_config& c, const double* sw,
-                        const double* rtab, int fh, int fw, int fc, size_t rs, size_t fs) {
-  const int H = h->cfg.model_h, W = h->cfg.model_w;
-  pf->row_stride = (long)rs;
-  pf->frame_stride = (long)fs;
-  pf->fh = fh; pf->fw = fw; pf->fc = fc;
-  pf->ry = (float)((double)fh / (double)H);
-  pf->rx = (float)((double)fw / (double)W);
-  pf->H = H; pf->W = W;
-  pf->rtab = rtab;
-  for (int k = 0; k < 3; ++k) pf->sw[k] = sw[k];
-  pf->lo = c.noise_cutoff;
-  pf->hi = c.high_threshold;
-  pf->denom = std::max(1e-6, c.high_threshold - c.noise_cutoff);
-  pf->gamma = c.gamma;
-  pf->use_bilateral = c.use_bilateral;
-}
-
-int post_enqueue(vss_post_state* st, const uint8_t* d_frames, int n, int fh, int fw, int fc, size_t rs, size_t fs,
-                 const float* d_masks, float* d_alpha, uint8_t* d_u8, hipStream_t s) {
-  vss_handle* h = st->h;
-  const int H = h->cfg.model_h, W = h->cfg.model_w;
-  const FaceFrame* faces = nullptr;
-  if (st->faces_n) {
-    if (st->faces_n != n)
-      return post_fail(st, VSS_E_INVALID_ARG, "vss_post_set_faces was given " + std::to_string(st->faces_n) +
-                                                  " frames, this call has " + std::to_string(n));
-    faces = st->faces;
-    st->faces_n = 0;  // consumed
-    st->faces = nullptr;
-  }
-  if (faces) {
-    // the stabilised EMA, one frame at a time (the warp reads prevAlpha at other pixels)
-    for (int t = 0; t < n; ++t) {
-      PostFaceEmaParams pe{};
-      pe.mask = d_masks + (long)t * H * W;
-      pe.prev = st->state;
-      pe.next = st->state2;
-      pe.ema = st->ema + (long)t * H * W;
-      pe.valid = st->valid;
-      pe.first = t == 0;
-      pe.face = faces + t;
-      pe.H = H;
-      pe.W = W;
-      pe.a = st->cfg.ema;
-      launch_post_face_ema(pe, s);
-      std::swap(st->state, st->state2);
-    }
-  } else {
-    PostEmaParams pe{};
-    pe.masks = d_masks;
-    pe.ema = st->ema;
-    pe.state = st->state;
-    pe.valid = st->valid;
-    pe.n = n;
-    pe.P = (long)H * W;
-    pe.a = st->cfg.ema;
-    launch_post_ema(pe, s);
-  }
-  HIP_TRY(h, hipMemsetAsync(st->valid, 1, sizeof(int), s));  // the stream has seen its first frame
-  PostFilterParams pf{};
-  pf.faces = faces;
-  pf.ema = st->ema;
-  pf.frames = d_frames;
-  post_filter_params(&pf, h, st->cfg, st->sw, st->rtab, fh, fw, fc, rs, fs);
-  pf.alpha = d_alpha;
-  pf.alpha_u8 = d_u8;
-  launch_post_filter(pf, n, s);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return post_fail(st, VSS_E_HIP, std::string("post launch: ") + hipGetErrorString(e));
-  return VSS_OK;
-}
-
 // The seam for the synchronous post / composite host calls on engine 0:
 // stage the frames into a free slot, H2D and forward on the handle's stream
 // (after that slot's previous work); returns the slot, claimed and marked
 // host_busy — the caller enqueues its own work and ends with finish_seam.
 // mu held through lk (released only while waiting for a slot).
-int seam_on_stream(vss_handle* h, std::unique_lock<std::mutex>& lk, const uint8_t* frames, int n, int fh, int fw,
-                   int fc, size_t rs, int* slot) {
+int vss_engine::seam_on_stream(vss_handle* h, std::unique_lock<std::mutex>& lk, const uint8_t* frames, int n, int fh,
+                               int fw, int fc, size_t rs, int* slot) {
   if (!frames) return fail(h, VSS_E_INVALID_ARG, "null frames");
   int rc = check_frames(h, n, fh, fw, fc, rs, rs * (size_t)fh, h->cfg.max_batch);
   if (rc) return rc;
@@ -2956,7 +2593,7 @@ int seam_on_stream(vss_handle* h, std::unique_lock<std::mutex>& lk, const uint8_
 // End of a synchronous post / composite call on slot k (rc: its enqueue
 // status): record the slot's done event, wait for the handle's stream with mu
 // released, give the slot back.
-int finish_seam(vss_handle* h, std::unique_lock<std::mutex>& lk, int k, int rc) {
+int vss_engine::finish_seam(vss_handle* h, std::unique_lock<std::mutex>& lk, int k, int rc) {
   Slot& s = h->slots[k];
   const int rr = release_slot(h, s, h->stream);
   if (!rc) rc = rr;
@@ -2971,146 +2608,6 @@ int finish_seam(vss_handle* h, std::unique_lock<std::mutex>& lk, int k, int rc) 
   h->slot_cv.notify_all();
   return rc;
 }
-
-}  // namespace
-
-extern "C" {
-
-void vss_post_config_default(vss_post_config* c) {
-  if (!c) return;
-  c->ema = 0.55;
-  c->noise_cutoff = 0.06;
-  c->high_threshold = 0.95;
-  c->gamma = 0.4;
-  c->sigma_spatial = 1.0;
-  c->sigma_range = 12.0;
-  c->use_bilateral = 1;
-}
-
-int vss_post_create(vss_handle* h, const vss_post_config* cfg, vss_post_state** out) {
-  if (!h || !out) return fail(h, VSS_E_INVALID_ARG, "null handle/out");
-  *out = nullptr;
-  if (h->cfg.model_h < 3 || h->cfg.model_w < 3) return fail(h, VSS_E_UNSUPPORTED, "mask too small for post");
-  vss_post_state* st = new vss_post_state();
-  st->h = h;
-  if (cfg) st->cfg = *cfg;
-  else vss_post_config_default(&st->cfg);
-  const size_t P = (size_t)h->cfg.model_h * h->cfg.model_w;
-  const size_t nb = (size_t)std::max(h->cfg.max_batch, h->user_max_batch);
-  auto bail = [&](int rc) {
-    vss_post_destroy(st);
-    return rc;
-  };
-  HIP_TRY(h, hipSetDevice(h->device));
-  if (hipMalloc(&st->state, P * 4) != hipSuccess || hipMalloc(&st->valid, 16) != hipSuccess ||
-      hipMalloc(&st->ema, P * 4 * nb) != hipSuccess || hipMalloc(&st->state2, P * 4) != hipSuccess ||
-      hipMalloc(&st->d_faces, sizeof(FaceFrame) * nb) != hipSuccess ||
-      hipMalloc(&st->rtab, (size_t)kRangeTab * 8) != hipSuccess)
-    return bail(fail(h, VSS_E_OOM, "post: hipMalloc failed"));
-  if (hipMemset(st->valid, 0, 16) != hipSuccess || hipMemset(st->state, 0, P * 4) != hipSuccess)
-    return bail(fail(h, VSS_E_HIP, "post: hipMemset failed"));
-  int rc = post_tables(st);
-  if (rc) return bail(rc);
-  *out = st;
-  return VSS_OK;
-}
-
-void vss_post_destroy(vss_post_state* st) {
-  if (!st) return;
-  if (st->h) {
-    (void)hipSetDevice(st->h->device);
-    (void)hipDeviceSynchronize();
-  }
-  if (st->state) (void)hipFree(st->state);
-  if (st->valid) (void)hipFree(st->valid);
-  if (st->ema) (void)hipFree(st->ema);
-  if (st->state2) (void)hipFree(st->state2);
-  if (st->d_faces) (void)hipFree(st->d_faces);
-  if (st->rtab) (void)hipFree(st->rtab);
-  delete st;
-}
-
-int vss_post_reset(vss_post_state* st) {
-  if (!st) return VSS_E_INVALID_ARG;
-  HIP_TRY(st->h, hipSetDevice(st->h->device));
-  HIP_TRY(st->h, hipDeviceSynchronize());
-  HIP_TRY(st->h, hipMemset(st->valid, 0, sizeof(int)));
-  st->faces_n = 0;
-  st->faces = nullptr;
-  return VSS_OK;
-}
-
-static_assert(sizeof(FaceFrame) == sizeof(vss_face_frame), "FaceFrame mirrors vss_face_frame");
-
-int vss_post_set_faces(vss_post_state* st, const vss_face_frame* faces, int n) {
-  if (!st) return VSS_E_INVALID_ARG;
-  if (!faces || n < 1 || n > std::max(st->h->cfg.max_batch, st->h->user_max_batch))
-    return post_fail(st, VSS_E_INVALID_ARG, "faces: 1..max_batch frames");
-  HIP_TRY(st->h, hipSetDevice(st->h->device));
-  HIP_TRY(st->h, hipMemcpyAsync(st->d_faces, faces, sizeof(FaceFrame) * n, hipMemcpyHostToDevice, st->h->stream));
-  HIP_TRY(st->h, hipStreamSynchronize(st->h->stream));  // consumers may run on any stream
-  st->faces = st->d_faces;
-  st->faces_n = n;
-  return VSS_OK;
-}
-
-int vss_post_set_faces_device(vss_post_state* st, const vss_face_frame* d_faces, int n) {
-  if (!st) return VSS_E_INVALID_ARG;
-  if (!d_faces || n < 1 || n > std::max(st->h->cfg.max_batch, st->h->user_max_batch))
-    return post_fail(st, VSS_E_INVALID_ARG, "faces: a device array of 1..max_batch frames");
-  st->faces = reinterpret_cast<const FaceFrame*>(d_faces);
-  st->faces_n = n;
-  return VSS_OK;
-}
-
-int vss_post_set_config(vss_post_state* st, const vss_post_config* cfg) {
-  if (!st || !cfg) return VSS_E_INVALID_ARG;
-  if (cfg->sigma_spatial <= 0 || cfg->sigma_range <= 0) return post_fail(st, VSS_E_INVALID_ARG, "sigmas must be > 0");
-  HIP_TRY(st->h, hipSetDevice(st->h->device));
-  HIP_TRY(st->h, hipDeviceSynchronize());
-  st->cfg = *cfg;
-  return post_tables(st);
-}
-
-int vss_postprocess_device(vss_post_state* st, const uint8_t* d_frames, int n, int height, int width, int channels,
-                           size_t row_stride, size_t frame_stride, const float* d_masks, float* d_alpha,
-                           uint8_t* d_alpha_u8, void* stream) {
-  if (!st) return fail(nullptr, VSS_E_INVALID_ARG, "null post state");
-  vss_handle* h = st->h;
-  if (!d_masks || (!d_frames && st->cfg.use_bilateral)) return fail(h, VSS_E_INVALID_ARG, "null device pointer");
-  int rc = check_frames(h, n, height, width, channels, row_stride, frame_stride,
-                        std::max(h->cfg.max_batch, h->user_max_batch));
-  if (rc) return rc;
-  HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  return post_enqueue(st, d_frames, n, height, width, channels, row_stride, frame_stride, d_masks, d_alpha,
-                      d_alpha_u8, s);
-}
-
-int vss_segment_post(vss_handle* h, vss_post_state* st, const uint8_t* frames, int n, int height, int width,
-                     int channels, size_t row_stride, float* alpha_out, uint8_t* alpha_u8_out) {
-  if (!h || !st || st->h != h) return fail(h, VSS_E_INVALID_ARG, "handle / post state mismatch");
-  if (!alpha_out && !alpha_u8_out) return fail(h, VSS_E_INVALID_ARG, "no output requested");
-  std::lock_guard<std::mutex> pl(h->post_mu);
-  std::unique_lock<std::mutex> lk(h->mu);
-  int k = 0;
-  int rc = seam_on_stream(h, lk, frames, n, height, width, channels, row_stride, &k);
-  if (rc) return rc;
-  Slot& s = h->slots[k];
-  const size_t P = (size_t)h->cfg.model_h * h->cfg.model_w;
-  float* d_alpha = alpha_out ? h->d_post_alpha : nullptr;
-  uint8_t* d_u8 = alpha_u8_out ? h->d_post_u8 : nullptr;
-  rc = post_enqueue(st, s.d_frames, n, height, width, channels, row_stride, row_stride * (size_t)height, s.d_masks,
-                    d_alpha, d_u8, h->stream);
-  hipError_t e = hipSuccess;
-  if (!rc && alpha_out) e = hipMemcpyAsync(alpha_out, d_alpha, (size_t)n * P * 4, hipMemcpyDeviceToHost, h->stream);
-  if (!rc && e == hipSuccess && alpha_u8_out)
-    e = hipMemcpyAsync(alpha_u8_out, d_u8, (size_t)n * P, hipMemcpyDeviceToHost, h->stream);
-  if (!rc && e != hipSuccess) rc = fail(h, VSS_E_HIP, std::string("D2H: ") + hipGetErrorString(e));
-  return finish_seam(h, lk, k, rc);
-}
-
-}  // extern "C"
 
 #ifdef VSS_TRACE
 // Trace build only: the stamps of `layer`'s last launch, [wgs][16] u64
@@ -3132,1229 +2629,6 @@ extern "C" int vss_trace_read(vss_handle* h, int layer, unsigned long long* out,
   return vss_trace_read_slot(h, h->last_slot, layer, out, cap);
 }
 #endif
-
-// ---- compositing (vss_post.hip k_composite) ---------------------------------
-namespace {
-
-int composite_enqueue(vss_handle* h, const uint8_t* d_frames, int n, int fh, int fw, int fc, size_t rs, size_t fs,
-                      const uint8_t* d_alpha, uint8_t* d_out, size_t ors, size_t ofs, hipStream_t s) {
-  CompositeParams p{};
-  p.frames = d_frames;
-  p.row_stride = (long)rs;
-  p.frame_stride = (long)fs;
-  p.fh = fh; p.fw = fw; p.fc = fc;
-  p.alpha = d_alpha;
-  p.H = h->cfg.model_h; p.W = h->cfg.model_w;
-  p.sy = (float)p.H / (float)fh;
-  p.sx = (float)p.W / (float)fw;
-  p.out = d_out;
-  p.out_row_stride = (long)ors;
-  p.out_frame_stride = (long)ofs;
-  launch_composite(p, n, s);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, VSS_E_HIP, std::string("composite launch: ") + hipGetErrorString(e));
-  return VSS_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int vss_composite_device(vss_handle* h, const uint8_t* d_frames, int n, int height, int width, int channels,
-                         size_t row_stride, size_t frame_stride, const uint8_t* d_alpha_u8, uint8_t* d_out_rgba,
-                         size_t out_row_stride, size_t out_frame_stride, void* stream) {
-  if (!h) return fail(nullptr, VSS_E_INVALID_ARG, "null handle");
-  if (!d_frames || !d_alpha_u8 || !d_out_rgba) return fail(h, VSS_E_INVALID_ARG, "null device pointer");
-  int rc = check_frames(h, n, height, width, channels, row_stride, frame_stride,
-                        std::max(h->cfg.max_batch, h->user_max_batch));
-  if (rc) return rc;
-  if (out_row_stride < (size_t)width * 4 || out_row_stride % 4 || out_frame_stride < out_row_stride * height ||
-      (reinterpret_cast<uintptr_t>(d_out_rgba) & 3))
-    return fail(h, VSS_E_INVALID_ARG, "bad RGBA output geometry (row stride >= 4*width, multiple of 4)");
-  HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  return composite_enqueue(h, d_frames, n, height, width, channels, row_stride, frame_stride, d_alpha_u8,
-                           d_out_rgba, out_row_stride, out_frame_stride, s);
-}
-
-int vss_segment_composite(vss_handle* h, vss_post_state* st, const uint8_t* frames, int n, int height, int width,
-                          int channels, size_t row_stride, uint8_t* out_rgba) {
-  if (!h || !st || st->h != h) return fail(h, VSS_E_INVALID_ARG, "handle / post state mismatch");
-  if (!out_rgba) return fail(h, VSS_E_INVALID_ARG, "null output");
-  std::lock_guard<std::mutex> pl(h->post_mu);
-  std::unique_lock<std::mutex> lk(h->mu);
-  HIP_TRY(h, hipSetDevice(h->device));
-  const size_t cap = (size_t)h->cfg.max_batch * h->cfg.max_frame_h * h->cfg.max_frame_w * 4;
-  if (!h->d_comp) {
-    int rc = dalloc(h, &h->d_comp, cap);
-    if (rc) return rc;
-  }
-  const size_t fs = row_stride * (size_t)height, ors = (size_t)width * 4, ofs = ors * height;
-  if ((size_t)n * ofs > cap)
-    return fail(h, VSS_E_INVALID_ARG, "RGBA output exceeds the handle's capacity (max_batch, max_frame_h/w)");
-  int k = 0;
-  int rc = seam_on_stream(h, lk, frames, n, height, width, channels, row_stride, &k);
-  if (rc) return rc;
-  Slot& s = h->slots[k];
-  rc = post_enqueue(st, s.d_frames, n, height, width, channels, row_stride, fs, s.d_masks, nullptr, h->d_post_u8,
-                    h->stream);
-  if (!rc)
-    rc = composite_enqueue(h, s.d_frames, n, height, width, channels, row_stride, fs, h->d_post_u8, h->d_comp, ors,
-                           ofs, h->stream);
-  if (!rc) {
-    const hipError_t e = hipMemcpyAsync(out_rgba, h->d_comp, (size_t)n * ofs, hipMemcpyDeviceToHost, h->stream);
-    if (e != hipSuccess) rc = fail(h, VSS_E_HIP, std::string("D2H: ") + hipGetErrorString(e));
-  }
-  return finish_seam(h, lk, k, rc);
-}
-
-}  // extern "C"
-
-// ---- virtual backgrounds (vss_background.hip) --------------------------------
-struct vss_background {
-  vss_handle* h = nullptr;
-  std::mutex mu;                 // setters and composites of one object are serialised
-  int mode = VSS_BG_COLOR;
-  uint32_t color = 32u | (32u << 8) | (32u << 16);  // u2FrameProc.ts:89
-  uint8_t* d_src = nullptr;      // IMAGE: the user's image [sh][sw][sc], tight rows
-  int sh = 0, sw = 0, sc = 0;
-  size_t src_bytes = 0;
-  uint8_t* d_img = nullptr;      // IMAGE: d_src scaled to img_fh x img_fw (0: not built)
-  int img_fh = 0, img_fw = 0;
-  size_t img_bytes = 0;
-  uint32_t* d_hblur = nullptr;   // BLUR: the horizontal pass's output, grown on demand
-  size_t hblur_bytes = 0;
-  int radius = 0;
-  uint16_t w[kBlurMaxRadius + 1] = {};  // taps 0 (centre) .. radius
-  int refine_radius = 0;         // the edge-aware matte: 0 = off
-  double refine_eps = 0.0;
-  uint8_t* d_matte = nullptr;    // its planes for n frames: (abar, bbar), (a_q, b_q), L; grown on demand
-  size_t matte_bytes = 0;
-  // branding layers (include/vss_layers.h)
-  struct Layer {
-    vss_layer l;                 // pixels = null: the sprite lives in d_sprites
-    size_t sprite_off;           // IMAGE: byte offset of its premultiplied copy
-  };
-  std::vector<Layer> layers;
-  int canvas_w = 1920, canvas_h = 1080;  // customization.ts:37
-  int level = 2;                 // 'medium', customization.ts:28
-  uint8_t* d_sprites = nullptr;  // every IMAGE layer's sprite, premultiplied RGBA, tight rows
-  size_t sprites_bytes = 0;
-  uint32_t* d_plate = nullptr;   // the overlay O at plate_fh x plate_fw (0: not built), rows of layer_pitch dwords
-  int plate_fh = 0, plate_fw = 0;
-  size_t plate_bytes = 0;
-  uint8_t* d_shadow = nullptr;   // the shadows' two u8 planes, [2][fh][layer_pitch]
-  size_t shadow_bytes = 0;
-  int img_mode = -1;             // what d_img holds: the mode it was built for,
-  bool img_layered = false;      // whether O is baked into it,
-  uint32_t img_color = 0;        // and (COLOR) from which colour
-  bool img_for_image = false;    // d_img has served image mode (else it exists for a colour under layers only)
-  hipEvent_t last = nullptr;     // recorded after every composite
-  hipStream_t last_stream = nullptr;
-  bool used = false;
-};
-
-namespace {
-
-// w[0..2r]: 16-bit fixed-point Gaussian taps that sum to 65536 exactly
-int blur_weights(int radius, double sigma, uint16_t* w, std::string* why) {
-  if (radius < 1 || radius > kBlurMaxRadius) {
-    *why = "blur radius must be in [1, 32]";
-    return VSS_E_INVALID_ARG;
-  }
-  if (!(sigma > 0.0) || std::isinf(sigma)) {
-    *why = "blur sigma must be a finite number > 0";
-    return VSS_E_INVALID_ARG;
-  }
-  double g[2 * kBlurMaxRadius + 1], sum = 0.0;
-  for (int k = -radius; k <= radius; ++k) sum += g[k + radius] = std::exp(-(double)(k * k) / (2.0 * sigma * sigma));
-  long rest = 0;
-  for (int k = 0; k <= 2 * radius; ++k) {
-    if (k == radius) continue;
-    const long v = (long)std::floor(65536.0 * g[k] / sum + 0.5);
-    w[k] = (uint16_t)v;
-    rest += v;
-  }
-  if (rest == 0) {  // the centre tap would be 65536: no u16, and no blur
-    *why = "blur sigma too small: every off-centre 16-bit weight rounds to 0";
-    return VSS_E_INVALID_ARG;
-  }
-  // The centre takes what the rounded taps leave.  With a wide sigma the 2r
-  // rounding errors can add up to more than the table's own slope at the
-  // centre (radius 32, sigma 40: 1116 left between two taps of 1120), and the
-  // kernel would dip at its peak.  Then the m innermost tap pairs give one
-  // unit each to the centre, m the smallest count that leaves the table
-  // non-increasing from the centre outwards; no tap moves by more than 1.
-  long centre = 65536 - rest;
-  if (centre < w[radius + 1]) {
-    const long first = w[radius + 1];
-    int m = 0;
-    for (int k = 1; k <= radius && !m; ++k)
-      if (centre + 2 * k >= first - 1 && (k == radius || w[radius + k] - 1 >= w[radius + k + 1])) m = k;
-    for (int k = 1; k <= m; ++k) {
-      --w[radius + k];
-      --w[radius - k];
-    }
-    centre += 2 * m;
-  }
-  w[radius] = (uint16_t)centre;
-  return VSS_OK;
-}
-
-// (re)allocate one device buffer of a background or video object to `bytes`
-// (0: free it); these buffers count into vss_info.device_bytes
-template <class T>
-int counted_alloc(vss_handle* h, T** p, size_t* have, size_t bytes) {
-  if (*p) {
-    (void)hipFree(*p);
-    h->bg_bytes -= *have;
-    *p = nullptr;
-    *have = 0;
-  }
-  if (!bytes) return VSS_OK;
-  void* q = nullptr;
-  if (hipMalloc(&q, bytes) != hipSuccess) return fail(h, VSS_E_OOM, "hipMalloc(" + std::to_string(bytes) + ") failed");
-  *p = static_cast<T*>(q);
-  *have = bytes;
-  h->bg_bytes += bytes;
-  return VSS_OK;
-}
-
-template <class T>
-int bg_alloc(vss_background* bg, T** p, size_t* have, size_t bytes) {
-  return counted_alloc(bg->h, p, have, bytes);
-}
-
-// before a device buffer of bg is freed or overwritten: its latest composite has ended
-int bg_quiesce(vss_background* bg) {
-  HIP_TRY(bg->h, hipSetDevice(bg->h->device));
-  if (bg->used) HIP_TRY(bg->h, hipEventSynchronize(bg->last));
-  return VSS_OK;
-}
-
-// bg->mu held.  The matte's mask-resolution stage for these frames (refinement
-// on): *ab = the (abar, bbar) plane the frame-resolution kernels apply.
-int matte_enqueue(vss_handle* h, vss_background* bg, const uint8_t* d_frames, int n, int fh, int fw, int fc, size_t rs,
-                  size_t fs, const uint8_t* d_alpha, int H, int W, hipStream_t s, const float2** ab) {
-  if (fh < H || fw < W)
-    return fail(h, VSS_E_INVALID_ARG, "refinement needs a frame no smaller than the mask (" + std::to_string(H) +
-                                          " x " + std::to_string(W) + "); turn it off for smaller frames");
-  if (W > 16384) return fail(h, VSS_E_INVALID_ARG, "refinement: mask wider than 16384");
-  const size_t px = (size_t)n * H * W, need = px * 17;  // float2 + int2 + u8 per mask pixel
-  if (need > bg->matte_bytes) {
-    int rc = bg_quiesce(bg);
-    if (!rc) rc = bg_alloc(bg, &bg->d_matte, &bg->matte_bytes, need);
-    if (rc) return rc;
-  }
-  MatteParams m{};
-  m.frames = d_frames;
-  m.row_stride = (long)rs;
-  m.frame_stride = (long)fs;
-  m.fh = fh; m.fw = fw; m.fc = fc;
-  m.alpha = d_alpha;
-  m.H = H; m.W = W;
-  m.radius = bg->refine_radius;
-  m.eps = bg->refine_eps;
-  m.ab = reinterpret_cast<float2*>(bg->d_matte);
-  m.q = reinterpret_cast<int2*>(bg->d_matte + px * 8);
-  m.L = bg->d_matte + px * 16;
-  launch_matte_stage(m, n, s);
-  *ab = m.ab;
-  return VSS_OK;
-}
-
-// map(v, canvas, frame) of include/vss_layers.h: round half up with true floor division
-long layers_map(long v, long canvas, long frame) {
-  const long num = 2 * v * frame + canvas, den = 2 * canvas;
-  long q = num / den;
-  if (num % den < 0) --q;
-  return q;
-}
-
-bool layers_visible(const vss_background* bg) {
-  for (const auto& L : bg->layers)
-    if (L.l.privacy <= bg->level) return true;
-  return false;
-}
-
-int clip(long v, int hi) { return (int)std::min<long>(std::max<long>(v, 0), hi); }
-
-// bg->mu held; some layer is visible.  The overlay plate O for a frame fh x fw,
-// rebuilt on s when the layers, the level or the frame size changed.
-int plate_enqueue(vss_handle* h, vss_background* bg, int fh, int fw, hipStream_t s) {
-  if (bg->plate_fh == fh && bg->plate_fw == fw) return VSS_OK;
-  const int pitch = layer_pitch(fw);
-  const size_t need = (size_t)pitch * fh * 4;
-  bool shadows = false;
-  for (const auto& L : bg->layers) shadows |= L.l.privacy <= bg->level && L.l.has_shadow;
-  const size_t need_sh = shadows ? (size_t)pitch * fh * 2 : 0;
-  if (need > bg->plate_bytes || need_sh > bg->shadow_bytes) {
-    int rc = bg_quiesce(bg);
-    if (!rc && need > bg->plate_bytes) rc = bg_alloc(bg, &bg->d_plate, &bg->plate_bytes, need);
-    if (!rc && need_sh > bg->shadow_bytes) rc = bg_alloc(bg, &bg->d_shadow, &bg->shadow_bytes, need_sh);
-    if (rc) return rc;
-  }
-  bg->plate_fh = bg->plate_fw = 0;
-  HIP_TRY(h, hipMemsetAsync(bg->d_plate, 0, need, s));
-  const long cw = bg->canvas_w, ch = bg->canvas_h;
-  for (const auto& L : bg->layers) {
-    const vss_layer& l = L.l;
-    if (l.privacy > bg->level) continue;
-    LayerGeom g{};
-    g.type = l.type;
-    g.X0 = layers_map(l.x, cw, fw);
-    g.X1 = layers_map((long)l.x + l.width, cw, fw);
-    g.Y0 = layers_map(l.y, ch, fh);
-    g.Y1 = layers_map((long)l.y + l.height, ch, fh);
-    if (g.X1 <= g.X0 || g.Y1 <= g.Y0) continue;
-    if (l.type == VSS_LAYER_ROUNDED_RECT) {
-      g.R = std::min(layers_map(l.radius, cw, fw), std::min((g.X1 - g.X0) / 2, (g.Y1 - g.Y0) / 2));
-      g.color = (uint32_t)l.color[0] | ((uint32_t)l.color[1] << 8) | ((uint32_t)l.color[2] << 16) |
-                ((uint32_t)l.color[3] << 24);
-    } else {
-      g.sprite = bg->d_sprites + L.sprite_off;
-      g.sh = l.src_h; g.sw = l.src_w;
-      g.sy = (float)l.src_h / (float)(g.Y1 - g.Y0);
-      g.sx = (float)l.src_w / (float)(g.X1 - g.X0);
-    }
-    if (l.has_shadow) {
-      ShadowParams sp{};
-      sp.g = g;
-      sp.dx = layers_map(l.shadow_dx, cw, fw);
-      sp.dy = layers_map(l.shadow_dy, ch, fh);
-      const double sigma = (double)l.shadow_blur * (double)fw / (2.0 * (double)cw);
-      int r = 3.0 * sigma >= (double)kBlurMaxRadius ? kBlurMaxRadius : (int)std::ceil(3.0 * sigma);
-      uint16_t w[2 * kBlurMaxRadius + 1];
-      std::string why;
-      if (r < 1 || blur_weights(r, sigma, w, &why)) r = 0;  // B = P
-      for (int k = 0; k <= r; ++k) sp.w[k] = w[r + k];
-      sp.radius = r;
-      sp.x0 = clip(g.X0 + sp.dx - r, fw); sp.x1 = clip(g.X1 + sp.dx + r, fw);
-      sp.y0 = clip(g.Y0 + sp.dy - r, fh); sp.y1 = clip(g.Y1 + sp.dy + r, fh);
-      sp.P = bg->d_shadow;
-      sp.Hb = bg->d_shadow + (size_t)pitch * fh;
-      sp.pitch = pitch;
-      sp.color = (uint32_t)l.shadow_color[0] | ((uint32_t)l.shadow_color[1] << 8) |
-                 ((uint32_t)l.shadow_color[2] << 16) | ((uint32_t)l.shadow_color[3] << 24);
-      sp.plate = bg->d_plate;
-      launch_layer_shadow(sp, s);
-    }
-    LayerDrawParams d{};
-    d.g = g;
-    d.x0 = clip(g.X0, fw); d.x1 = clip(g.X1, fw);
-    d.y0 = clip(g.Y0, fh); d.y1 = clip(g.Y1, fh);
-    d.plate = bg->d_plate;
-    d.pitch = pitch;
-    launch_layer_draw(d, s);
-  }
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, VSS_E_HIP, std::string("layer launch: ") + hipGetErrorString(e));
-  bg->plate_fh = fh;
-  bg->plate_fw = fw;
-  return VSS_OK;
-}
-
-void composite_params(CompositeParams* c, const uint8_t* d_frames, int fh, int fw, int fc, size_t rs, size_t fs,
-                      const uint8_t* d_alpha, int H, int W, uint8_t* d_out, size_t ors, size_t ofs) {
-  c->frames = d_frames;
-  c->row_stride = (long)rs;
-  c->frame_stride = (long)fs;
-  c->fh = fh; c->fw = fw; c->fc = fc;
-  c->alpha = d_alpha;
-  c->H = H; c->W = W;
-  c->sy = (float)c->H / (float)fh;
-  c->sx = (float)c->W / (float)fw;
-  c->out = d_out;
-  c->out_row_stride = (long)ors;
-  c->out_frame_stride = (long)ofs;
-}
-
-// bg->mu held
-int bg_enqueue(vss_handle* h, vss_background* bg, const uint8_t* d_frames, int n, int fh, int fw, int fc, size_t rs,
-               size_t fs, const uint8_t* d_alpha, uint8_t* d_out, size_t ors, size_t ofs, hipStream_t s) {
-  if (bg->mode == VSS_BG_IMAGE && !bg->d_src)
-    return fail(h, VSS_E_INVALID_ARG, "background is in image mode but no image was set");
-  if (bg->mode == VSS_BG_BLUR && !bg->radius)
-    return fail(h, VSS_E_INVALID_ARG, "background is in blur mode but no blur was set");
-  // the previous composite (and the image it may have scaled) ran on another stream
-  if (bg->used && bg->last_stream != s) HIP_TRY(h, hipStreamWaitEvent(s, bg->last, 0));
-  BgCompositeParams p{};
-  composite_params(&p.c, d_frames, fh, fw, fc, rs, fs, d_alpha, h->cfg.model_h, h->cfg.model_w, d_out, ors, ofs);
-  p.color = bg->color;
-  if (bg->refine_radius) {
-    const int rc = matte_enqueue(h, bg, d_frames, n, fh, fw, fc, rs, fs, d_alpha, p.c.H, p.c.W, s, &p.ab);
-    if (rc) return rc;
-  }
-  // branding layers: the overlay plate O, rebuilt here (outside anything captured or replayed) when it is stale
-  const bool layered = layers_visible(bg);
-  if (layered) {
-    const int rc = plate_enqueue(h, bg, fh, fw, s);
-    if (rc) return rc;
-  }
-  int mode = bg->mode;
-  if (mode == VSS_BG_IMAGE || (mode == VSS_BG_COLOR && layered)) {
-    // the cached plate: the scaled image, or with layers bg' = O over the image or the colour
-    if (bg->img_fh != fh || bg->img_fw != fw || bg->img_mode != mode || bg->img_layered != layered ||
-        (mode == VSS_BG_COLOR && bg->img_color != bg->color)) {
-      const size_t need = (size_t)bg_image_stride(fw) * fh;
-      if (need > bg->img_bytes) {
-        int rc = bg_quiesce(bg);
-        if (!rc) rc = bg_alloc(bg, &bg->d_img, &bg->img_bytes, need);
-        if (rc) return rc;
-      }
-      bg->img_fh = bg->img_fw = 0;
-      if (mode == VSS_BG_IMAGE) {
-        BgResizeParams r{};
-        r.src = bg->d_src;
-        r.sh = bg->sh; r.sw = bg->sw; r.sc = bg->sc;
-        r.sy = (float)bg->sh / (float)fh;
-        r.sx = (float)bg->sw / (float)fw;
-        r.out = bg->d_img;
-        r.fh = fh; r.fw = fw;
-        launch_bg_resize(r, s);
-        bg->img_for_image = true;
-      }
-      if (layered) {
-        BgBakeParams b{};
-        b.image = bg->d_img;
-        b.overlay = bg->d_plate;
-        b.fh = fh; b.fw = fw;
-        b.from_color = mode == VSS_BG_COLOR;
-        b.color = bg->color;
-        launch_bg_bake(b, s);
-      }
-      bg->img_fh = fh;
-      bg->img_fw = fw;
-      bg->img_mode = mode;
-      bg->img_layered = layered;
-      bg->img_color = bg->color;
-    }
-    p.image = bg->d_img;
-    mode = VSS_BG_IMAGE;  // a colour under layers is a plate too
-  } else if (bg->mode == VSS_BG_BLUR) {
-    if (layered) p.overlay = bg->d_plate;
-    const size_t need = (size_t)n * fh * fw * 4;
-    if (need > bg->hblur_bytes) {
-      int rc = bg_quiesce(bg);
-      if (!rc) rc = bg_alloc(bg, &bg->d_hblur, &bg->hblur_bytes, need);
-      if (rc) return rc;
-    }
-    BlurHParams b{};
-    b.frames = d_frames;
-    b.row_stride = (long)rs;
-    b.frame_stride = (long)fs;
-    b.fh = fh; b.fw = fw; b.fc = fc;
-    b.out = bg->d_hblur;
-    b.radius = bg->radius;
-    std::copy(bg->w, bg->w + kBlurMaxRadius + 1, b.w);
-    launch_blur_h(b, n, s);
-    p.hblur = bg->d_hblur;
-    p.radius = bg->radius;
-    std::copy(bg->w, bg->w + kBlurMaxRadius + 1, p.w);
-  }
-  launch_bg_composite(p, mode, n, s);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, VSS_E_HIP, std::string("background launch: ") + hipGetErrorString(e));
-  HIP_TRY(h, hipEventRecord(bg->last, s));
-  bg->last_stream = s;
-  bg->used = true;
-  return VSS_OK;
-}
-
-}  // namespace
-
-static_assert(VSS_BG_COLOR == kBgColor && VSS_BG_IMAGE == kBgImage && VSS_BG_BLUR == kBgBlur, "modes mirror vss.h");
-static_assert(VSS_LAYER_IMAGE == kLayerImage && VSS_LAYER_ROUNDED_RECT == kLayerRect, "layer types mirror vss_layers.h");
-
-extern "C" {
-
-int vss_blur_weights(int radius, double sigma, uint16_t* w) {
-  if (!w) return fail(nullptr, VSS_E_INVALID_ARG, "null weights");
-  std::string why;
-  const int rc = blur_weights(radius, sigma, w, &why);
-  return rc ? fail(nullptr, rc, why) : VSS_OK;
-}
-
-int vss_background_create(vss_handle* h, vss_background** out) {
-  if (!h || !out) return fail(h, VSS_E_INVALID_ARG, "null handle/out");
-  *out = nullptr;
-  HIP_TRY(h, hipSetDevice(h->device));
-  vss_background* bg = new vss_background();
-  bg->h = h;
-  const hipError_t e = hipEventCreateWithFlags(&bg->last, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    delete bg;
-    return fail(h, VSS_E_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
-  }
-  *out = bg;
-  return VSS_OK;
-}
-
-void vss_background_destroy(vss_background* bg) {
-  if (!bg) return;
-  (void)bg_quiesce(bg);
-  (void)bg_alloc(bg, &bg->d_src, &bg->src_bytes, 0);
-  (void)bg_alloc(bg, &bg->d_img, &bg->img_bytes, 0);
-  (void)bg_alloc(bg, &bg->d_hblur, &bg->hblur_bytes, 0);
-  (void)bg_alloc(bg, &bg->d_matte, &bg->matte_bytes, 0);
-  (void)bg_alloc(bg, &bg->d_sprites, &bg->sprites_bytes, 0);
-  (void)bg_alloc(bg, &bg->d_plate, &bg->plate_bytes, 0);
-  (void)bg_alloc(bg, &bg->d_shadow, &bg->shadow_bytes, 0);
-  if (bg->last) (void)hipEventDestroy(bg->last);
-  delete bg;
-}
-
-int vss_background_set_color(vss_background* bg, int r, int g, int b) {
-  if (!bg) return fail(nullptr, VSS_E_INVALID_ARG, "null background");
-  if (r < 0 || r > 255 || g < 0 || g > 255 || b < 0 || b > 255)
-    return fail(bg->h, VSS_E_INVALID_ARG, "colour components must be in [0, 255]");
-  std::lock_guard<std::mutex> lk(bg->mu);
-  bg->color = (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)b << 16);
-  bg->mode = VSS_BG_COLOR;
-  return VSS_OK;
-}
-
-int vss_background_set_image(vss_background* bg, const uint8_t* pixels, int height, int width, int channels,
-                             size_t row_stride) {
-  if (!bg) return fail(nullptr, VSS_E_INVALID_ARG, "null background");
-  vss_handle* h = bg->h;
-  if (!pixels) return fail(h, VSS_E_INVALID_ARG, "null image");
-  if (height < 1 || width < 1) return fail(h, VSS_E_INVALID_ARG, "bad image size");
-  if (channels != 3 && channels != 4) return fail(h, VSS_E_INVALID_ARG, "image channels must be 3 or 4");
-  if (row_stride < (size_t)width * channels) return fail(h, VSS_E_INVALID_ARG, "row_stride < width*channels");
-  std::lock_guard<std::mutex> lk(bg->mu);
-  int rc = bg_quiesce(bg);  // a composite may still read the old image
-  if (rc) return rc;
-  const size_t rb = (size_t)width * channels;
-  if ((rc = bg_alloc(bg, &bg->d_src, &bg->src_bytes, rb * height))) {
-    bg->sh = bg->sw = bg->sc = 0;
-    return rc;
-  }
-  bg->img_fh = bg->img_fw = 0;  // the scaled copy is rebuilt by the next composite
-  const hipError_t e = hipMemcpy2D(bg->d_src, rb, pixels, row_stride, rb, height, hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    (void)bg_alloc(bg, &bg->d_src, &bg->src_bytes, 0);
-    return fail(h, VSS_E_HIP, std::string("image upload: ") + hipGetErrorString(e));
-  }
-  bg->sh = height; bg->sw = width; bg->sc = channels;
-  bg->mode = VSS_BG_IMAGE;
-  return VSS_OK;
-}
-
-int vss_background_set_mode(vss_background* bg, int mode) {
-  if (!bg) return fail(nullptr, VSS_E_INVALID_ARG, "null background");
-  if (mode != VSS_BG_COLOR && mode != VSS_BG_IMAGE && mode != VSS_BG_BLUR)
-    return fail(bg->h, VSS_E_INVALID_ARG, "mode must be VSS_BG_COLOR, VSS_BG_IMAGE or VSS_BG_BLUR");
-  std::lock_guard<std::mutex> lk(bg->mu);
-  bg->mode = mode;
-  return VSS_OK;
-}
-
-int vss_background_set_blur(vss_background* bg, int radius, double sigma) {
-  if (!bg) return fail(nullptr, VSS_E_INVALID_ARG, "null background");
-  uint16_t w[2 * kBlurMaxRadius + 1];
-  std::string why;
-  const int rc = blur_weights(radius, sigma, w, &why);
-  if (rc) return fail(bg->h, rc, why);
-  std::lock_guard<std::mutex> lk(bg->mu);
-  for (int k = 0; k <= radius; ++k) bg->w[k] = w[radius + k];
-  bg->radius = radius;
-  bg->mode = VSS_BG_BLUR;
-  return VSS_OK;
-}
-
-int vss_background_set_refine(vss_background* bg, int radius, double eps) {
-  if (!bg) return fail(nullptr, VSS_E_INVALID_ARG, "null background");
-  if (radius < 0 || radius > VSS_REFINE_MAX_RADIUS)
-    return fail(bg->h, VSS_E_INVALID_ARG, "refine radius must be 0 (off) or in [1, 8]");
-  if (radius && !(eps >= 1.0 && eps <= 65025.0))  // NaN fails both
-    return fail(bg->h, VSS_E_INVALID_ARG, "refine eps must be in [1, 65025]");
-  std::lock_guard<std::mutex> lk(bg->mu);
-  bg->refine_radius = radius;
-  bg->refine_eps = radius ? eps : 0.0;
-  return VSS_OK;
-}
-
-// ---- branding layers (include/vss_layers.h) ----
-int vss_layers_map(int v, int canvas, int frame) {
-  if (canvas < 1) return 0;
-  const long q = layers_map(v, canvas, frame);
-  return (int)std::min<long>(std::max<long>(q, INT_MIN), INT_MAX);
-}
-
-int vss_background_set_layers(vss_background* bg, const vss_layer* layers, int n, int canvas_w, int canvas_h) {
-  if (!bg) return fail(nullptr, VSS_E_INVALID_ARG, "null background");
-  vss_handle* h = bg->h;
-  if (n < 0 || n > VSS_MAX_LAYERS) return fail(h, VSS_E_INVALID_ARG, "layer count must be in [0, 32]");
-  if (canvas_w < 1 || canvas_h < 1) return fail(h, VSS_E_INVALID_ARG, "canvas size must be >= 1 x 1");
-  if (n > 0 && !layers) return fail(h, VSS_E_INVALID_ARG, "null layer array");
-  size_t total = 0;
-  for (int i = 0; i < n; ++i) {
-    const vss_layer& l = layers[i];
-    const std::string at = "layer " + std::to_string(i) + ": ";
-    if (l.type != VSS_LAYER_IMAGE && l.type != VSS_LAYER_ROUNDED_RECT)
-      return fail(h, VSS_E_INVALID_ARG, at + "unknown type");
-    if (l.privacy < 1 || l.privacy > 3) return fail(h, VSS_E_INVALID_ARG, at + "privacy must be in [1, 3]");
-    if (l.width < 0 || l.height < 0) return fail(h, VSS_E_INVALID_ARG, at + "width and height must be >= 0");
-    if (l.radius < 0) return fail(h, VSS_E_INVALID_ARG, at + "radius must be >= 0");
-    if (l.shadow_blur < 0) return fail(h, VSS_E_INVALID_ARG, at + "shadow_blur must be >= 0");
-    if (l.type == VSS_LAYER_IMAGE) {
-      if (!l.pixels) return fail(h, VSS_E_INVALID_ARG, at + "null sprite");
-      if (l.src_h < 1 || l.src_h > VSS_LAYER_MAX_SPRITE || l.src_w < 1 || l.src_w > VSS_LAYER_MAX_SPRITE)
-        return fail(h, VSS_E_INVALID_ARG, at + "sprite sides must be in [1, 4096]");
-      if (l.row_stride < (size_t)l.src_w * 4) return fail(h, VSS_E_INVALID_ARG, at + "row_stride < 4 * src_w");
-      total += (size_t)l.src_h * l.src_w * 4;
-    }
-  }
-  // the sprites, premultiplied once: c' = (c*a + 127) / 255
-  std::vector<uint8_t> host(total);
-  std::vector<vss_background::Layer> fresh((size_t)n);
-  size_t off = 0;
-  for (int i = 0; i < n; ++i) {
-    fresh[i].l = layers[i];
-    fresh[i].l.pixels = nullptr;
-    fresh[i].sprite_off = off;
-    if (layers[i].type != VSS_LAYER_IMAGE) continue;
-    const vss_layer& l = layers[i];
-    for (int y = 0; y < l.src_h; ++y) {
-      const uint8_t* src = l.pixels + (size_t)y * l.row_stride;
-      uint8_t* dst = host.data() + off + (size_t)y * l.src_w * 4;
-      for (int x = 0; x < l.src_w; ++x) {
-        const unsigned a = src[4 * x + 3];
-        for (int c = 0; c < 3; ++c) dst[4 * x + c] = (uint8_t)((src[4 * x + c] * a + 127u) / 255u);
-        dst[4 * x + 3] = (uint8_t)a;
-      }
-    }
-    off += (size_t)l.src_h * l.src_w * 4;
-  }
-  std::lock_guard<std::mutex> lk(bg->mu);
-  int rc = bg_quiesce(bg);  // a composite may still read the old sprites and plates
-  if (rc) return rc;
-  bg->layers.clear();
-  bg->plate_fh = bg->plate_fw = 0;  // O and what is baked from it: rebuilt by the next composite
-  bg->img_fh = bg->img_fw = 0;
-  rc = bg_alloc(bg, &bg->d_sprites, &bg->sprites_bytes, total);
-  if (!rc && total) {
-    const hipError_t e = hipMemcpy(bg->d_sprites, host.data(), total, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-      (void)bg_alloc(bg, &bg->d_sprites, &bg->sprites_bytes, 0);
-      rc = fail(h, VSS_E_HIP, std::string("sprite upload: ") + hipGetErrorString(e));
-    }
-  }
-  if (rc) n = 0;  // out of memory or a failed upload: no layers, as after n = 0
-  if (n == 0) {
-    (void)bg_alloc(bg, &bg->d_plate, &bg->plate_bytes, 0);
-    (void)bg_alloc(bg, &bg->d_shadow, &bg->shadow_bytes, 0);
-    // a plate that only a colour under layers needed
-    if (!bg->img_for_image) (void)bg_alloc(bg, &bg->d_img, &bg->img_bytes, 0);
-    bg->img_mode = -1;
-    return rc;
-  }
-  bg->layers = std::move(fresh);
-  bg->canvas_w = canvas_w;
-  bg->canvas_h = canvas_h;
-  return VSS_OK;
-}
-
-int vss_background_set_privacy(vss_background* bg, int level) {
-  if (!bg) return fail(nullptr, VSS_E_INVALID_ARG, "null background");
-  if (level < 1 || level > 3) return fail(bg->h, VSS_E_INVALID_ARG, "privacy level must be in [1, 3]");
-  std::lock_guard<std::mutex> lk(bg->mu);
-  if (level == bg->level) return VSS_OK;
-  bg->level = level;
-  bg->plate_fh = bg->plate_fw = 0;
-  bg->img_fh = bg->img_fw = 0;
-  return VSS_OK;
-}
-
-int vss_background_overlay_device(vss_handle* h, vss_background* bg, int height, int width, uint8_t* d_out,
-                                  size_t row_stride, void* stream) {
-  if (!h) return fail(nullptr, VSS_E_INVALID_ARG, "null handle");
-  if (!bg || bg->h != h) return fail(h, VSS_E_INVALID_ARG, "handle / background mismatch");
-  if (!d_out) return fail(h, VSS_E_INVALID_ARG, "null device pointer");
-  if (height < 1 || width < 1 || height > 16384 || width > 16384)
-    return fail(h, VSS_E_INVALID_ARG, "overlay size must be in [1, 16384]");
-  if (row_stride < (size_t)width * 4) return fail(h, VSS_E_INVALID_ARG, "row_stride < 4 * width");
-  HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  std::lock_guard<std::mutex> lk(bg->mu);
-  if (bg->used && bg->last_stream != s) HIP_TRY(h, hipStreamWaitEvent(s, bg->last, 0));
-  if (layers_visible(bg)) {
-    const int rc = plate_enqueue(h, bg, height, width, s);
-    if (rc) return rc;
-    HIP_TRY(h, hipMemcpy2DAsync(d_out, row_stride, bg->d_plate, (size_t)layer_pitch(width) * 4, (size_t)width * 4,
-                                height, hipMemcpyDeviceToDevice, s));
-  } else {
-    HIP_TRY(h, hipMemset2DAsync(d_out, row_stride, 0, (size_t)width * 4, height, s));
-  }
-  HIP_TRY(h, hipEventRecord(bg->last, s));
-  bg->last_stream = s;
-  bg->used = true;
-  return VSS_OK;
-}
-
-int vss_background_alpha_device(vss_handle* h, vss_background* bg, const uint8_t* d_frames, int n, int height,
-                                int width, int channels, size_t row_stride, size_t frame_stride,
-                                const uint8_t* d_alpha_u8, uint8_t* d_out_alpha, size_t out_row_stride,
-                                size_t out_frame_stride, void* stream) {
-  if (!h) return fail(nullptr, VSS_E_INVALID_ARG, "null handle");
-  return vss_background_alpha_device_at(h, bg, d_frames, n, height, width, channels, row_stride, frame_stride,
-                                        d_alpha_u8, h->cfg.model_h, h->cfg.model_w, d_out_alpha, out_row_stride,
-                                        out_frame_stride, stream);
-}
-
-int vss_background_alpha_device_at(vss_handle* h, vss_background* bg, const uint8_t* d_frames, int n, int height,
-                                   int width, int channels, size_t row_stride, size_t frame_stride,
-                                   const uint8_t* d_alpha_u8, int mask_h, int mask_w, uint8_t* d_out_alpha,
-                                   size_t out_row_stride, size_t out_frame_stride, void* stream) {
-  if (!h) return fail(nullptr, VSS_E_INVALID_ARG, "null handle");
-  if (mask_h < 1 || mask_w < 1) return fail(h, VSS_E_INVALID_ARG, "mask_h / mask_w must be >= 1");
-  if (!bg || bg->h != h) return fail(h, VSS_E_INVALID_ARG, "handle / background mismatch");
-  if (!d_frames || !d_alpha_u8 || !d_out_alpha) return fail(h, VSS_E_INVALID_ARG, "null device pointer");
-  int rc = check_frames(h, n, height, width, channels, row_stride, frame_stride,
-                        std::max(h->cfg.max_batch, h->user_max_batch));
-  if (rc) return rc;
-  if (out_row_stride < (size_t)width || out_frame_stride < out_row_stride * height)
-    return fail(h, VSS_E_INVALID_ARG, "bad alpha output geometry (row stride >= width)");
-  HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  std::lock_guard<std::mutex> lk(bg->mu);
-  if (bg->used && bg->last_stream != s) HIP_TRY(h, hipStreamWaitEvent(s, bg->last, 0));
-  MatteAlphaParams p{};
-  composite_params(&p.c, d_frames, height, width, channels, row_stride, frame_stride, d_alpha_u8, mask_h, mask_w,
-                   d_out_alpha, out_row_stride, out_frame_stride);
-  if (bg->refine_radius && (rc = matte_enqueue(h, bg, d_frames, n, height, width, channels, row_stride, frame_stride,
-                                               d_alpha_u8, mask_h, mask_w, s, &p.ab)))
-    return rc;
-  launch_matte_alpha(p, n, s);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, VSS_E_HIP, std::string("alpha launch: ") + hipGetErrorString(e));
-  HIP_TRY(h, hipEventRecord(bg->last, s));
-  bg->last_stream = s;
-  bg->used = true;
-  return VSS_OK;
-}
-
-int vss_background_composite_device(vss_handle* h, vss_background* bg, const uint8_t* d_frames, int n, int height,
-                                    int width, int channels, size_t row_stride, size_t frame_stride,
-                                    const uint8_t* d_alpha_u8, uint8_t* d_out_rgba, size_t out_row_stride,
-                                    size_t out_frame_stride, void* stream) {
-  if (!h) return fail(nullptr, VSS_E_INVALID_ARG, "null handle");
-  if (!bg || bg->h != h) return fail(h, VSS_E_INVALID_ARG, "handle / background mismatch");
-  if (!d_frames || !d_alpha_u8 || !d_out_rgba) return fail(h, VSS_E_INVALID_ARG, "null device pointer");
-  int rc = check_frames(h, n, height, width, channels, row_stride, frame_stride,
-                        std::max(h->cfg.max_batch, h->user_max_batch));
-  if (rc) return rc;
-  if (out_row_stride < (size_t)width * 4 || out_row_stride % 4 || out_frame_stride < out_row_stride * height ||
-      (reinterpret_cast<uintptr_t>(d_out_rgba) & 3))
-    return fail(h, VSS_E_INVALID_ARG, "bad RGBA output geometry (row stride >= 4*width, multiple of 4)");
-  HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  std::lock_guard<std::mutex> lk(bg->mu);
-  return bg_enqueue(h, bg, d_frames, n, height, width, channels, row_stride, frame_stride, d_alpha_u8, d_out_rgba,
-                    out_row_stride, out_frame_stride, s);
-}
-
-int vss_segment_background(vss_handle* h, vss_post_state* st, vss_background* bg, const uint8_t* frames, int n,
-                           int height, int width, int channels, size_t row_stride, uint8_t* out_rgba) {
-  if (!h || !st || st->h != h) return fail(h, VSS_E_INVALID_ARG, "handle / post state mismatch");
-  if (!bg || bg->h != h) return fail(h, VSS_E_INVALID_ARG, "handle / background mismatch");
-  if (!out_rgba) return fail(h, VSS_E_INVALID_ARG, "null output");
-  std::lock_guard<std::mutex> pl(h->post_mu);
-  std::unique_lock<std::mutex> lk(h->mu);
-  HIP_TRY(h, hipSetDevice(h->device));
-  const size_t cap = (size_t)h->cfg.max_batch * h->cfg.max_frame_h * h->cfg.max_frame_w * 4;
-  if (!h->d_comp) {
-    int rc = dalloc(h, &h->d_comp, cap);
-    if (rc) return rc;
-  }
-  const size_t fs = row_stride * (size_t)height, ors = (size_t)width * 4, ofs = ors * height;
-  if ((size_t)n * ofs > cap)
-    return fail(h, VSS_E_INVALID_ARG, "RGBA output exceeds the handle's capacity (max_batch, max_frame_h/w)");
-  int k = 0;
-  int rc = seam_on_stream(h, lk, frames, n, height, width, channels, row_stride, &k);
-  if (rc) return rc;
-  Slot& s = h->slots[k];
-  rc = post_enqueue(st, s.d_frames, n, height, width, channels, row_stride, fs, s.d_masks, nullptr, h->d_post_u8,
-                    h->stream);
-  if (!rc) {
-    std::lock_guard<std::mutex> bl(bg->mu);
-    rc = bg_enqueue(h, bg, s.d_frames, n, height, width, channels, row_stride, fs, h->d_post_u8, h->d_comp, ors, ofs,
-                    h->stream);
-  }
-  if (!rc) {
-    const hipError_t e = hipMemcpyAsync(out_rgba, h->d_comp, (size_t)n * ofs, hipMemcpyDeviceToHost, h->stream);
-    if (e != hipSuccess) rc = fail(h, VSS_E_HIP, std::string("D2H: ") + hipGetErrorString(e));
-  }
-  return finish_seam(h, lk, k, rc);
-}
-
-}  // extern "C"
-
-// ---- NV12 video I/O (vss_video.hip; the definition: include/vss_video.h) -----
-struct vss_video {
-  vss_handle* h = nullptr;
-  std::mutex mu;                 // setters and calls of one object are serialised
-  int std_ = VSS_CSC_BT709_LIMITED;
-  uint8_t* d_buf = nullptr;      // RGBA in | RGBA out (px_cap pixels each) | masks f32 | alpha u8 (max_batch frames)
-  size_t buf_bytes = 0, px_cap = 0;
-  uint8_t* d_nv = nullptr;       // the host call's device planes: Y in | UV in | Y out | UV out
-  size_t nv_bytes = 0;
-  int slot = -1;                 // the handle slot whose executable graph is bound to d_buf (taken by the first call)
-  hipEvent_t last = nullptr;     // recorded after every call
-  hipStream_t last_stream = nullptr;
-  bool used = false;
-};
-
-namespace {
-
-constexpr CscCoef kCsc[4] = {
-    {16, 298, 409, -100, -208, 516, 66, 129, 25, -38, -74, 112, 112, -94, -18},    // BT.601 limited
-    {16, 298, 459, -55, -136, 541, 47, 157, 16, -26, -86, 112, 112, -102, -10},    // BT.709 limited
-    {0, 256, 359, -88, -183, 454, 77, 150, 29, -43, -85, 128, 128, -107, -21},     // BT.601 full
-    {0, 256, 403, -48, -120, 475, 54, 183, 19, -29, -99, 128, 128, -116, -12},     // BT.709 full
-};
-
-int check_std(vss_handle* h, int std) {
-  if (std < 0 || std > 3) return fail(h, VSS_E_INVALID_ARG, "std must be one of VSS_CSC_* (0..3)");
-  return VSS_OK;
-}
-
-// one NV12 batch's geometry; `what` names the planes in the message
-int check_nv12(vss_handle* h, const char* what, const uint8_t* y, size_t yp, size_t yfs, const uint8_t* uv, size_t up,
-               size_t ufs, int n, int fh, int fw, int max_n) {
-  const std::string w(what);
-  if (!y || !uv) return fail(h, VSS_E_INVALID_ARG, w + ": null plane pointer");
-  if (n < 1 || n > max_n) return fail(h, VSS_E_INVALID_ARG, "n must be in [1, max_batch]");
-  if (fh < 2 || fw < 2 || (fh & 1) || (fw & 1))
-    return fail(h, VSS_E_INVALID_ARG, "NV12 needs an even height and width, both >= 2");
-  if (yp < (size_t)fw || up < (size_t)fw) return fail(h, VSS_E_INVALID_ARG, w + ": pitch < width");
-  if (yfs < yp * (size_t)fh) return fail(h, VSS_E_INVALID_ARG, w + ": y_frame_stride < y_pitch * height");
-  if (ufs < up * (size_t)(fh / 2)) return fail(h, VSS_E_INVALID_ARG, w + ": uv_frame_stride < uv_pitch * height/2");
-  return VSS_OK;
-}
-
-int check_rgba(vss_handle* h, const uint8_t* p, size_t rs, size_t fs, int fh, int fw) {
-  if (!p) return fail(h, VSS_E_INVALID_ARG, "null RGBA pointer");
-  if (rs < (size_t)fw * 4 || rs % 4 || fs < rs * (size_t)fh || fs % 4 || (reinterpret_cast<uintptr_t>(p) & 3))
-    return fail(h, VSS_E_INVALID_ARG,
-                "bad RGBA geometry (row stride >= 4*width; strides and base pointer multiples of 4)");
-  return VSS_OK;
-}
-
-Nv12Params nv12_params(int std, const uint8_t* y, size_t yp, size_t yfs, const uint8_t* uv, size_t up, size_t ufs,
-                       const uint8_t* rgba, size_t rs, size_t fs, int fh, int fw) {
-  Nv12Params p{};
-  p.y = const_cast<uint8_t*>(y);
-  p.uv = const_cast<uint8_t*>(uv);
-  p.y_pitch = (long)yp; p.y_frame_stride = (long)yfs;
-  p.uv_pitch = (long)up; p.uv_frame_stride = (long)ufs;
-  p.rgba = const_cast<uint8_t*>(rgba);
-  p.row_stride = (long)rs; p.frame_stride = (long)fs;
-  p.fh = fh; p.fw = fw;
-  p.k = kCsc[std];
-  return p;
-}
-
-int launched(vss_handle* h, const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(h, VSS_E_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
-  return VSS_OK;
-}
-
-int video_alloc(vss_video* v, uint8_t** p, size_t* have, size_t bytes) {
-  return counted_alloc(v->h, p, have, bytes);
-}
-
-// before a device buffer of v is freed: its latest call has ended
-int video_quiesce(vss_video* v) {
-  HIP_TRY(v->h, hipSetDevice(v->h->device));
-  if (v->used) HIP_TRY(v->h, hipEventSynchronize(v->last));
-  return VSS_OK;
-}
-
-// v->mu held; arguments checked.  The whole chain on s.
-int video_enqueue(vss_video* v, vss_post_state* st, vss_background* bg, const uint8_t* d_y, size_t yp, size_t yfs,
-                  const uint8_t* d_uv, size_t up, size_t ufs, int n, int fh, int fw, uint8_t* d_oy, size_t oyp,
-                  size_t oyfs, uint8_t* d_ouv, size_t oup, size_t oufs, hipStream_t s) {
-  vss_handle* h = v->h;
-  const size_t px = (size_t)n * fh * fw, P = (size_t)h->cfg.model_h * h->cfg.model_w;
-  const size_t nb = (size_t)std::max(h->cfg.max_batch, h->user_max_batch);
-  int rc;
-  if (px > v->px_cap) {
-    if ((rc = video_quiesce(v))) return rc;
-    v->px_cap = 0;
-    if ((rc = video_alloc(v, &v->d_buf, &v->buf_bytes, px * 8 + nb * P * 5))) return rc;
-    v->px_cap = px;
-  }
-  if (v->used && v->last_stream != s) HIP_TRY(h, hipStreamWaitEvent(s, v->last, 0));
-  uint8_t* d_in = v->d_buf;
-  uint8_t* d_out = v->d_buf + v->px_cap * 4;
-  float* d_masks = reinterpret_cast<float*>(v->d_buf + v->px_cap * 8);
-  uint8_t* d_alpha = v->d_buf + v->px_cap * 8 + nb * P * 4;
-  const size_t rs = (size_t)fw * 4, fs = rs * fh;
-  launch_nv12_unpack(nv12_params(v->std_, d_y, yp, yfs, d_uv, up, ufs, d_in, rs, fs, fh, fw), n, s);
-  rc = launched(h, "nv12 unpack");
-  if (!rc) rc = segment_device_on(h, &v->slot, d_in, n, fh, fw, 4, rs, fs, d_masks, s);
-  if (!rc) rc = vss_postprocess_device(st, d_in, n, fh, fw, 4, rs, fs, d_masks, nullptr, d_alpha, s);
-  if (!rc) {
-    std::lock_guard<std::mutex> bl(bg->mu);
-    rc = bg_enqueue(h, bg, d_in, n, fh, fw, 4, rs, fs, d_alpha, d_out, rs, fs, s);
-  }
-  if (!rc) {
-    launch_nv12_pack(nv12_params(v->std_, d_oy, oyp, oyfs, d_ouv, oup, oufs, d_out, rs, fs, fh, fw), n, s);
-    rc = launched(h, "nv12 pack");
-  }
-  // also after a failed enqueue: what did go out reads or writes the scratch
-  HIP_TRY(h, hipEventRecord(v->last, s));
-  v->last_stream = s;
-  v->used = true;
-  return rc;
-}
-
-int check_video_call(vss_video* v, vss_post_state* st, vss_background* bg) {
-  if (!v) return fail(nullptr, VSS_E_INVALID_ARG, "null video");
-  if (!st || st->h != v->h) return fail(v->h, VSS_E_INVALID_ARG, "video / post state mismatch");
-  if (!bg || bg->h != v->h) return fail(v->h, VSS_E_INVALID_ARG, "video / background mismatch");
-  return VSS_OK;
-}
-
-}  // namespace
-
-static_assert(VSS_CSC_BT601_LIMITED == 0 && VSS_CSC_BT709_LIMITED == 1 && VSS_CSC_BT601_FULL == 2 &&
-                  VSS_CSC_BT709_FULL == 3,
-              "kCsc is indexed by VSS_CSC_*");
-
-extern "C" {
-
-int vss_nv12_to_rgba_device(vss_handle* h, int std, const uint8_t* d_y, size_t y_pitch, size_t y_frame_stride,
-                            const uint8_t* d_uv, size_t uv_pitch, size_t uv_frame_stride, int n, int height, int width,
-                            uint8_t* d_rgba, size_t row_stride, size_t frame_stride, void* stream) {
-  if (!h) return fail(nullptr, VSS_E_INVALID_ARG, "null handle");
-  int rc = check_std(h, std);
-  if (!rc)
-    rc = check_nv12(h, "input", d_y, y_pitch, y_frame_stride, d_uv, uv_pitch, uv_frame_stride, n, height, width,
-                    std::max(h->cfg.max_batch, h->user_max_batch));
-  if (!rc) rc = check_rgba(h, d_rgba, row_stride, frame_stride, height, width);
-  if (rc) return rc;
-  HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  launch_nv12_unpack(nv12_params(std, d_y, y_pitch, y_frame_stride, d_uv, uv_pitch, uv_frame_stride, d_rgba, row_stride,
-                                 frame_stride, height, width), n, s);
-  return launched(h, "nv12 unpack");
-}
-
-int vss_rgba_to_nv12_device(vss_handle* h, int std, const uint8_t* d_rgba, size_t row_stride, size_t frame_stride,
-                            int n, int height, int width, uint8_t* d_y, size_t y_pitch, size_t y_frame_stride,
-                            uint8_t* d_uv, size_t uv_pitch, size_t uv_frame_stride, void* stream) {
-  if (!h) return fail(nullptr, VSS_E_INVALID_ARG, "null handle");
-  int rc = check_std(h, std);
-  if (!rc)
-    rc = check_nv12(h, "output", d_y, y_pitch, y_frame_stride, d_uv, uv_pitch, uv_frame_stride, n, height, width,
-                    std::max(h->cfg.max_batch, h->user_max_batch));
-  if (!rc) rc = check_rgba(h, d_rgba, row_stride, frame_stride, height, width);
-  if (rc) return rc;
-  HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  launch_nv12_pack(nv12_params(std, d_y, y_pitch, y_frame_stride, d_uv, uv_pitch, uv_frame_stride, d_rgba, row_stride,
-                               frame_stride, height, width), n, s);
-  return launched(h, "nv12 pack");
-}
-
-int vss_video_create(vss_handle* h, int std, vss_video** out) {
-  if (!h || !out) return fail(h, VSS_E_INVALID_ARG, "null handle/out");
-  *out = nullptr;
-  if (int rc = check_std(h, std)) return rc;
-  HIP_TRY(h, hipSetDevice(h->device));
-  vss_video* v = new vss_video();
-  v->h = h;
-  v->std_ = std;
-  const hipError_t e = hipEventCreateWithFlags(&v->last, hipEventDisableTiming);
-  if (e != hipSuccess) {
-    delete v;
-    return fail(h, VSS_E_HIP, std::string("hipEventCreate: ") + hipGetErrorString(e));
-  }
-  *out = v;
-  return VSS_OK;
-}
-
-void vss_video_destroy(vss_video* v) {
-  if (!v) return;
-  (void)video_quiesce(v);
-  (void)video_alloc(v, &v->d_buf, &v->buf_bytes, 0);
-  (void)video_alloc(v, &v->d_nv, &v->nv_bytes, 0);
-  if (v->last) (void)hipEventDestroy(v->last);
-  delete v;
-}
-
-int vss_video_set_standard(vss_video* v, int std) {
-  if (!v) return fail(nullptr, VSS_E_INVALID_ARG, "null video");
-  if (int rc = check_std(v->h, std)) return rc;
-  std::lock_guard<std::mutex> lk(v->mu);
-  v->std_ = std;
-  return VSS_OK;
-}
-
-int vss_video_process_device(vss_video* v, vss_post_state* st, vss_background* bg, const uint8_t* d_y, size_t y_pitch,
-                             size_t y_frame_stride, const uint8_t* d_uv, size_t uv_pitch, size_t uv_frame_stride, int n,
-                             int height, int width, uint8_t* d_out_y, size_t oy_pitch, size_t oy_frame_stride,
-                             uint8_t* d_out_uv, size_t ouv_pitch, size_t ouv_frame_stride, void* stream) {
-  int rc = check_video_call(v, st, bg);
-  if (rc) return rc;
-  vss_handle* h = v->h;
-  rc = check_nv12(h, "input", d_y, y_pitch, y_frame_stride, d_uv, uv_pitch, uv_frame_stride, n, height, width,
-                  h->cfg.max_batch);
-  if (!rc)
-    rc = check_nv12(h, "output", d_out_y, oy_pitch, oy_frame_stride, d_out_uv, ouv_pitch, ouv_frame_stride, n, height,
-                    width, h->cfg.max_batch);
-  if (rc) return rc;
-  HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  std::lock_guard<std::mutex> lk(v->mu);
-  return video_enqueue(v, st, bg, d_y, y_pitch, y_frame_stride, d_uv, uv_pitch, uv_frame_stride, n, height, width,
-                       d_out_y, oy_pitch, oy_frame_stride, d_out_uv, ouv_pitch, ouv_frame_stride, s);
-}
-
-int vss_video_process(vss_video* v, vss_post_state* st, vss_background* bg, const uint8_t* y, const uint8_t* uv, int n,
-                      int height, int width, uint8_t* out_y, uint8_t* out_uv) {
-  int rc = check_video_call(v, st, bg);
-  if (rc) return rc;
-  vss_handle* h = v->h;
-  const size_t w = width > 0 ? (size_t)width : 0, hh = height > 0 ? (size_t)height : 0;
-  rc = check_nv12(h, "input", y, w, w * hh, uv, w, w * (hh / 2), n, height, width, h->cfg.max_batch);
-  if (!rc) rc = check_nv12(h, "output", out_y, w, w * hh, out_uv, w, w * (hh / 2), n, height, width, h->cfg.max_batch);
-  if (rc) return rc;
-  HIP_TRY(h, hipSetDevice(h->device));
-  std::lock_guard<std::mutex> lk(v->mu);
-  const size_t yb = (size_t)n * w * hh, ub = yb / 2;  // bytes of the Y planes and of the UV planes
-  if (2 * (yb + ub) > v->nv_bytes) {
-    if ((rc = video_quiesce(v))) return rc;
-    if ((rc = video_alloc(v, &v->d_nv, &v->nv_bytes, 2 * (yb + ub)))) return rc;
-  }
-  uint8_t* d_y = v->d_nv;
-  uint8_t* d_uv = d_y + yb;
-  uint8_t* d_oy = d_uv + ub;
-  uint8_t* d_ouv = d_oy + yb;
-  hipStream_t s = h->stream;
-  if (v->used && v->last_stream != s) HIP_TRY(h, hipStreamWaitEvent(s, v->last, 0));  // the planes' previous reader
-  HIP_TRY(h, hipMemcpyAsync(d_y, y, yb, hipMemcpyHostToDevice, s));
-  HIP_TRY(h, hipMemcpyAsync(d_uv, uv, ub, hipMemcpyHostToDevice, s));
-  rc = video_enqueue(v, st, bg, d_y, w, w * hh, d_uv, w, w * (hh / 2), n, height, width, d_oy, w, w * hh, d_ouv, w,
-                     w * (hh / 2), s);
-  if (!rc) {
-    HIP_TRY(h, hipMemcpyAsync(out_y, d_oy, yb, hipMemcpyDeviceToHost, s));
-    HIP_TRY(h, hipMemcpyAsync(out_uv, d_ouv, ub, hipMemcpyDeviceToHost, s));
-  }
-  HIP_TRY(h, hipStreamSynchronize(s));
-  return rc;
-}
-
-}  // extern "C"
-
-// ---- the post chain over many streams (vss_post.hip k_post_pool; include/vss_pool.h) ----
-struct vss_post_pool {
-  vss_handle* h = nullptr;
-  std::mutex mu;                  // calls, resets and setters of one pool are serialised
-  vss_post_config cfg{};
-  int capacity = 0;
-  float* planes = nullptr;        // [capacity][2][P] prevAlpha, double-buffered per stream
-  size_t planes_bytes = 0;
-  double* rtab = nullptr;         // one range table for every stream
-  size_t rtab_bytes = 0;
-  double sw[3] = {0, 0, 0};
-  double tab_sigma = -1.0;
-  std::vector<uint8_t> seen;      // per stream: it has seen a frame (prevAlpha exists)
-  std::vector<uint8_t> cur;       // per stream: the plane that holds its prevAlpha
-  std::vector<uint64_t> stamp;    // per stream: the last call that named it (duplicate ids)
-  uint64_t calls = 0;
-  hipEvent_t last = nullptr;      // recorded after every call
-  hipStream_t last_stream = nullptr;
-  bool used = false;
-};
-
-namespace {
-
-// before the table is overwritten or the planes are freed: the pool's latest call has ended
-int pool_quiesce(vss_post_pool* p) {
-  HIP_TRY(p->h, hipSetDevice(p->h->device));
-  if (p->used) HIP_TRY(p->h, hipEventSynchronize(p->last));
-  return VSS_OK;
-}
-
-// p->mu held.  What a call may be refused for, before anything is enqueued.
-int pool_check(vss_post_pool* p, const int* ids, int n, const uint8_t* d_frames, int fh, int fw, int fc, size_t rs,
-               size_t fs, int max_n) {
-  vss_handle* h = p->h;
-  if (!ids) return fail(h, VSS_E_INVALID_ARG, "pool: null stream ids");
-  if (!d_frames && p->cfg.use_bilateral) return fail(h, VSS_E_INVALID_ARG, "pool: null frames with use_bilateral on");
-  if (int rc = check_frames(h, n, fh, fw, fc, rs, fs, max_n)) return rc;
-  const uint64_t call = ++p->calls;
-  for (int t = 0; t < n; ++t) {
-    if (ids[t] < 0 || ids[t] >= p->capacity)
-      return fail(h, VSS_E_INVALID_ARG, "pool: stream id " + std::to_string(ids[t]) + " outside [0, " +
-                                            std::to_string(p->capacity) + ")");
-    if (p->stamp[ids[t]] == call)
-      return fail(h, VSS_E_INVALID_ARG, "pool: stream id " + std::to_string(ids[t]) + " twice in one call");
-    p->stamp[ids[t]] = call;
-  }
-  return VSS_OK;
-}
-
-// p->mu held; arguments checked.  ceil(n / kPoolFrames) launches and the ordering event.
-int pool_enqueue(vss_post_pool* p, const int* ids, int n, const uint8_t* d_frames, int fh, int fw, int fc, size_t rs,
-                 size_t fs, const float* d_masks, const FaceFrame* d_faces, float* d_alpha, uint8_t* d_u8,
-                 hipStream_t s) {
-  vss_handle* h = p->h;
-  const long P = (long)h->cfg.model_h * h->cfg.model_w;
-  if (p->used && p->last_stream != s) HIP_TRY(h, hipStreamWaitEvent(s, p->last, 0));
-  PostPoolParams pp{};
-  post_filter_params(&pp.f, h, p->cfg, p->sw, p->rtab, fh, fw, fc, rs, fs);
-  pp.planes = p->planes;
-  pp.a = p->cfg.ema;
-  hipError_t e = hipSuccess;
-  for (int t0 = 0; t0 < n && e == hipSuccess; t0 += kPoolFrames) {
-    const int m = std::min(kPoolFrames, n - t0);
-    pp.f.faces = d_faces ? d_faces + t0 : nullptr;
-    pp.f.frames = d_frames ? d_frames + (size_t)t0 * fs : nullptr;
-    pp.f.alpha = d_alpha ? d_alpha + t0 * P : nullptr;
-    pp.f.alpha_u8 = d_u8 ? d_u8 + t0 * P : nullptr;
-    pp.masks = d_masks + t0 * P;
-    for (int t = 0; t < m; ++t) {
-      const int id = ids[t0 + t];
-      pp.entry[t] = (unsigned)id << 2 | (unsigned)p->cur[id] << 1 | (unsigned)p->seen[id];
-    }
-    launch_post_pool(pp, m, s);
-    e = hipGetLastError();
-    // the launch is in the stream: these streams' prevAlpha is in their other plane from here on
-    if (e == hipSuccess)
-      for (int t = 0; t < m; ++t) {
-        const int id = ids[t0 + t];
-        p->cur[id] ^= 1;
-        p->seen[id] = 1;
-      }
-  }
-  // also after a failed launch: what did go out reads and writes the planes
-  HIP_TRY(h, hipEventRecord(p->last, s));
-  p->last_stream = s;
-  p->used = true;
-  if (e != hipSuccess) return fail(h, VSS_E_HIP, std::string("pool launch: ") + hipGetErrorString(e));
-  return VSS_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int vss_post_pool_create(vss_handle* h, const vss_post_config* cfg, int capacity, vss_post_pool** out) {
-  if (!h || !out) return fail(h, VSS_E_INVALID_ARG, "null handle/out");
-  *out = nullptr;
-  if (capacity < 1 || capacity > (1 << 29)) return fail(h, VSS_E_INVALID_ARG, "pool: capacity must be in [1, 2^29]");
-  if (h->cfg.model_h < 3 || h->cfg.model_w < 3) return fail(h, VSS_E_UNSUPPORTED, "mask too small for post");
-  vss_post_config c;
-  if (cfg) c = *cfg;
-  else vss_post_config_default(&c);
-  if (!(c.sigma_spatial > 0) || !(c.sigma_range > 0)) return fail(h, VSS_E_INVALID_ARG, "sigmas must be > 0");
-  HIP_TRY(h, hipSetDevice(h->device));
-  vss_post_pool* p = new vss_post_pool();
-  p->h = h;
-  p->cfg = c;
-  p->capacity = capacity;
-  p->seen.assign(capacity, 0);
-  p->cur.assign(capacity, 0);
-  p->stamp.assign(capacity, 0);
-  const size_t P = (size_t)h->cfg.model_h * h->cfg.model_w;
-  int rc = counted_alloc(h, &p->planes, &p->planes_bytes, (size_t)capacity * 2 * P * 4);
-  if (!rc) rc = counted_alloc(h, &p->rtab, &p->rtab_bytes, (size_t)kRangeTab * 8);
-  if (!rc && hipEventCreateWithFlags(&p->last, hipEventDisableTiming) != hipSuccess)
-    rc = fail(h, VSS_E_HIP, "pool: hipEventCreate failed");
-  if (!rc && !post_tables_for(p->cfg, p->sw, p->rtab, &p->tab_sigma))
-    rc = fail(h, VSS_E_HIP, "pool: table upload failed");
-  if (rc) {
-    vss_post_pool_destroy(p);
-    return rc;
-  }
-  *out = p;
-  return VSS_OK;
-}
-
-void vss_post_pool_destroy(vss_post_pool* p) {
-  if (!p) return;
-  (void)pool_quiesce(p);
-  (void)counted_alloc(p->h, &p->planes, &p->planes_bytes, 0);
-  (void)counted_alloc(p->h, &p->rtab, &p->rtab_bytes, 0);
-  if (p->last) (void)hipEventDestroy(p->last);
-  delete p;
-}
-
-int vss_post_pool_set_config(vss_post_pool* p, const vss_post_config* cfg) {
-  if (!p) return fail(nullptr, VSS_E_INVALID_ARG, "null pool");
-  if (!cfg) return fail(p->h, VSS_E_INVALID_ARG, "pool: null config");
-  if (!(cfg->sigma_spatial > 0) || !(cfg->sigma_range > 0)) return fail(p->h, VSS_E_INVALID_ARG, "sigmas must be > 0");
-  std::lock_guard<std::mutex> lk(p->mu);
-  if (int rc = pool_quiesce(p)) return rc;  // the table may be rewritten
-  p->cfg = *cfg;
-  if (!post_tables_for(p->cfg, p->sw, p->rtab, &p->tab_sigma)) return fail(p->h, VSS_E_HIP, "pool: table upload failed");
-  return VSS_OK;
-}
-
-int vss_post_pool_reset(vss_post_pool* p, int stream_id) {
-  if (!p) return fail(nullptr, VSS_E_INVALID_ARG, "null pool");
-  if (stream_id < -1 || stream_id >= p->capacity)
-    return fail(p->h, VSS_E_INVALID_ARG, "pool: stream id " + std::to_string(stream_id) + " outside [0, " +
-                                             std::to_string(p->capacity) + ") and not -1");
-  std::lock_guard<std::mutex> lk(p->mu);
-  // host state only: the stream's next frame is told that it is the first
-  if (stream_id < 0) std::fill(p->seen.begin(), p->seen.end(), 0);
-  else p->seen[stream_id] = 0;
-  return VSS_OK;
-}
-
-int vss_post_pool_process_device(vss_post_pool* p, const int* stream_ids, int n, const uint8_t* d_frames, int height,
-                                 int width, int channels, size_t row_stride, size_t frame_stride, const float* d_masks,
-                                 const vss_face_frame* d_faces, float* d_alpha, uint8_t* d_alpha_u8, void* stream) {
-  if (!p) return fail(nullptr, VSS_E_INVALID_ARG, "null pool");
-  vss_handle* h = p->h;
-  if (!d_masks) return fail(h, VSS_E_INVALID_ARG, "pool: null masks");
-  std::lock_guard<std::mutex> lk(p->mu);
-  int rc = pool_check(p, stream_ids, n, d_frames, height, width, channels, row_stride, frame_stride,
-                      std::max(h->cfg.max_batch, h->user_max_batch));
-  if (rc) return rc;
-  HIP_TRY(h, hipSetDevice(h->device));
-  hipStream_t s = stream ? static_cast<hipStream_t>(stream) : h->stream;
-  return pool_enqueue(p, stream_ids, n, d_frames, height, width, channels, row_stride, frame_stride, d_masks,
-                      reinterpret_cast<const FaceFrame*>(d_faces), d_alpha, d_alpha_u8, s);
-}
-
-int vss_segment_post_pool(vss_handle* h, vss_post_pool* p, const int* stream_ids, const uint8_t* frames, int n,
-                          int height, int width, int channels, size_t row_stride, float* alpha_out,
-                          uint8_t* alpha_u8_out) {
-  if (!h || !p || p->h != h) return fail(h, VSS_E_INVALID_ARG, "handle / post pool mismatch");
-  if (!alpha_out && !alpha_u8_out) return fail(h, VSS_E_INVALID_ARG, "no output requested");
-  if (!frames) return fail(h, VSS_E_INVALID_ARG, "null frames");
-  std::lock_guard<std::mutex> pl(h->post_mu);
-  std::lock_guard<std::mutex> ql(p->mu);
-  int rc = pool_check(p, stream_ids, n, frames, height, width, channels, row_stride, row_stride * (size_t)height,
-                      h->cfg.max_batch);
-  if (rc) return rc;
-  std::unique_lock<std::mutex> lk(h->mu);
-  int k = 0;
-  rc = seam_on_stream(h, lk, frames, n, height, width, channels, row_stride, &k);
-  if (rc) return rc;
-  Slot& s = h->slots[k];
-  const size_t P = (size_t)h->cfg.model_h * h->cfg.model_w;
-  float* d_alpha = alpha_out ? h->d_post_alpha : nullptr;
-  uint8_t* d_u8 = alpha_u8_out ? h->d_post_u8 : nullptr;
-  rc = pool_enqueue(p, stream_ids, n, s.d_frames, height, width, channels, row_stride, row_stride * (size_t)height,
-                    s.d_masks, nullptr, d_alpha, d_u8, h->stream);
-  hipError_t e = hipSuccess;
-  if (!rc && alpha_out) e = hipMemcpyAsync(alpha_out, d_alpha, (size_t)n * P * 4, hipMemcpyDeviceToHost, h->stream);
-  if (!rc && e == hipSuccess && alpha_u8_out)
-    e = hipMemcpyAsync(alpha_u8_out, d_u8, (size_t)n * P, hipMemcpyDeviceToHost, h->stream);
-  if (!rc && e != hipSuccess) rc = fail(h, VSS_E_HIP, std::string("D2H: ") + hipGetErrorString(e));
-  return finish_seam(h, lk, k, rc);
-}
-
-}  // extern "C"
 
 // Introspection for the registry generator's LDS mirror (tests/test_registry.py):
 // the bytes of LDS block_lds() carves for one k_block shape.
