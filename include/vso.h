@@ -33,6 +33,12 @@
  *
  * Attributes (tests/op_cases.py is the table the sessions are held to):
  *   opset_import          read; it selects Softmax's form and Split's default.
+ *   Conv                  2-D, constant weights and bias; group, strides,
+ *                         dilations (0 or 2 values each), pads (0 or 4 values),
+ *                         auto_pad (it wins over pads); kernel_shape is taken
+ *                         from the weights.  Refused: any other list length,
+ *                         channels that do not match the weights and group, an
+ *                         empty output.
  *   MaxPool, AveragePool  kernel_shape, strides, dilations, pads (0 or 4
  *                         values), auto_pad, ceil_mode, count_include_pad: the
  *                         divisor is the window's taps inside the padded input

@@ -358,17 +358,28 @@ def _pads2(attrs, k, x_hw, strides, dil):
 
 
 def conv2d(x, w, b, attrs):
+    """ONNX Conv on NCHW, as the GPU session takes it: 2-D only, and strides /
+    dilations / pads either absent or of full length (2 / 2 / 4)."""
+    if x.ndim != 4 or w.ndim != 4:
+        raise ValueError(f"Conv: 2D only (input {x.shape}, weights {w.shape})")
     x = x.astype(np.float64)
     w = w.astype(np.float64)
     n, c, h, wd = x.shape
     m, cg, kh, kw = w.shape
     g = attrs.get("group", 1)
+    if g < 1 or c != cg * g or m % g:
+        raise ValueError(f"Conv: channel/group mismatch (input {x.shape}, weights {w.shape}, group {g})")
     s = attrs.get("strides", [1, 1])
     d = attrs.get("dilations", [1, 1])
+    for name, v, want in (("strides", s, 2), ("dilations", d, 2), ("pads", attrs.get("pads", [0] * 4), 4)):
+        if len(v) != want:
+            raise ValueError(f"Conv: {name} must have {want} values")
     pt, pl, pb, pr = _pads2(attrs, (kh, kw), (h, wd), s, d)
-    xp = np.pad(x, ((0, 0), (0, 0), (pt, pb), (pl, pr)))
     ho = (h + pt + pb - d[0] * (kh - 1) - 1) // s[0] + 1
     wo = (wd + pl + pr - d[1] * (kw - 1) - 1) // s[1] + 1
+    if ho < 1 or wo < 1:
+        raise ValueError(f"Conv: empty output ({ho} x {wo})")
+    xp = np.pad(x, ((0, 0), (0, 0), (pt, pb), (pl, pr)))
     out = np.zeros((n, m, ho, wo), np.float64)
     mg = m // g
     if g == c and g == m:  # depthwise: every channel at once, tap by tap
@@ -573,11 +584,16 @@ def run(model: Model, feeds: dict, want=None, conv_operands=None) -> dict:
     env = dict(model.inits)
     env.update({k: np.asarray(v) for k, v in feeds.items()})
     env[""] = None
+    const = set(model.inits) - set(feeds)  # the values known without the feeds: what the session folds
     for nd in model.nodes:
         op, a, ins = nd["op"], nd["attrs"], [env.get(i) for i in nd["inputs"]]
         x = ins[0] if ins else None
+        if all(i in const for i in nd["inputs"] if i):
+            const.update(nd["outputs"])
         if op == "Conv":
             w = ins[1]
+            if nd["inputs"][1] not in const:
+                raise ValueError("Conv: weights must be constant")
             if conv_operands and tiled_conv(w, a):
                 x, w = round_operand(x, conv_operands), round_operand(w, conv_operands)
             y = conv2d(x, w, ins[2] if len(ins) > 2 else None, a)

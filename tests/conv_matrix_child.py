@@ -8,8 +8,11 @@ spec: "plain:f32,bf16,f16;up:bf16,f16" — the models and the precisions to
 run, one after another.  Writes an .npz to its standard output: every output
 of every session's first run (key "<model>/<precision>/<case>") and "info",
 the bytes of one JSON object {"<model>/<precision>": {"launches": [...],
-"tile_convs": n, "rerun_equal": bool}}.  run_child() is the parent's side (tests/test_gpu_conv_tile_matrix.py):
-it starts no further child once one has ended abnormally."""
+"tile_convs": n, "rerun_equal": bool}}.  A model "op_<family>" is that family
+of the operator matrix (tests/op_cases.py), its outputs keyed by graph output
+name.  run_child() is the parent's side (tests/test_gpu_conv_tile_matrix.py,
+tests/test_gpu_op_matrix.py): it starts no further child once one has ended
+abnormally."""
 import importlib.util
 import io
 import json
@@ -37,13 +40,22 @@ def parse_spec(spec):
     return [(part.split(":")[0], part.split(":")[1].split(",")) for part in spec.split(";")]
 
 
+def _model(model):
+    """(bytes, feeds, one key per graph output, in order) of a model of a spec."""
+    if model.startswith("op_"):
+        import op_cases as OC
+        cases = OC.groups()[model[3:]]
+        data, f, outs = OC.build(cases)
+        return data, f, [o for cs in cases for o in outs[cs.name]]
+    return MODELS[model][0](), feeds(model), MODELS[model][2]
+
+
 def run_sessions(ort, spec):
     """({"<model>/<precision>/<case>": output}, {"<model>/<precision>": info})
     of the sessions `spec` names, in this process."""
     outs, info = {}, {}
     for model, precisions in parse_spec(spec):
-        build, _, cases, _ = MODELS[model]
-        data, f = build(), feeds(model)
+        data, f, cases = _model(model)
         for prec in precisions:
             with ort.InferenceSession(data, precision=prec) as s:
                 got = s.run(f)

@@ -4,7 +4,8 @@ tests/test_op_matrix_oracle.py (the oracle against an independent float64
 evaluation, CPU) and tests/test_gpu_op_matrix.py (the GPU session against the
 oracle).
 
-A case is one operator node: its attributes, its inputs in operator order
+A case is one operator node (the conv family: with the nodes a session fuses
+behind it, `chain`): its attributes, its inputs in operator order
 (graph inputs filled from a seeded generator, or constants where the operator
 needs them constant), the model's opset, and whether the session must compute
 it ("value") or refuse it at creation ("refused").  build() packs any number
@@ -42,6 +43,9 @@ class Case:
     n_out: int = 1
     post: tuple = ()        # ("PRelu", slope array): a second node on the output (the fused forms)
     kernels: tuple = ()     # what a session of this case alone launches (a part of each name, in order)
+    # further nodes, each on the output of the one before: (op, its further inputs (as `inputs`), attributes);
+    # the last one's output is the case's (the conv family's pairs and epilogues)
+    chain: tuple = ()
 
 
 CASES: list[Case] = []
@@ -317,6 +321,190 @@ case("Softmax_opset11_axis0", "softmax11", "Softmax", [x(3, 5)], {"axis": 0}, op
 case("Softmax_opset11_axis-1", "softmax11", "Softmax", [x(2, 3, 5)], {"axis": -1}, opset=11)
 
 # ---------------------------------------------------------------------------
+# Conv: every kernel form launch_conv / conv_kernel_name (vso_kernels.hip) and
+# plan_conv (vso_model.hip) choose but k_conv_tile in f32 (tests/test_gpu_conv_tile_matrix.py),
+# one Conv per case (or a depthwise -> 1x1 pair, or a Conv with its epilogue),
+# the name of its launch asserted.  Batch 2, planes 9x11 (99 outputs: a pixel
+# tile tail on every tile size) and channel counts off the 16 / 64 tiles unless
+# a form's own threshold asks for more.  K = Cg * kh * kw.  In f32 a dense
+# square 3x3 / 5x5 stride-1 or 3x3 stride-2 case stays below 8e6 MACs (above,
+# it is k_conv_tile's); in a 16-bit session those cases run on k_conv_tile
+# whatever their size (onnx_ref.tiled_conv), every other case as in f32.
+_conv_seed = [100]
+
+
+def _cw(*shape):
+    _conv_seed[0] += 1
+    return cf(shape, _conv_seed[0])
+
+
+def small(pw, ch, split):
+    return f"k_conv_small<{str(pw).lower()}, {ch}, {str(split).lower()}>("
+
+
+def then(op_, *ins, **attrs):
+    return (op_, tuple(ins), attrs)
+
+
+def conv(name, xs, ws, attrs=None, kernels=(), bias=True, chain=()):
+    """One Conv of a graph input `xs` with constant weights `ws` (and a bias), then `chain`."""
+    case(f"Conv_{name}", "conv", "Conv", [x(*xs), _cw(*ws)] + ([_cw(ws[0])] if bias else []), attrs,
+         kernels=tuple(kernels), chain=tuple(chain))
+
+
+def pw_after(c_, m_, bias=True):
+    """The 1x1 Conv of a depthwise -> 1x1 pair."""
+    return then("Conv", _cw(m_, c_, 1, 1), *([_cw(m_)] if bias else []))
+
+
+CLIP6 = then("Clip", c(0.0, np.float32), c(6.0, np.float32))
+P9 = (9, 11)
+
+# k_conv_small<false, 8 | 16 | 32, false> (K <= 32 | 64 | 128) and <false, 16, true> (K > 128: four
+# waves, ceil(K / 16) * 4 of K each); A operands as float4 where K % 4 == 0, else one by one
+conv("small_K27", (2, 3, *P9), (5, 3, 3, 3), {"kernel_shape": [3, 3], "pads": [1, 1, 1, 1]}, [small(False, 8, False)])
+conv("small_K27_s2x1", (2, 3, *P9), (17, 3, 3, 3), {"strides": [2, 1], "pads": [1, 1, 1, 1]}, [small(False, 8, False)])
+conv("small_K32_2x2", (2, 8, *P9), (17, 8, 2, 2), {"kernel_shape": [2, 2], "pads": [1, 0, 0, 1]},
+     [small(False, 8, False)])
+conv("small_K21_1x7", (2, 3, *P9), (16, 3, 1, 7), {"kernel_shape": [1, 7], "pads": [0, 3, 0, 2]},
+     [small(False, 8, False)])
+conv("small_K28_7x1_s2x1", (2, 4, *P9), (20, 4, 7, 1), {"strides": [2, 1], "pads": [3, 0, 3, 0]},
+     [small(False, 8, False)])
+conv("small_K36_s2", (2, 4, *P9), (17, 4, 3, 3), {"strides": [2, 2], "pads": [1, 1, 1, 1]}, [small(False, 16, False)])
+conv("small_K63_dil2x1", (2, 7, *P9), (5, 7, 3, 3), {"dilations": [2, 1], "pads": [2, 1, 2, 1]},
+     [small(False, 16, False)])
+conv("small_K64_2x2_nobias", (2, 16, *P9), (20, 16, 2, 2), {"kernel_shape": [2, 2]}, [small(False, 16, False)],
+     bias=False)
+conv("small_K45_3x5_dil1x3", (2, 3, *P9), (16, 3, 3, 5), {"dilations": [1, 3], "pads": [1, 6, 1, 6]},
+     [small(False, 16, False)])
+# pads of the kernel's extent: the outputs of the outermost ring see no input, they equal the bias
+conv("small_K72_pads3", (2, 8, *P9), (20, 8, 3, 3), {"pads": [3, 3, 3, 3]}, [small(False, 32, False)])
+conv("small_K128_2x2_s2", (2, 32, *P9), (17, 32, 2, 2), {"strides": [2, 2]}, [small(False, 32, False)])
+conv("small_K75_5x5", (2, 3, *P9), (5, 3, 5, 5), {"pads": [2, 2, 2, 2]}, [small(False, 32, False)])
+conv("small_K98_7x7", (2, 2, *P9), (16, 2, 7, 7), {"pads": [3, 3, 3, 3]}, [small(False, 32, False)])
+conv("small_K132_2x2", (2, 33, *P9), (20, 33, 2, 2), {"pads": [0, 1, 1, 0]}, [small(False, 16, True)])
+conv("small_K135", (2, 15, *P9), (17, 15, 3, 3), {"pads": [1, 1, 1, 1]}, [small(False, 16, True)])  # last wave: 27 of 36
+conv("small_K147_7x7_s2", (2, 3, *P9), (16, 3, 7, 7), {"strides": [2, 2], "pads": [3, 3, 3, 3]},
+     [small(False, 16, True)])
+conv("small_K1800", (2, 200, *P9), (5, 200, 3, 3), {"pads": [1, 1, 1, 1]}, [small(False, 16, True)])
+conv("small_K27_relu", (2, 3, *P9), (5, 3, 3, 3), {"pads": [1, 1, 1, 1]}, [small(False, 8, False)],
+     chain=[then("Add", x(2, 5, *P9)), then("Relu")])
+conv("small_K135_prelu", (2, 15, *P9), (17, 15, 3, 3), {"pads": [1, 1, 1, 1]}, [small(False, 16, True)],
+     chain=[then("PRelu", _cw(17, 1, 1))])
+# groups: Mg 5 (a channel tile tail in every group), and a channel multiplier (Cg 1, Mg 2)
+conv("small_G2_Mg5", (2, 6, *P9), (10, 3, 3, 3), {"group": 2, "pads": [1, 1, 1, 1]}, [small(False, 8, False)])
+conv("small_G2_Mg5_K135", (2, 30, *P9), (10, 15, 3, 3), {"group": 2, "pads": [1, 1, 1, 1]}, [small(False, 16, True)])
+conv("small_multiplier2", (2, 6, *P9), (12, 1, 3, 3), {"group": 6, "pads": [1, 1, 1, 1]}, [small(False, 8, False)])
+# k_conv_small<true, ...>: a 1x1 that k_conv_pw does not take — grouped, or more than 192 channels on
+# fewer than 256 of its workgroups
+conv("small_pw_G2_Cg4", (2, 8, *P9), (10, 4, 1, 1), {"group": 2}, [small(True, 8, False)])
+conv("small_pw_G2_Cg40", (2, 80, *P9), (34, 40, 1, 1), {"group": 2}, [small(True, 16, False)])
+conv("small_pw_G2_Cg100", (2, 200, *P9), (40, 100, 1, 1), {"group": 2}, [small(True, 32, False)])
+conv("small_pw_G3_Cg30", (2, 90, *P9), (15, 30, 1, 1), {"group": 3}, [small(True, 8, False)], bias=False)  # K % 4 != 0
+conv("small_pw_C200", (2, 200, *P9), (20, 200, 1, 1), {}, [small(True, 16, True)])
+conv("small_pw_C201", (2, 201, 7, 9), (5, 201, 1, 1), {}, [small(True, 16, True)],  # K % 4 != 0, last wave 45 of 52
+     chain=[then("Add", x(2, 5, 7, 9)), CLIP6])
+
+# k_conv_gemm: at least 1024 64x64 tiles.  Grouped: 64 pixel tiles x 16 (image, group) pairs, K 27 a
+# K-step tail, 5 of a tile's 64 channels.  Dense: 256 pixel tiles (the last one pixel short) x 2
+# channel tiles (the second holds one channel) x 2 images; non-square, so no precision tiles it
+conv("gemm_G8_Mg5", (2, 24, 63, 65), (40, 3, 3, 3), {"group": 8, "pads": [1, 1, 1, 1]}, ["k_conv_gemm("])
+conv("gemm_M65_2x3_dil2x1", (2, 3, 127, 129), (65, 3, 2, 3), {"dilations": [2, 1], "pads": [1, 1, 1, 1]},
+     ["k_conv_gemm("], chain=[then("Relu")])
+
+# k_conv_dw, one output per thread (a graph output: no 1x1 takes it over)
+conv("dw_3x3", (2, 5, *P9), (5, 1, 3, 3), {"group": 5, "pads": [1, 1, 1, 1]}, ["k_conv_dw("])
+conv("dw_5x5_s2", (2, 5, *P9), (5, 1, 5, 5), {"group": 5, "strides": [2, 2], "pads": [2, 2, 2, 2]}, ["k_conv_dw("],
+     chain=[CLIP6])
+conv("dw_3x5_s1x2", (2, 5, *P9), (5, 1, 3, 5), {"group": 5, "strides": [1, 2], "pads": [2, 1, 0, 1]}, ["k_conv_dw("])
+conv("dw_7x1_dil2", (2, 5, *P9), (5, 1, 7, 1), {"group": 5, "dilations": [2, 2], "pads": [6, 0, 6, 0]},
+     ["k_conv_dw("], bias=False)
+conv("dw_3x3_dil2_pads0022", (2, 5, *P9), (5, 1, 3, 3), {"group": 5, "dilations": [2, 2], "pads": [0, 0, 2, 2]},
+     ["k_conv_dw("])
+# the four-outputs-per-thread body inside k_conv_dw: N * M = 65536 planes (one more than
+# k_conv_dw_plane's grid takes) and exactly 1024 * 256 quads
+conv("dw_quad_body", (2, 32768, 4, 4), (32768, 1, 3, 3), {"group": 32768, "pads": [1, 1, 1, 1]}, ["k_conv_dw("])
+# k_conv_dw_plane<1 | 2>: 3x3, rows of a multiple of 4 outputs, at least 1024 * 256 quads.  (k_conv_dw's
+# conv_dw_body<long> needs 2^30 outputs: it has no case.)
+conv("dw_plane1", (2, 33, 127, 128), (33, 1, 3, 3), {"group": 33, "pads": [1, 1, 1, 1]}, ["k_conv_dw_plane<1>("])
+conv("dw_plane2_s2", (4, 64, 128, 128), (64, 1, 3, 3), {"group": 64, "strides": [2, 2], "pads": [0, 0, 1, 1]},
+     ["k_conv_dw_plane<2>("], chain=[then("Relu")])
+
+# k_conv_dwpw: a depthwise -> 1x1 pair on fewer than 512 k_conv_pw workgroups (or a depthwise that is
+# not 3x3 / 5x5).  Its 3x3 path and its generic one; C 24 (K % 16 != 0: A operands one by one) and 32;
+# M 70 (the second channel block's last three waves have no channel); 99 / 90 / 30 pixels (a tile tail)
+conv("dwpw_3x3_C24_M70", (2, 24, *P9), (24, 1, 3, 3), {"group": 24, "pads": [1, 1, 1, 1]}, ["k_conv_dwpw("],
+     chain=[then("Relu"), pw_after(24, 70)])
+conv("dwpw_3x3_s2_C32_M20", (2, 32, *P9), (32, 1, 3, 3), {"group": 32, "strides": [2, 2], "pads": [0, 0, 1, 1]},
+     ["k_conv_dwpw("], chain=[CLIP6, pw_after(32, 20), then("Add", x(2, 20, 4, 5)), then("Relu")])
+conv("dwpw_3x3_dil2_C24_M5", (2, 24, *P9), (24, 1, 3, 3), {"group": 24, "dilations": [2, 2], "pads": [2, 2, 2, 2]},
+     ["k_conv_dwpw("], bias=False, chain=[pw_after(24, 5)])
+conv("dwpw_3x3_pads0120_C32_M40", (2, 32, *P9), (32, 1, 3, 3), {"group": 32, "pads": [0, 1, 2, 0]},
+     ["k_conv_dwpw("], chain=[then("PRelu", _cw(32, 1, 1)), pw_after(32, 40), then("PRelu", _cw(40, 1, 1))])
+conv("dwpw_5x5_C24_M17", (2, 24, *P9), (24, 1, 5, 5), {"group": 24, "pads": [2, 2, 2, 2]}, ["k_conv_dwpw("],
+     chain=[then("PRelu", _cw(24, 1, 1)), pw_after(24, 17, bias=False)])
+conv("dwpw_3x5_dil2_C32_M70", (2, 32, *P9), (32, 1, 3, 5), {"group": 32, "dilations": [2, 2], "pads": [1, 4, 2, 3]},
+     ["k_conv_dwpw("], chain=[then("Relu"), pw_after(32, 70), CLIP6])
+conv("dwpw_5x5_s2_C32_M20", (2, 32, *P9), (32, 1, 5, 5), {"group": 32, "strides": [2, 2], "pads": [2, 1, 1, 2]},
+     ["k_conv_dwpw("], bias=False, chain=[pw_after(32, 20)])
+conv("dwpw_7x7_C24_M20", (2, 24, *P9), (24, 1, 7, 7), {"group": 24, "pads": [3, 3, 3, 3]}, ["k_conv_dwpw("],
+     chain=[then("LeakyRelu", alpha=0.1), pw_after(24, 20), then("Add", x(2, 20, *P9))])
+
+# k_conv_pw<1 | 2 | 4, 0> (M <= 16 | <= 32 | more): an ungrouped 1x1 of at most 192 channels (M 5 at
+# least: up to 4 channels are k_conv_thin's), or of more on at least 256 workgroups; 63 pixels
+for c_, m_ in ((3, 5), (32, 5), (33, 20), (68, 20), (32, 40), (68, 40)):
+    conv(f"pw_C{c_}_M{m_}", (2, c_, 7, 9), (m_, c_, 1, 1), {}, [f"k_conv_pw<{1 if m_ <= 16 else 2 if m_ <= 32 else 4}, 0>("])
+conv("pw_C33_M40_res_relu", (2, 33, 7, 9), (40, 33, 1, 1), {}, ["k_conv_pw<4, 0>("],
+     chain=[then("Add", x(2, 40, 7, 9)), then("Relu")])
+conv("pw_C3_M5_prelu_nobias", (2, 3, 7, 9), (5, 3, 1, 1), {}, ["k_conv_pw<1, 0>("], bias=False,
+     chain=[then("PRelu", _cw(5, 1, 1))])
+conv("pw_C200_M65", (2, 200, 90, 92), (65, 200, 1, 1), {}, ["k_conv_pw<4, 0>("])  # 130 x 2 x 2 = 520 workgroups
+# (515 x 2 64x64 tiles: under VSO_PW=0 this one is k_conv_gemm's, the others k_conv_small<true, ...>'s)
+conv("pw_C5_M10_181x182", (2, 5, 181, 182), (10, 5, 1, 1), {}, ["k_conv_pw<1, 0>("])
+
+# k_conv_pw<WM, 3 | 5>: a 3x3 / 5x5 depthwise -> 1x1 pair on at least 512 workgroups (514 to 520)
+conv("dwpw_pw1_3x3", (2, 5, 255, 258), (5, 1, 3, 3), {"group": 5, "pads": [1, 1, 1, 1]}, ["k_conv_pw<1, 3>("],
+     chain=[then("Relu"), pw_after(5, 10)])
+conv("dwpw_pw2_5x5", (2, 36, 181, 182), (36, 1, 5, 5), {"group": 36, "pads": [2, 2, 2, 2]}, ["k_conv_pw<2, 5>("],
+     chain=[CLIP6, pw_after(36, 20), then("Add", x(2, 20, 181, 182))])
+conv("dwpw_pw4_3x3", (2, 8, 90, 92), (8, 1, 3, 3), {"group": 8, "pads": [1, 1, 1, 1]}, ["k_conv_pw<4, 3>("],
+     bias=False, chain=[pw_after(8, 65), then("Relu")])
+conv("dwpw_pw4_3x3_s2", (2, 8, 180, 184), (8, 1, 3, 3), {"group": 8, "strides": [2, 2], "pads": [0, 0, 1, 1]},
+     ["k_conv_pw<4, 3>("], chain=[then("PRelu", _cw(8, 1, 1)), pw_after(8, 65)])
+conv("dwpw_pw2_3x3_pads0120", (2, 6, 183, 181), (6, 1, 3, 3), {"group": 6, "pads": [0, 1, 2, 0]}, ["k_conv_pw<2, 3>("],
+     chain=[then("LeakyRelu", alpha=0.1), pw_after(6, 20)])
+conv("dwpw_pw4_5x5_dil2", (2, 8, 90, 92), (8, 1, 5, 5), {"group": 8, "dilations": [2, 2], "pads": [4, 4, 4, 4]},
+     ["k_conv_pw<4, 5>("], chain=[then("Relu"), pw_after(8, 65), then("Add", x(2, 65, 90, 92)), CLIP6])
+conv("dwpw_pw1_5x5_s1x2", (2, 5, 255, 515), (5, 1, 5, 5), {"group": 5, "strides": [1, 2], "pads": [2, 2, 2, 2]},
+     ["k_conv_pw<1, 5>("], chain=[pw_after(5, 10, bias=False)])
+
+# k_conv_thin<1..4>: an ungrouped 1x1 onto at most 4 channels.  63 and 1089 pixels (odd), 80 and 1056
+# (float4 loads); above 1024 a second workgroup per image
+for m_, c_, hw_ in ((1, 5, (7, 9)), (2, 1, (8, 10)), (3, 256, (7, 9)), (4, 5, (33, 32)), (4, 256, (8, 10)),
+                    (2, 5, (33, 33)), (1, 256, (33, 32)), (3, 1, (33, 33))):
+    conv(f"thin_M{m_}_C{c_}_{_tag(hw_)}", (2, c_, *hw_), (m_, c_, 1, 1), {}, [f"k_conv_thin<{m_}>("])
+conv("thin_M4_C5_res_leaky", (2, 5, 7, 9), (4, 5, 1, 1), {}, ["k_conv_thin<4>("],
+     chain=[then("Add", x(2, 4, 7, 9)), then("LeakyRelu")])
+
+# the attributes (k_conv_small<false, 8, false>): auto_pad on odd (9x11) and even (10x12) planes, the
+# odd pad at the end (SAME_UPPER) or at the start (SAME_LOWER); auto_pad wins over pads; all omitted
+for ap_ in ("SAME_UPPER", "SAME_LOWER"):
+    for hw_ in (P9, (10, 12)):
+        conv(f"attr_{ap_}_s2_{_tag(hw_)}", (2, 3, *hw_), (5, 3, 3, 3), {"auto_pad": ap_, "strides": [2, 2]},
+             [small(False, 8, False)])
+    conv(f"attr_{ap_}_dil2", (2, 3, *P9), (5, 3, 3, 3), {"auto_pad": ap_, "dilations": [2, 2]},
+         [small(False, 8, False)])
+    conv(f"attr_{ap_}_2x2", (2, 3, *P9), (5, 3, 2, 2), {"auto_pad": ap_}, [small(False, 8, False)])
+    conv(f"attr_{ap_}_4x4_s3x2", (2, 2, 10, 12), (5, 2, 4, 4), {"auto_pad": ap_, "strides": [3, 2]},
+         [small(False, 8, False)])
+conv("attr_VALID", (2, 3, *P9), (5, 3, 3, 3), {"auto_pad": "VALID", "kernel_shape": [3, 3]}, [small(False, 8, False)])
+conv("attr_VALID_with_pads", (2, 3, *P9), (5, 3, 3, 3), {"auto_pad": "VALID", "pads": [1, 1, 1, 1]},
+     [small(False, 8, False)])
+conv("attr_SAME_UPPER_with_pads", (2, 3, *P9), (5, 3, 3, 3), {"auto_pad": "SAME_UPPER", "pads": [0, 0, 0, 0]},
+     [small(False, 8, False)])
+conv("attr_none", (2, 3, *P9), (5, 3, 3, 3), {}, [small(False, 8, False)])
+
+# ---------------------------------------------------------------------------
 # what the session refuses at creation (and the oracle refuses to evaluate)
 case("refuse_Resize_antialias", "refused", "Resize", _resize_inputs(scale=0.5), {"mode": "linear", "antialias": 1},
      opset=18, expect="refused")
@@ -345,6 +533,16 @@ case("refuse_PRelu_1d_channels", "refused", "PRelu", [x(*X), cf((3,), 41)], expe
 case("refuse_ConvPRelu_1d_channels", "refused", "Conv", [x(1, 3, 6, 5), cf((4, 3, 3, 3), 6), cf((4,), 7)],
      {"kernel_shape": [3, 3], "pads": [1, 1, 1, 1]}, post=("PRelu", cf((4,), 9)[1]), expect="refused")
 case("refuse_PRelu_wider_slope", "refused", "PRelu", [x(3, 1, 1), x(2, 3, 10, 11)], expect="refused")
+case("refuse_Conv_runtime_weights", "refused", "Conv", [x(2, 3, *P9), x(5, 3, 3, 3)], expect="refused")
+case("refuse_Conv_channels", "refused", "Conv", [x(2, 4, *P9), _cw(5, 3, 3, 3)], expect="refused")
+case("refuse_Conv_group_channels", "refused", "Conv", [x(2, 6, *P9), _cw(5, 3, 3, 3)], {"group": 2}, expect="refused")
+case("refuse_Conv_rank3", "refused", "Conv", [x(2, 3, 9), _cw(5, 3, 3)], expect="refused")
+case("refuse_Conv_empty_output", "refused", "Conv", [x(2, 3, 2, 2), _cw(5, 3, 3, 3)], expect="refused")
+case("refuse_Conv_pads_length", "refused", "Conv", [x(2, 3, *P9), _cw(5, 3, 3, 3)], {"pads": [1, 1]}, expect="refused")
+case("refuse_Conv_strides_length", "refused", "Conv", [x(2, 3, *P9), _cw(5, 3, 3, 3)], {"strides": [2]},
+     expect="refused")
+case("refuse_Conv_dilations_length", "refused", "Conv", [x(2, 3, *P9), _cw(5, 3, 3, 3)], {"dilations": [2]},
+     expect="refused")
 
 VALUE_CASES = [k for k in CASES if k.expect == "value"]
 REFUSED_CASES = [k for k in CASES if k.expect == "refused"]
@@ -364,6 +562,11 @@ def groups():
 def _input_name(cs: Case, pos_: int):
     kind, shape = cs.inputs[pos_]
     return f"{cs.family}_{kind}{pos_}_{_tag(shape)}_s{cs.seed}"
+
+
+def _chain_input_name(cs: Case, k: int, pos_: int):
+    kind, shape = cs.chain[k][1][pos_]
+    return f"{cs.family}_{kind}{k}.{pos_}_{_tag(shape)}_s{cs.seed}"
 
 
 def _generate(name, kind, shape):
@@ -389,23 +592,32 @@ def build(cases):
     assert all(k.opset == opset for k in cases)
     b = M.Builder(0)
     feeds, graph_in, graph_out, outs = {}, [], [], {}
+
+    def operand(spec, n):
+        if spec is None:
+            return ""
+        if spec[0] == "c":
+            return b.const(spec[1])
+        if n not in feeds:
+            feeds[n] = _generate(n, *spec)
+            graph_in.append((n, list(spec[1])))
+        return n
+
     for cs in cases:
-        names = []
-        for pos_, spec in enumerate(cs.inputs):
-            if spec is None:
-                names.append("")
-            elif spec[0] == "c":
-                names.append(b.const(spec[1]))
-            else:
-                n = _input_name(cs, pos_)
-                if n not in feeds:
-                    feeds[n] = _generate(n, *spec)
-                    graph_in.append((n, list(spec[1])))
-                names.append(n)
+        names = [operand(spec, spec and spec[0] != "c" and _input_name(cs, pos_)) for pos_, spec in enumerate(cs.inputs)]
         while names and names[-1] == "":
             names.pop()
         finals = output_names(cs)
-        if cs.post:
+        if cs.chain:
+            cur = b.name("mid")
+            b.nodes.append(R.make_node(cs.op, names, [cur], **cs.attrs))
+            for k, (op_, ins_, at_) in enumerate(cs.chain):
+                more = [operand(spec, spec and spec[0] != "c" and _chain_input_name(cs, k, pos_))
+                        for pos_, spec in enumerate(ins_)]
+                nxt = finals[0] if k + 1 == len(cs.chain) else b.name("mid")
+                b.nodes.append(R.make_node(op_, [cur] + more, [nxt], **at_))
+                cur = nxt
+        elif cs.post:
             mid = b.name("mid")
             b.nodes.append(R.make_node(cs.op, names, [mid], **cs.attrs))
             b.nodes.append(R.make_node(cs.post[0], [mid, b.const(cs.post[1])], finals))
@@ -423,3 +635,9 @@ def operands(cs: Case, feeds):
     for pos_, spec in enumerate(cs.inputs):
         out.append(None if spec is None else spec[1] if spec[0] == "c" else feeds[_input_name(cs, pos_)])
     return out
+
+
+def chain_operands(cs: Case, feeds):
+    """Per node of the case's chain: its further inputs as arrays, in operator order."""
+    return [[spec[1] if spec[0] == "c" else feeds[_chain_input_name(cs, k, pos_)] for pos_, spec in enumerate(ins_)]
+            for k, (_, ins_, _) in enumerate(cs.chain)]

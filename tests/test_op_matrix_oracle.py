@@ -2,7 +2,8 @@
 evaluation of every value case of the operator matrix (tests/op_cases.py):
 torch.nn.functional in double precision where torch has the operator, a
 direct numpy statement of the ONNX definition where it has not (asymmetric
-pads, the nearest modes, the coordinate transformations torch lacks).
+pads, the nearest modes, the coordinate transformations torch lacks).  Conv:
+torch's conv2d in double on an input padded here, the pads worked out here.
 Nothing here calls back into onnx_ref for the expected value.
 
 Bars: data movement, MaxPool and nearest Resize compare equal; the rest agree
@@ -218,7 +219,22 @@ def _pad_expected(cs, ops):
     return F.pad(_t(xv), flat, value=value).float().numpy()
 
 
-def expected(cs, ops):
+def _conv_f64(xt, w, b, at):
+    """ONNX Conv of a float64 tensor, rounded to float32 once: torch's conv2d in
+    double precision on an input padded here — explicit pads [top, left,
+    bottom, right], or auto_pad worked out by _same_pads (auto_pad wins)."""
+    import torch.nn.functional as F
+    s, d, ap = at.get("strides", [1, 1]), at.get("dilations", [1, 1]), at.get("auto_pad", "NOTSET")
+    if ap in ("SAME_UPPER", "SAME_LOWER"):
+        (t, bt), (l, r) = (_same_pads(xt.shape[2 + i], w.shape[2 + i], s[i], d[i], ap == "SAME_LOWER") for i in range(2))
+    else:
+        t, l, bt, r = [0, 0, 0, 0] if ap == "VALID" else at.get("pads", [0, 0, 0, 0])
+    y = F.conv2d(F.pad(xt, (l, r, t, bt)), _t(w), None if b is None else _t(b), stride=tuple(s), dilation=tuple(d),
+                 groups=at.get("group", 1))
+    return y.float().double()
+
+
+def expected(cs, ops, chain_ops=()):
     """Outputs of the case (a list), evaluated independently of onnx_ref."""
     import torch
     import torch.nn.functional as F
@@ -228,9 +244,26 @@ def expected(cs, ops):
         return [_pool_expected(cs, xv)]
     if op in ("Resize", "Upsample"):
         return [_resize_expected(cs, ops)]
-    if op == "Conv":  # + PRelu
-        y = F.conv2d(_t(xv), _t(ops[1]), _t(ops[2]), padding=1).float().double()  # the Conv's own float32 output
-        return [_f32(torch.where(y < 0, y * _t(cs.post[1]), y))]
+    if op == "Conv":  # then the nodes behind it
+        y = _conv_f64(_t(xv), ops[1], ops[2] if len(ops) > 2 else None, at)
+        follow = [(cs.post[0], [cs.post[1]], {})] if cs.post else \
+            [(op_, more, at_) for (op_, _, at_), more in zip(cs.chain, chain_ops)]
+        for op_, more, at_ in follow:
+            if op_ == "Conv":
+                y = _conv_f64(y, more[0], more[1] if len(more) > 1 else None, at_)
+            elif op_ == "Add":
+                y = y + _t(more[0])
+            elif op_ == "Relu":
+                y = F.relu(y)
+            elif op_ == "Clip":
+                y = torch.clamp(y, float(more[0]), float(more[1]))
+            elif op_ == "LeakyRelu":
+                y = F.leaky_relu(y, float(np.float32(at_.get("alpha", 0.01))))
+            else:
+                assert op_ == "PRelu", op_
+                y = torch.where(y < 0, y * _t(more[0]), y)
+            y = y.float().double()  # every node's own float32 output
+        return [_f32(y)]
     if op == "Relu":
         return [_f32(F.relu(_t(xv)))]
     if op == "LeakyRelu":
@@ -341,7 +374,7 @@ def _oracle_outputs(cs):
 def test_oracle_matches_independent_f64(name):
     cs = OC.BY_NAME[name]
     feeds, got = _oracle_outputs(cs)
-    want = expected(cs, OC.operands(cs, feeds))
+    want = expected(cs, OC.operands(cs, feeds), OC.chain_operands(cs, feeds))
     assert len(got) == len(want)
     for k, (g, w) in enumerate(zip(got, want)):
         assert g.dtype == np.float32 and w.dtype == np.float32, (name, k, g.dtype, w.dtype)
@@ -389,5 +422,15 @@ def test_matrix_covers_the_kernel_forms():
     """Each kernel form the GPU file asserts has a case that names it."""
     named = {k for cs in OC.VALUE_CASES for k in cs.kernels}
     for form in ("k_resize<true>(", "k_resize<false>(", "k_gap_wave(", "k_gap(", "k_gemm<true>(", "k_gemm<false>(",
-                 "k_binary_planes(", "k_binary(", "k_copy_rows<true>(", "k_copy_rows<false>(", "k_copy(", "k_affine("):
+                 "k_binary_planes(", "k_binary(", "k_copy_rows<true>(", "k_copy_rows<false>(", "k_copy(", "k_affine(",
+                 # the convolutions (k_conv_tile: tests/test_gpu_conv_tile_matrix.py)
+                 *(OC.small(pw, ch, split) for pw in (False, True) for ch, split in ((8, False), (16, False),
+                                                                                      (32, False), (16, True))),
+                 "k_conv_gemm(", "k_conv_dw(", "k_conv_dw_plane<1>(", "k_conv_dw_plane<2>(", "k_conv_dwpw(",
+                 *(f"k_conv_pw<{wm}, {dwk}>(" for wm in (1, 2, 4) for dwk in (0, 3, 5)),
+                 *(f"k_conv_thin<{m}>(" for m in (1, 2, 3, 4))):
         assert form in named, form
+    # the four-outputs-per-thread body inside k_conv_dw shares its launch name with the flat one
+    quad = OC.BY_NAME["Conv_dw_quad_body"]
+    n, c, h, w = quad.inputs[0][1]
+    assert quad.kernels == ("k_conv_dw(",) and n * c > 65535 and n * c * h * w // 4 >= 1024 * 256 and w % 4 == 0

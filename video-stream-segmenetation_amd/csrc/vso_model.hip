@@ -1182,10 +1182,16 @@ struct Planner {
     if (p.G < 1 || p.C != p.Cg * p.G || p.M % p.G) return fail("Conv '" + nd.name + "': channel/group mismatch");
     p.Mg = p.M / p.G;
     std::vector<int64_t> st = nd.ais("strides"), dl = nd.ais("dilations"), pd = nd.ais("pads");
-    p.sh = st.size() > 0 ? (int)st[0] : 1; p.sw = st.size() > 1 ? (int)st[1] : 1;
-    p.dh = dl.size() > 0 ? (int)dl[0] : 1; p.dw = dl.size() > 1 ? (int)dl[1] : 1;
-    int pt = pd.size() == 4 ? (int)pd[0] : 0, pl = pd.size() == 4 ? (int)pd[1] : 0;
-    int pb = pd.size() == 4 ? (int)pd[2] : 0, pr = pd.size() == 4 ? (int)pd[3] : 0;
+    // (absent, or one value per axis / per side: a shorter list would leave an axis at its default unnoticed)
+    if (!st.empty() && st.size() != 2) return fail("Conv '" + nd.name + "': strides must have 2 values");
+    if (!dl.empty() && dl.size() != 2) return fail("Conv '" + nd.name + "': dilations must have 2 values");
+    if (!pd.empty() && pd.size() != 4) return fail("Conv '" + nd.name + "': pads must have 4 values");
+    p.sh = st.empty() ? 1 : (int)st[0]; p.sw = st.empty() ? 1 : (int)st[1];
+    p.dh = dl.empty() ? 1 : (int)dl[0]; p.dw = dl.empty() ? 1 : (int)dl[1];
+    if (p.sh < 1 || p.sw < 1 || p.dh < 1 || p.dw < 1)
+      return fail("Conv '" + nd.name + "': strides and dilations must be positive");
+    int pt = pd.empty() ? 0 : (int)pd[0], pl = pd.empty() ? 0 : (int)pd[1];
+    int pb = pd.empty() ? 0 : (int)pd[2], pr = pd.empty() ? 0 : (int)pd[3];
     const std::string ap = nd.as("auto_pad", "NOTSET");
     if (ap == "SAME_UPPER" || ap == "SAME_LOWER") {
       const int in[2] = {p.H, p.W}, k[2] = {p.kh, p.kw}, s2[2] = {p.sh, p.sw}, d2[2] = {p.dh, p.dw};
