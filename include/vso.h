@@ -162,6 +162,20 @@ int vso_tile_conv_count(const vso_session* s);
  * MobileNetV2 backbone): k_ir in f32 sessions, k_ir_b16 (bf16 hi / lo splits
  * of both 1x1 operands, ~f32 precision) in bf16 / f16 ones, plus a
  * k_ir_reduce launch when the hidden channels are split over workgroups.
+ * A block fuses when its input channels are a multiple of 4, its hidden ones
+ * of 16, its depthwise is 3x3 / pads 1 / stride 1 or 2, and (CIN, COUT,
+ * stride) has a kernel instance.  f32, by (ceil(CIN / 16), ceil(COUT / 16),
+ * stride): (1,2,2) (2,2,1) (2,2,2) (2,4,2) (4,4,1) (4,6,1) (6,6,1) (6,10,2)
+ * (10,10,1) (10,20,1) (4,4,2) (6,6,2) — MobileNetV2's 16->24 s2, 24->24,
+ * 24->32 s2, 32->64 s2, 64->64, 64->96, 96->96, 96->160 s2, 160->160,
+ * 160->320, 64->64 s2, 96->96 s2 and every pair that rounds to the same
+ * steps (20->20, 28->49 s2, 148->305 ...).  bf16 / f16, by (ceil(CIN / 32),
+ * ceil(COUT / 16), stride): (1,2,2) (1,2,1) (1,4,2) (2,4,1) (2,6,1) (3,6,1)
+ * (3,10,2) (5,10,1) (5,20,1) (2,4,2) (3,6,2) — the same blocks, and 16->24
+ * and 48->64 at stride 1, which have no f32 instance (there the block runs as
+ * two or three generic launches).  A block whose project feeds the Add of a
+ * strided residual (MaxPool 2x2 [+ channel Pad] of the block's input:
+ * BlazeFace) is left to the generic plan, whose epilogue reads the pool's input.
  * Planning knobs, read once per process: VSO_IR=0 plans them as three
  * launches; VSO_IR_B16=0 keeps the f32 form in 16-bit sessions; VSO_IR_CPS
  * (default 6) hidden 16-channel chunks per slice of a 16-bit block. */

@@ -8,7 +8,7 @@ spec: "plain:f32,bf16,f16;up:bf16,f16" — the models and the precisions to
 run, one after another.  Writes an .npz to its standard output: every output
 of every session's first run (key "<model>/<precision>/<case>") and "info",
 the bytes of one JSON object {"<model>/<precision>": {"launches": [...],
-"tile_convs": n, "rerun_equal": bool}}.  A model "op_<family>" is that family
+"tile_convs": n, "ir_blocks": n, "rerun_equal": bool}}.  A model "op_<family>" is that family
 of the operator matrix (tests/op_cases.py), its outputs keyed by graph output
 name.  run_child() is the parent's side (tests/test_gpu_conv_tile_matrix.py,
 tests/test_gpu_op_matrix.py): it starts no further child once one has ended
@@ -64,7 +64,7 @@ def run_sessions(ort, spec):
                 for case, name in zip(cases, s.output_names):
                     outs[f"{model}/{prec}/{case}"] = got[name]
                 info[f"{model}/{prec}"] = {"launches": s.launches(), "tile_convs": s.tile_convs(),
-                                           "rerun_equal": all(np.array_equal(got[k], again[k]) for k in got)}
+                                           "ir_blocks": s.ir_blocks(), "rerun_equal": all(np.array_equal(got[k], again[k]) for k in got)}
     return outs, info
 
 

@@ -5,7 +5,8 @@ evaluation, CPU) and tests/test_gpu_op_matrix.py (the GPU session against the
 oracle).
 
 A case is one operator node (the conv family: with the nodes a session fuses
-behind it, `chain`): its attributes, its inputs in operator order
+behind it, `chain`; the ir family: one inverted-residual block, a chain whose
+nodes may name the case's input or each other): its attributes, its inputs in operator order
 (graph inputs filled from a seeded generator, or constants where the operator
 needs them constant), the model's opset, and whether the session must compute
 it ("value") or refuse it at creation ("refused").  build() packs any number
@@ -46,6 +47,12 @@ class Case:
     # further nodes, each on the output of the one before: (op, its further inputs (as `inputs`), attributes);
     # the last one's output is the case's (the conv family's pairs and epilogues)
     chain: tuple = ()
+    # a chain operand may also be ("in", k): the case's own input k, or ("node", j): the output of the case's
+    # node j (0: its operator, j: chain[j - 1]).  A chain node may carry a fourth element, {"whole": its
+    # inputs are all listed, ("prev",) standing for the node before; "out": its output is one more graph
+    # output of the case, ahead of the last node's}.
+    kernels16: tuple = ()   # `kernels` of a bf16 / f16 session (the ir family, whose fused forms differ by precision)
+    echo: bool = False      # the case's input 0 is a graph output too (the first of the case's)
 
 
 CASES: list[Case] = []
@@ -76,6 +83,13 @@ def cf(shape, seed, lo=None):
     """A seeded float32 constant: standard normal, or uniform in [lo, lo + 1)."""
     rng = np.random.default_rng(1000 + seed)
     a = rng.standard_normal(shape) if lo is None else rng.random(shape) + lo
+    return ("c", a.astype(np.float32))
+
+
+def wf(shape, seed, fan_in=None):
+    """A seeded float32 constant of the ir family: a weight, standard normal / sqrt(fan_in), or a bias
+    (no fan_in), 0.1 * standard normal."""
+    a = np.random.default_rng(2000 + seed).standard_normal(shape) * (0.1 if fan_in is None else fan_in ** -0.5)
     return ("c", a.astype(np.float32))
 
 
@@ -505,6 +519,186 @@ conv("attr_SAME_UPPER_with_pads", (2, 3, *P9), (5, 3, 3, 3), {"auto_pad": "SAME_
 conv("attr_none", (2, 3, *P9), (5, 3, 3, 3), {}, [small(False, 8, False)])
 
 # ---------------------------------------------------------------------------
+# The MobileNetV2 inverted residual, one block per case: Conv 1x1 -> Clip -> Conv 3x3 depthwise -> Clip ->
+# Conv 1x1 [-> Add], fused by try_plan_ir (vso_model.hip) into one launch of k_ir (f32 sessions) or k_ir_b16
+# (bf16 / f16 sessions), plus k_ir_reduce where the hidden channels are split into slices (vso_ir.hip).
+# ir_entry() picks the instance by (ceil(CIN / 16) in f32 | ceil(CIN / 32) in 16 bits, ceil(COUT / 16), stride).
+#
+# Planes: the 4 x 16 output tile's every tail on the smallest plane — 5 x 18 outputs (2 x 2 tiles, a 1-row
+# and a 2-column tail) from 5 x 18 at stride 1, from 9 x 35 (odd) or 10 x 36 (even) at stride 2.
+#
+# Slices, written per case as (f32, b16), from try_plan_ir / ir_slab_plan under default knobs, wg0 = N * tiles
+# workgroups per slice and nch = HID / 16 chunks:
+#   f32: ks = min(nch, (512 + wg0 / 2) / wg0), cps = ceil(nch / ks), slices = ceil(nch / cps).  wg0 = 8 (batch
+#        2 on 5 x 18) gives ks = min(nch, 64): one chunk per slice, nch slices.
+#   b16: ks = ceil(nch / 6); below 256 workgroups ks = min(nch, ceil(256 / wg0)); cps = ceil(nch / ks), made even
+#        unless it is all of nch; then cps drops by 2 while the slab and the hidden planes exceed 160 KiB of
+#        LDS; slices = ceil(nch / cps).  wg0 = 8 gives chunk pairs: ceil(nch / 2) slices.
+# Weights are 1 / sqrt(fan-in) normals (wf): standard-normal ones saturate the clips.
+_ir_seed = [0]
+PREV, IN0 = ("prev",), ("in", 0)
+PW4, DWPW = "k_conv_pw<4, 0>(", "k_conv_dwpw("
+ADD = ("k_binary(",)
+
+
+def _iw(shape, fan_in=None):
+    _ir_seed[0] += 1
+    return wf(shape, _ir_seed[0], fan_in)
+
+
+def node(op_, ins, **attrs):
+    """A chain node with all its inputs listed (PREV: the node before it)."""
+    return (op_, tuple(ins), attrs, {"whole": True})
+
+
+def also_out(nd):
+    """The chain node, its output one more graph output of the case."""
+    return nd[:3] + (dict(nd[3] if len(nd) > 3 else {}, out=True),)
+
+
+def clip(lo, hi, attr=False):
+    """Clip to [lo, hi], either bound None for absent; attr: as attributes (before opset 11)."""
+    if attr:
+        return then("Clip", **{k: v for k, v in (("min", lo), ("max", hi)) if v is not None})
+    ins = [None if lo is None else c(lo, np.float32), None if hi is None else c(hi, np.float32)]
+    while ins and ins[-1] is None:
+        ins.pop()
+    return then("Clip", *ins)
+
+
+def ir_launches(form, cin, cout, s, slices):
+    """The launches of a fused block: its kernel instance, and k_ir_reduce above one slice."""
+    nt = -(-cin // (16 if form == "k_ir" else 32))
+    tail = ">(" if form == "k_ir_b16w" else ", 4>("
+    return (f"{form}<{nt}, {-(-cout // 16)}, {s}{tail}",) + (("k_ir_reduce(",) if slices > 1 else ())
+
+
+def ir(name, cin, cout, hw, f32, b16, s=1, hid=None, n=2, res=False, clips=((0.0, 6.0), (0.0, 6.0)),
+       bias=(True, True, True), dw=None, k=3, ex=None, act1=None, tail=None, outs=(), after=(), after16=None,
+       attr_clips=False, dw_gain=1.0, family="ir", **kw):
+    """One block on a graph input [n, cin, *hw].  f32 / b16: the slices of the fused form in an f32 / a 16-bit
+    session, or the launches of the generic plan where the block is not fused; `after`: further launches in
+    both (after16: in a 16-bit session, where they differ).  `tail`: the nodes behind the project instead of
+    the residual Add; `outs`: chain nodes whose outputs are graph outputs too; dw / ex: the depthwise's / the
+    expand's attributes; act1: the first activation; dw_gain: the depthwise's weights times that (where
+    1 / sqrt(9) leaves too few outputs inside the second Clip)."""
+    hid = hid or 6 * cin
+    dw_at = dw if dw is not None else {"group": hid, "strides": [s, s], "pads": [1, 1, 1, 1]}
+    chain = [act1 or clip(*clips[0], attr=attr_clips),
+             then("Conv", _iw((hid, 1, k, k), k * k / dw_gain ** 2), *([_iw((hid,))] if bias[1] else []), **dw_at),
+             clip(*clips[1], attr=attr_clips),
+             then("Conv", _iw((cout, hid, 1, 1), hid), *([_iw((cout,))] if bias[2] else []))]
+    chain += list(tail) if tail is not None else [then("Add", IN0)] if res else []
+    for j in outs:
+        chain[j] = also_out(chain[j])
+    launches = [ir_launches(form, cin, cout, s, v) if isinstance(v, int) else tuple(v)
+                for form, v in (("k_ir", f32), ("k_ir_b16", b16))]
+    case(f"IR_{name}", family, "Conv",
+         [x(n, cin, *hw), _iw((hid, cin, 1, 1), cin)] + ([_iw((hid,))] if bias[0] else []), ex or {},
+         kernels=launches[0] + tuple(after), kernels16=launches[1] + tuple(after if after16 is None else after16),
+         chain=tuple(chain), n_out=1 + len(outs), **kw)
+
+
+S1, ODD, EVEN = (5, 18), (9, 35), (10, 36)
+# one case per entry of kIr / kIr16, expansion 6; the last four channel pairs on 3 x 5 outputs (one tile: two
+# workgroups, up to 60 slices)
+ir("16_24_s2", 16, 24, ODD, 6, 3, s=2)
+ir("16_24_s2_even", 16, 24, EVEN, 6, 3, s=2)
+ir("24_24_res", 24, 24, S1, 9, 5, res=True)
+ir("24_32_s2", 24, 32, ODD, 9, 5, s=2)
+ir("32_64_s2_even", 32, 64, EVEN, 12, 6, s=2)
+ir("64_64_res", 64, 64, S1, 24, 12, res=True)
+ir("64_96", 64, 96, S1, 24, 12)
+ir("96_96_res", 96, 96, S1, 36, 18, res=True)
+ir("96_160_s2", 96, 160, ODD, 36, 18, s=2)
+ir("160_160_res_3x5", 160, 160, (3, 5), 60, 30, res=True)
+ir("160_320_3x5", 160, 320, (3, 5), 60, 30)
+# 26 images: 10 slices of 6 chunks reach 256 workgroups, and 6 chunks of 160 -> 320 weights exceed the LDS
+# budget — ir_slab_plan steps down 6 -> 4 -> 2 chunks, 30 slices.  f32: (512 + 13) / 26 = 20 slices of 3.
+ir("160_320_3x5_n26", 160, 320, (3, 5), 20, 30, n=26)
+ir("64_64_s2_3x5", 64, 64, (5, 9), 24, 12, s=2)
+ir("96_96_s2_3x5_even", 96, 96, (6, 10), 36, 18, s=2)
+# channel tails: CIN off the 16 / 32 steps (the zero fill past CIN), COUT off 16 (the ch < COUT tails); HID a
+# multiple of 16 near 6 CIN, an odd chunk count where it can be (7, 19, 31, 55 chunks)
+ir("20_20_res", 20, 20, S1, 7, 4, hid=112, res=True)
+ir("28_49_s2", 28, 49, ODD, 10, 5, hid=160, s=2)
+ir("52_52_res", 52, 52, S1, 19, 10, hid=304, res=True)
+ir("84_81", 84, 81, S1, 31, 16, hid=496)
+ir("148_305", 148, 305, S1, 55, 28, hid=880)
+ir("4_17_s2_hid16", 4, 17, EVEN, 1, 1, hid=16, s=2)
+# forms that differ by precision: no f32 instance <1, 2, 1> / <3, 4, 1>, b16 instances <1, 2, 1> / <2, 4, 1>.
+# f32: the expand on k_conv_pw, the depthwise inside the project's k_conv_dwpw (HID 96), or on its own ahead of
+# a k_conv_small project (HID 288: above k_conv_dwpw's 256 channels, and a 1x1 of more than 192 channels on
+# few workgroups)
+ir("16_24_s1", 16, 24, S1, (PW4, DWPW), 3)
+ir("48_64_s1", 48, 64, S1, (PW4, "k_conv_dw(", small(True, 16, True)), 9)
+# hidden width: one chunk (the b16 forms project a half-empty pair), three (a pair and a tail), and nine on a
+# plane of 9 x 19 tiles — f32: 342 workgroups, (512 + 171) / 342 = 1 slice of nine chunks; b16: ceil(9 / 6) = 2
+# slices, of 6 and 3 chunks
+ir("24_24_res_hid16", 24, 24, S1, 1, 1, hid=16, res=True)
+ir("24_24_res_hid48", 24, 24, S1, 3, 2, hid=48, res=True)
+ir("24_24_res_hid144_36x304", 24, 24, (36, 304), 1, 2, res=True)
+# clips: a lower bound above 0 (the depthwise pads with 0, not with the clipped 0), two ranges that differ
+# (lo1 / hi1 against lo2 / hi2), one bound, none, attributes
+ir("24_24_res_clip0.5_4", 24, 24, S1, 9, 5, res=True, clips=((0.5, 4.0), (0.5, 4.0)), dw_gain=3.0)
+ir("24_24_res_clips_differ", 24, 24, S1, 9, 5, res=True, clips=((-0.5, 2.0), (0.25, 5.0)))
+ir("24_24_res_clip_min_only", 24, 24, S1, 9, 5, res=True, clips=((-1.0, None), (-1.0, None)))
+ir("24_24_res_clip_none", 24, 24, S1, 9, 5, res=True, clips=((None, None), (None, None)))
+ir("24_24_res_clip_attr", 24, 24, S1, 9, 5, res=True, attr_clips=True, family="ir6", opset=6)
+# bias
+ir("24_24_res_nobias", 24, 24, S1, 9, 5, res=True, bias=(False, False, False))
+ir("24_32_s2_nobias_dw", 24, 32, EVEN, 9, 5, s=2, bias=(True, False, True))
+# the residual and the outputs.  Fused with the residual: Add(x, project) too, and a block input that is a graph
+# output.  Fused without (the Add its own k_binary launch): a project output that is a graph output, Add(project,
+# project), Add(project, another input).  Two blocks in a row, both outputs read.
+ir("24_24_res_swapped", 24, 24, S1, 9, 5, tail=[node("Add", [IN0, PREV])])
+ir("24_24_res_input_out", 24, 24, S1, 9, 5, res=True, echo=True, seed=1)
+ir("24_24_res_project_out", 24, 24, S1, 9, 5, res=True, outs=(3,), after=ADD)
+ir("24_24_add_self", 24, 24, S1, 9, 5, tail=[node("Add", [PREV, PREV])], after=ADD)
+ir("24_24_add_other", 24, 24, S1, 9, 5, tail=[then("Add", x(2, 24, *S1))], after=ADD)
+
+
+def _second_block(cin, hid):
+    """A second 24 -> 24 block behind the first one's Add (chain node 5), its residual from there."""
+    return [then("Conv", _iw((hid, cin, 1, 1), cin), _iw((hid,))), clip(0.0, 6.0),
+            then("Conv", _iw((hid, 1, 3, 3), 9), _iw((hid,)), group=hid, pads=[1, 1, 1, 1]), clip(0.0, 6.0),
+            then("Conv", _iw((cin, hid, 1, 1), hid), _iw((cin,))), then("Add", ("node", 5))]
+
+
+ir("24_24_res_twice", 24, 24, S1, 9, 5, tail=[then("Add", IN0)] + _second_block(24, 144), outs=(4,),
+   after=ir_launches("k_ir", 24, 24, 1, 9), after16=ir_launches("k_ir_b16", 24, 24, 1, 5))
+# planes and batch: one pixel, one row, one whole tile, one column; stride 2 from 1 x 1 and 2 x 2; batch 1, 3
+# (wg0 = N * tiles stays far below 512 / 9: nch slices in f32, chunk pairs in b16)
+for hw_ in ((1, 1), (1, 17), (4, 16), (5, 1)):
+    ir(f"24_24_res_{_tag(hw_)}", 24, 24, hw_, 9, 5, res=True)
+ir("16_24_s2_1x1", 16, 24, (1, 1), 6, 3, s=2)
+ir("16_24_s2_2x2", 16, 24, (2, 2), 6, 3, s=2)
+ir("24_24_res_n1", 24, 24, S1, 9, 5, n=1, res=True)
+ir("24_24_res_n3", 24, 24, S1, 9, 5, n=3, res=True)
+# near misses: graphs try_plan_ir must leave to the generic plan — the expand on k_conv_pw (a strided one on
+# k_conv_small), the depthwise inside the project's k_conv_dwpw (the residual Add in its epilogue)
+GEN = (PW4, DWPW)
+ir("miss_dw_SAME_UPPER_s2", 24, 32, EVEN, GEN, GEN, s=2, dw={"group": 144, "strides": [2, 2], "auto_pad": "SAME_UPPER"})
+ir("miss_dw_pads0110", 24, 32, S1, GEN, GEN, dw={"group": 144, "pads": [0, 1, 1, 0]})
+ir("miss_dw_dil2", 24, 24, S1, GEN, GEN, dw={"group": 144, "dilations": [2, 2], "pads": [2, 2, 2, 2]}, res=True)
+ir("miss_dw_5x5", 24, 24, S1, GEN, GEN, k=5, dw={"group": 144, "pads": [2, 2, 2, 2]}, res=True)
+ir("miss_dw_s2x1", 24, 32, EVEN, GEN, GEN, dw={"group": 144, "strides": [2, 1], "pads": [1, 1, 1, 1]})
+ir("miss_relu_first", 24, 24, S1, GEN, GEN, act1=then("Relu"), res=True)
+ir("miss_clip1_out", 24, 24, S1, GEN, GEN, res=True, outs=(0,))
+ir("miss_expand_s2", 24, 32, EVEN, (small(False, 8, False), DWPW), (small(False, 8, False), DWPW), ex={"strides": [2, 2]})
+ir("miss_hid40", 24, 24, S1, GEN, GEN, hid=40, res=True)
+ir("miss_cin18", 18, 24, S1, GEN, GEN, hid=96)
+# 48 -> 48: <3, 3, 1> and <2, 3, 1> are in neither table (HID 288: as IR_48_64_s1 in f32)
+ir("miss_48_48_res", 48, 48, S1, (PW4, "k_conv_dw(", small(True, 16, True)),
+   (PW4, "k_conv_dw(", small(True, 16, True)), res=True)
+# BlazeFace's strided residual around a stride-2 block: Add(project, [Pad(] MaxPool2x2(x) [)]).  The pool and the
+# pad are find_residual_fusions' (read in the project's epilogue): the block is left to the generic plan
+POOL = node("MaxPool", [IN0], kernel_shape=[2, 2], strides=[2, 2])
+ir("miss_pool_residual", 64, 64, EVEN, GEN, GEN, s=2, hid=128, tail=[POOL, node("Add", [("node", 4), PREV])])
+ir("miss_pool_pad_residual", 16, 24, EVEN, GEN, GEN, s=2,
+   tail=[POOL, then("Pad", ci(0, 0, 0, 0, 0, 8, 0, 0)), node("Add", [("node", 4), PREV])])
+
+# ---------------------------------------------------------------------------
 # what the session refuses at creation (and the oracle refuses to evaluate)
 case("refuse_Resize_antialias", "refused", "Resize", _resize_inputs(scale=0.5), {"mode": "linear", "antialias": 1},
      opset=18, expect="refused")
@@ -605,18 +799,26 @@ def build(cases):
 
     for cs in cases:
         names = [operand(spec, spec and spec[0] != "c" and _input_name(cs, pos_)) for pos_, spec in enumerate(cs.inputs)]
+        made = []  # the outputs of the case's nodes, in order
+
+        def chain_operand(spec, k, pos_):
+            if spec and spec[0] in ("prev", "in", "node"):
+                return made[-1] if spec[0] == "prev" else names[spec[1]] if spec[0] == "in" else made[spec[1]]
+            return operand(spec, spec and spec[0] != "c" and _chain_input_name(cs, k, pos_))
+
         while names and names[-1] == "":
             names.pop()
         finals = output_names(cs)
         if cs.chain:
-            cur = b.name("mid")
-            b.nodes.append(R.make_node(cs.op, names, [cur], **cs.attrs))
-            for k, (op_, ins_, at_) in enumerate(cs.chain):
-                more = [operand(spec, spec and spec[0] != "c" and _chain_input_name(cs, k, pos_))
-                        for pos_, spec in enumerate(ins_)]
-                nxt = finals[0] if k + 1 == len(cs.chain) else b.name("mid")
-                b.nodes.append(R.make_node(op_, [cur] + more, [nxt], **at_))
-                cur = nxt
+            extra = iter(finals[:-1])
+            made.append(b.name("mid"))
+            b.nodes.append(R.make_node(cs.op, names, [made[0]], **cs.attrs))
+            for k, nd in enumerate(cs.chain):
+                (op_, ins_, at_), opts = nd[:3], nd[3] if len(nd) > 3 else {}
+                more = [chain_operand(spec, k, pos_) for pos_, spec in enumerate(ins_)]
+                nxt = finals[-1] if k + 1 == len(cs.chain) else next(extra) if opts.get("out") else b.name("mid")
+                b.nodes.append(R.make_node(op_, more if opts.get("whole") else [made[-1]] + more, [nxt], **at_))
+                made.append(nxt)
         elif cs.post:
             mid = b.name("mid")
             b.nodes.append(R.make_node(cs.op, names, [mid], **cs.attrs))
@@ -624,7 +826,7 @@ def build(cases):
         else:
             b.nodes.append(R.make_node(cs.op, names, finals, **cs.attrs))
         # MaxPool's Indices are asked for by naming them; only the values are graph outputs
-        outs[cs.name] = finals[:1] if cs.op == "MaxPool" else finals
+        outs[cs.name] = finals[:1] if cs.op == "MaxPool" else ([names[0]] if cs.echo else []) + finals
         graph_out += [(o, []) for o in outs[cs.name]]
     return b.model(graph_in, graph_out, opset=opset), feeds, outs
 
@@ -639,5 +841,8 @@ def operands(cs: Case, feeds):
 
 def chain_operands(cs: Case, feeds):
     """Per node of the case's chain: its further inputs as arrays, in operator order."""
-    return [[spec[1] if spec[0] == "c" else feeds[_chain_input_name(cs, k, pos_)] for pos_, spec in enumerate(ins_)]
-            for k, (_, ins_, _) in enumerate(cs.chain)]
+    def one(spec, k, pos_):
+        if spec[0] in ("prev", "in", "node"):  # a reference to another value of the case: left as written
+            return spec
+        return spec[1] if spec[0] == "c" else feeds[_chain_input_name(cs, k, pos_)]
+    return [[one(spec, k, pos_) for pos_, spec in enumerate(nd[1])] for k, nd in enumerate(cs.chain)]

@@ -23,9 +23,18 @@ at a time, none started after an abnormal end.  One form has no case:
 k_conv_dw's conv_dw_body<long> needs 2^30 outputs.  Measured errors per kernel
 form and three deliberate breaks these tests catch: profiles/NOTES.md, "Conv
 operator matrix".
+
+The ir family (one MobileNetV2 inverted residual per case, csrc/vso_ir.hip)
+runs in f32 with the other families — k_ir and k_ir_reduce by `kernels`, the
+near misses on the generic plan — and here in bf16 and f16 sessions
+(`kernels16`: k_ir_b16; one oracle, no operand of the family is rounded) and
+under each of try_plan_ir's knobs in a child process.  Figures and three
+breaks of vso_ir.hip that only these tests catch: profiles/NOTES.md, "IR
+block matrix".
 """
 import math
 import re
+import time
 
 import numpy as np
 import pytest
@@ -115,34 +124,37 @@ def _conv_oracle(prec):
     return _conv[prec]
 
 
-def _per_case(launches):
+def _per_case(launches, cases=CONV, field="kernels"):
     """{case: its launches} of a session of the whole family: the launches come
-    in node order, len(case.kernels) for each case."""
-    assert len(launches) == sum(len(cs.kernels) for cs in CONV), launches
+    in node order, len(case.kernels) (or of another `field`) for each case."""
+    assert len(launches) == sum(len(getattr(cs, field)) for cs in cases), launches
     out, k = {}, 0
-    for cs in CONV:
-        assert cs.kernels, cs.name
-        out[cs.name] = launches[k:k + len(cs.kernels)]
-        k += len(cs.kernels)
+    for cs in cases:
+        assert getattr(cs, field), cs.name
+        out[cs.name] = launches[k:k + len(getattr(cs, field))]
+        k += len(getattr(cs, field))
     return out
 
 
-def _beyond_bar(got, want, label, names):
-    """The family's outputs against the oracle's at the matrix's bar; the worst
-    err / bar per kernel form (as launched: `names`, from _per_case) is printed."""
+def _beyond_bar(got, want, label, names, cases=CONV, outs=None):
+    """The family's outputs (`outs`: {case: its graph outputs}, one of the case's name if None)
+    against the oracle's at the matrix's bar; the worst err / bar per kernel
+    form (as launched: `names`, from _per_case) is printed."""
     failures, worst = [], {}
-    for cs in CONV:
-        g, w = got[cs.name], want[cs.name]
-        if g.shape != w.shape:
-            failures.append(f"{cs.name}: shape {g.shape}, oracle {w.shape}")
-            continue
-        err = np.abs(g.astype(np.float64) - w)
-        ratio = float((err / (TOL * np.maximum(1.0, np.abs(w)))).max())
-        print(f"{label} {cs.name}: max abs err {float(err.max()):.3e}, err / bar {ratio:.3f}")
-        if not (err <= TOL * np.maximum(1.0, np.abs(w))).all():
-            bad = ~(err <= TOL * np.maximum(1.0, np.abs(w)))
-            failures.append(f"{cs.name}: {int(bad.sum())} elements beyond {TOL:g} * max(1, |want|), "
-                            f"worst {float(err.max()):.3e}")
+    for cs in cases:
+        ratio = 0.0
+        for o in outs[cs.name] if outs else [cs.name]:
+            g, w = got[o], want[o]
+            if g.shape != w.shape:
+                failures.append(f"{o}: shape {g.shape}, oracle {w.shape}")
+                continue
+            err = np.abs(g.astype(np.float64) - w)
+            ratio = max(ratio, float((err / (TOL * np.maximum(1.0, np.abs(w)))).max()))
+            print(f"{label} {o}: max abs err {float(err.max()):.3e}, err / bar {ratio:.3f}")
+            if not (err <= TOL * np.maximum(1.0, np.abs(w))).all():
+                bad = ~(err <= TOL * np.maximum(1.0, np.abs(w)))
+                failures.append(f"{o}: {int(bad.sum())} elements beyond {TOL:g} * max(1, |want|), "
+                                f"worst {float(err.max()):.3e}")
         form = " + ".join(re.search(r"k_\w+(<[^>]*>)?", n).group(0) for n in names[cs.name])
         worst[form] = max(worst.get(form, 0.0), ratio)
     for form, ratio in sorted(worst.items()):
@@ -239,4 +251,153 @@ def test_conv_family_knob_off(ort, conv_f32, knob):
                             f"{float(np.abs(got[cs.name] - f32_out[cs.name]).max()):.3e}")
     if knob == "VSO_PW":  # both fallbacks are reached
         assert {_pw_fallback(cs) for cs in moved} >= {"k_conv_gemm(", OC.small(True, 8, False), OC.small(True, 16, True)}
+    assert not failures, "\n".join(failures)
+
+
+# ---- the ir family: 16-bit sessions and the planner's knobs ---------------------
+IR_FAMILIES = ("ir", "ir6")  # (one opset per model: the attribute-form Clips are a family of their own)
+IR = [cs for fam in IR_FAMILIES for cs in OC.groups()[fam]]
+IR_FUSED16 = [cs for cs in IR if "k_ir" in cs.kernels16[0]]
+_ir = {}
+
+
+def _ir_models():
+    """{family: (model, feeds, {case: its graph outputs})}, and the f64 oracle's outputs of both
+    (no convolution of the family is one onnx_ref.tiled_conv rounds: one oracle for every precision)."""
+    if "models" not in _ir:
+        _ir["models"] = {fam: OC.build(OC.groups()[fam]) for fam in IR_FAMILIES}
+        _ir["outs"] = {k: v for m in _ir["models"].values() for k, v in m[2].items()}
+        _ir["want"] = {k: v for data, feeds, _ in _ir["models"].values() for k, v in R.run(R.load(data), feeds).items()}
+    return _ir["models"]
+
+
+def _ir_sessions(ort, prec):
+    """(outputs, launches in order, ir_blocks, whether a second run was bitwise the same) of both
+    families' sessions in this process, once per precision."""
+    if prec not in _ir:
+        got, launches, blocks, same = {}, [], 0, True
+        t0 = time.perf_counter()
+        for fam, (data, feeds, _) in _ir_models().items():
+            with ort.InferenceSession(data, precision=prec) as s:
+                out = s.run(feeds)
+                again = s.run(feeds)
+                same = same and all(np.array_equal(out[k], again[k], equal_nan=True) for k in out)
+                got.update(out)
+                launches += s.launches()
+                blocks += s.ir_blocks()
+        print(f"ir family, {prec} sessions: {time.perf_counter() - t0:.2f} s, {len(launches)} launches")
+        _ir[prec] = (got, launches, blocks, same)
+    return _ir[prec]
+
+
+def _expect_launches(names, expect, failures):
+    """Each case's launches against the parts of their names in `expect` ({case: tuple})."""
+    for cs in IR:
+        if len(names[cs.name]) != len(expect[cs.name]) or not all(k in n for k, n in zip(expect[cs.name], names[cs.name])):
+            failures.append(f"{cs.name}: launched {names[cs.name]}, expected {expect[cs.name]}")
+
+
+@pytest.mark.parametrize("prec", ["bf16", "f16"])
+def test_ir_family_16bit(ort, prec):
+    """A bf16 / f16 session of the whole family: every case at the bar against
+    the f64 oracle, on the launches it writes down (kernels16), a second run
+    bitwise the same, ir_blocks() the number of fused cases' blocks — and the
+    two precisions bitwise equal (k_ir_b16 splits into bf16 in both)."""
+    _ir_models()
+    got, launches, blocks, same = _ir_sessions(ort, prec)
+    names = _per_case(launches, IR, "kernels16")
+    failures = _beyond_bar(got, _ir["want"], prec, names, IR, _ir["outs"])
+    _expect_launches(names, {cs.name: cs.kernels16 for cs in IR}, failures)
+    assert same, "the second run differs from the first"
+    assert blocks == sum(sum("k_ir_b16<" in k for k in cs.kernels16) for cs in IR), blocks
+    other = _ir_sessions(ort, "f16" if prec == "bf16" else "bf16")[0]
+    for o, g in got.items():
+        if not np.array_equal(g, other[o], equal_nan=True):
+            failures.append(f"{o}: the bf16 and f16 sessions differ")
+    assert not failures, "\n".join(failures)
+
+
+def _drop_reduce(cs, field, keep=()):
+    return tuple(k for k in getattr(cs, field) if k != "k_ir_reduce(" or cs.name in keep)
+
+
+# VSO_IR_KS1=1 (one slice from one workgroup on): a case keeps k_ir_reduce where all its chunks' weights do not
+# fit the 160 KiB of LDS beside the hidden planes — ir_slab_plan steps the slice down two chunks at a time.  By
+# its arithmetic (slab = 2 cps 16 (4 ceil(CIN / 32) + 2) 16 + 2 ceil(COUT / 16) 16 (4 ceil(cps / 2) + 2) 16 + 44
+# cps 16 bytes, + 14336 at stride 1 | 39040 at stride 2): every case of HID >= 288 here; HID <= 192 fits whole.
+KS1_KEEPS = {"IR_64_64_res", "IR_64_96", "IR_96_96_res", "IR_96_160_s2", "IR_160_160_res_3x5", "IR_160_320_3x5",
+             "IR_160_320_3x5_n26", "IR_64_64_s2_3x5", "IR_96_96_s2_3x5_even", "IR_52_52_res", "IR_84_81", "IR_148_305",
+             "IR_48_64_s1"}
+
+
+def _wave(cs):
+    """kernels16 under VSO_IR_WAVE=1: k_ir_b16w for the fused cases of at most 64 input channels
+    (each of their forms is in kIr16w), the same slices."""
+    if cs not in IR_FUSED16 or cs.inputs[0][1][1] > 64:
+        return cs.kernels16
+    return tuple(re.sub(r"k_ir_b16<(\d+, \d+, \d), 4>\(", r"k_ir_b16w<\1>(", k) for k in cs.kernels16)
+
+
+IR_KNOBS = {
+    # setting: (session precision, {case: launches})
+    "VSO_IR=0": ("f32", None),
+    "VSO_IR_WGS=1": ("f32", lambda cs: _drop_reduce(cs, "kernels")),
+    "VSO_IR_B16=0": ("bf16", lambda cs: cs.kernels),
+    "VSO_IR_WAVE=1": ("bf16", _wave),
+    "VSO_IR_KS1=1": ("bf16", lambda cs: _drop_reduce(cs, "kernels16", KS1_KEEPS)),
+    # the workgroup target alone ((512 + wg0 / 2) / wg0 slices, then whole pairs): the slices of the default
+    # but on the 36 x 304 plane (342 workgroups: one slice)
+    "VSO_IR_CPS=0": ("bf16", lambda cs: cs.kernels16[:1] if cs.name == "IR_24_24_res_hid144_36x304" else cs.kernels16),
+}
+
+
+@pytest.mark.parametrize("setting", sorted(IR_KNOBS))
+def test_ir_family_knob(ort, setting):
+    """The family under one setting of try_plan_ir's knobs (read once per
+    process: a child process each, one at a time, none after an abnormal end):
+    every case at the bar, on the launches the setting implies.  VSO_IR_B16=0
+    in a bf16 session is the f32 session bitwise (the same kernels on the same
+    operands); VSO_IR_WAVE=1 is the default bf16 session bitwise (k_ir_b16w:
+    the same operands, products and sums as k_ir_b16)."""
+    prec, expect = IR_KNOBS[setting]
+    _ir_models()
+    knob, value = setting.split("=")
+    t0 = time.perf_counter()
+    outs, info = C.run_child(setting, {knob: value}, ";".join(f"op_{fam}:{prec}" for fam in IR_FAMILIES))
+    print(f"ir family, {setting} {prec} child: {time.perf_counter() - t0:.2f} s")
+    got = {o: outs[f"op_{cs.family}/{prec}/{o}"] for cs in IR for o in _ir["outs"][cs.name]}
+    launches = [n for fam in IR_FAMILIES for n in info[f"op_{fam}/{prec}"]["launches"]]
+    blocks = sum(info[f"op_{fam}/{prec}"]["ir_blocks"] for fam in IR_FAMILIES)
+    assert all(info[f"op_{fam}/{prec}"]["rerun_equal"] for fam in IR_FAMILIES)
+    failures = []
+    if expect is None:  # no fused block: the launches are the generic plan's, whatever their number
+        assert blocks == 0 and launches and not any("k_ir" in n for n in launches), launches
+        for cs in IR:
+            for o in _ir["outs"][cs.name]:
+                err = np.abs(got[o].astype(np.float64) - _ir["want"][o])
+                if not (err <= TOL * np.maximum(1.0, np.abs(_ir["want"][o]))).all():
+                    failures.append(f"{o}: beyond the bar, worst {float(err.max()):.3e}")
+    else:
+        want_names = {cs.name: expect(cs) for cs in IR}
+        assert len(launches) == sum(len(v) for v in want_names.values()), launches
+        names, k = {}, 0
+        for cs in IR:
+            names[cs.name] = launches[k:k + len(want_names[cs.name])]
+            k += len(names[cs.name])
+        failures = _beyond_bar(got, _ir["want"], setting, names, IR, _ir["outs"])
+        _expect_launches(names, want_names, failures)
+        assert blocks == sum(sum(k.startswith(("k_ir<", "k_ir_b16")) for k in v) for v in want_names.values()), blocks
+    if setting in ("VSO_IR_B16=0", "VSO_IR_WAVE=1"):
+        here, here_launches = _ir_sessions(ort, "f32" if setting == "VSO_IR_B16=0" else "bf16")[:2]
+        if setting == "VSO_IR_B16=0" and launches != here_launches:
+            failures.append(f"launched {launches}, this process's f32 session {here_launches}")
+        for o, g in got.items():
+            if not np.array_equal(g, here[o], equal_nan=True):
+                failures.append(f"{o}: differs from this process's {'f32' if setting == 'VSO_IR_B16=0' else 'bf16'} "
+                                f"session, max {float(np.abs(g - here[o]).max()):.3e}")
+    if setting == "VSO_IR_WAVE=1":
+        moved = [cs.name for cs in IR if _wave(cs) != cs.kernels16]
+        assert len(moved) >= 20 and "IR_64_96" in moved and "IR_96_96_res" not in moved, moved
+    if setting == "VSO_IR_KS1=1":
+        assert KS1_KEEPS <= {cs.name for cs in IR_FUSED16}
     assert not failures, "\n".join(failures)

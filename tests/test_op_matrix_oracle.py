@@ -9,6 +9,11 @@ Nothing here calls back into onnx_ref for the expected value.
 Bars: data movement, MaxPool and nearest Resize compare equal; the rest agree
 to 1e-6 * max(1, |want|) per element (float64 against float64, both rounded
 to float32 once).  The refused cases must raise in the oracle too.
+
+The ir family (inverted-residual blocks) is pinned to 1e-12 besides, and
+carries the conditions its GPU bar rests on: a numpy restatement of the fused
+kernels' arithmetic (tests/ir_ref.py) within half the bar, no saturated Clip,
+and the restatement's mutants beyond the bar (at the end of this file).
 """
 import numpy as np
 import pytest
@@ -246,24 +251,43 @@ def expected(cs, ops, chain_ops=()):
         return [_resize_expected(cs, ops)]
     if op == "Conv":  # then the nodes behind it
         y = _conv_f64(_t(xv), ops[1], ops[2] if len(ops) > 2 else None, at)
-        follow = [(cs.post[0], [cs.post[1]], {})] if cs.post else \
-            [(op_, more, at_) for (op_, _, at_), more in zip(cs.chain, chain_ops)]
-        for op_, more, at_ in follow:
+        follow = [(cs.post[0], [cs.post[1]], {}, {})] if cs.post else \
+            [(nd[0], more, nd[2], nd[3] if len(nd) > 3 else {}) for nd, more in zip(cs.chain, chain_ops)]
+        made, outs = [y], []  # every node's output (a chain operand may name one), the further graph outputs
+        for op_, more, at_, opts in follow:
+            # a reference ("prev" | "in", k | "node", j) to another value of the case, or the operand itself
+            ins = [(made[-1] if v[0] == "prev" else _t(ops[v[1]]) if v[0] == "in" else made[v[1]])
+                   if isinstance(v, tuple) else v for v in more]
+            if not opts.get("whole"):
+                ins = [made[-1]] + ins
+            y = ins[0]
             if op_ == "Conv":
-                y = _conv_f64(y, more[0], more[1] if len(more) > 1 else None, at_)
+                y = _conv_f64(y, ins[1], ins[2] if len(ins) > 2 else None, at_)
             elif op_ == "Add":
-                y = y + _t(more[0])
+                y = y + (ins[1] if torch.is_tensor(ins[1]) else _t(ins[1]))
             elif op_ == "Relu":
                 y = F.relu(y)
-            elif op_ == "Clip":
-                y = torch.clamp(y, float(more[0]), float(more[1]))
+            elif op_ == "Clip":  # bounds as inputs (either may be absent) or, before opset 11, attributes
+                lo = at_.get("min") if len(ins) < 2 or ins[1] is None else float(ins[1])
+                hi = at_.get("max") if len(ins) < 3 or ins[2] is None else float(ins[2])
+                y = torch.clamp(y, lo, hi) if lo is not None or hi is not None else y
             elif op_ == "LeakyRelu":
                 y = F.leaky_relu(y, float(np.float32(at_.get("alpha", 0.01))))
+            elif op_ == "MaxPool":
+                assert set(at_) == {"kernel_shape", "strides"}, at_
+                y = F.max_pool2d(y, tuple(at_["kernel_shape"]), tuple(at_["strides"]))
+            elif op_ == "Pad":  # zeros appended to the channels
+                pads = [int(v) for v in ins[1]]
+                assert len(pads) == 8 and not any(pads[:5] + pads[6:]), pads
+                y = torch.cat([y, torch.zeros(y.shape[0], pads[5], *y.shape[2:], dtype=y.dtype)], dim=1)
             else:
                 assert op_ == "PRelu", op_
-                y = torch.where(y < 0, y * _t(more[0]), y)
+                y = torch.where(y < 0, y * _t(ins[1]), y)
             y = y.float().double()  # every node's own float32 output
-        return [_f32(y)]
+            made.append(y)
+            if opts.get("out"):
+                outs.append(y)
+        return ([xv] if cs.echo else []) + [_f32(o) for o in outs + [y]]
     if op == "Relu":
         return [_f32(F.relu(_t(xv)))]
     if op == "LeakyRelu":
@@ -434,3 +458,151 @@ def test_matrix_covers_the_kernel_forms():
     quad = OC.BY_NAME["Conv_dw_quad_body"]
     n, c, h, w = quad.inputs[0][1]
     assert quad.kernels == ("k_conv_dw(",) and n * c > 65535 and n * c * h * w // 4 >= 1024 * 256 and w % 4 == 0
+
+
+# ---- the ir family: inverted-residual blocks (csrc/vso_ir.hip) -------------------
+# The GPU bar of the matrix (tests/test_gpu_op_matrix.py), per element.
+BAR = 1e-4
+IR = [k for k in OC.VALUE_CASES if k.family in ("ir", "ir6")]
+IR_FUSED = [k for k in IR if any("k_ir" in n for n in k.kernels + k.kernels16)]
+IR_MISSES = [k for k in IR if k not in IR_FUSED]
+_ir_memo = {}
+
+
+def _ir_restated(cs, form, mutant=None):
+    """(the oracle's outputs, the restatement's, its Clips' inputs) of a fused case."""
+    import ir_ref
+    key = (cs.name, form, mutant)
+    if key not in _ir_memo:
+        feeds, want = _oracle_outputs(cs)
+        got, clips = ir_ref.run(cs, OC.operands(cs, feeds), OC.chain_operands(cs, feeds), form, mutant)
+        _ir_memo[key] = (want, got, clips)
+    return _ir_memo[key]
+
+
+def _err_over_bar(got, want):
+    """The worst |got - want| / (BAR * max(1, |want|)) over the outputs' elements."""
+    assert len(got) == len(want) and all(g.shape == w.shape for g, w in zip(got, want))
+    return max(float((np.abs(g.astype(np.float64) - w) / (BAR * np.maximum(1.0, np.abs(w)))).max())
+               for g, w in zip(got, want))
+
+
+@pytest.mark.parametrize("name", [k.name for k in IR])
+def test_ir_oracle_pinned_to_f64(name):
+    """onnx_ref on every case of the family against the independent float64
+    evaluation above (torch's conv2d in double on an input padded here), to
+    1e-12 relative: both round every node's output to float32 once, so they
+    differ only where a float64 sum of another order rounds across a float32
+    tie — which these cases' values do not."""
+    cs = OC.BY_NAME[name]
+    feeds, got = _oracle_outputs(cs)
+    want = expected(cs, OC.operands(cs, feeds), OC.chain_operands(cs, feeds))
+    assert len(got) == len(want) == cs.n_out + cs.echo
+    for g, w in zip(got, want):
+        assert g.shape == w.shape and g.dtype == w.dtype == np.float32
+        assert (np.abs(g.astype(np.float64) - w) <= 1e-12 * np.maximum(1.0, np.abs(w))).all(), \
+            (name, float(np.abs(g.astype(np.float64) - w).max()))
+
+
+def test_ir_family_rounds_no_operand():
+    """No convolution of the family is one a 16-bit session tiles (onnx_ref.tiled_conv):
+    the oracle of a bf16 / f16 session is the f32 one."""
+    for cs in IR:
+        convs = [(cs.inputs[1][1], cs.attrs)] + [(nd[1][0][1], nd[2]) for nd in cs.chain if nd[0] == "Conv"]
+        assert len(convs) % 3 == 0 and not any(R.tiled_conv(w, at_) for w, at_ in convs), cs.name
+
+
+def test_ir_family_covers_the_forms():
+    """Every instance of kIr and kIr16 (vso_ir.hip) and k_ir_reduce has a case
+    that names it; the near misses and the cases without an f32 form name none."""
+    f32 = {n for cs in IR for n in cs.kernels if n.startswith("k_ir")}
+    b16 = {n for cs in IR for n in cs.kernels16 if n.startswith("k_ir")}
+    entries = [(1, 2, 2), (2, 2, 1), (2, 2, 2), (2, 4, 2), (4, 4, 1), (4, 6, 1), (6, 6, 1), (6, 10, 2), (10, 10, 1),
+               (10, 20, 1), (4, 4, 2), (6, 6, 2)]
+    entries16 = [(1, 2, 2), (1, 2, 1), (1, 4, 2), (2, 4, 1), (2, 6, 1), (3, 6, 1), (3, 10, 2), (5, 10, 1), (5, 20, 1),
+                 (2, 4, 2), (3, 6, 2)]
+    assert f32 == {f"k_ir<{a}, {b}, {s}, 4>(" for a, b, s in entries} | {"k_ir_reduce("}
+    assert b16 == {f"k_ir_b16<{a}, {b}, {s}, 4>(" for a, b, s in entries16} | {"k_ir_reduce("}
+    for cs in IR_MISSES:
+        assert cs.kernels == cs.kernels16 and cs.kernels and not any("k_ir" in n for n in cs.kernels), cs.name
+    for name in ("IR_16_24_s1", "IR_48_64_s1"):
+        cs = OC.BY_NAME[name]
+        assert not any("k_ir" in n for n in cs.kernels) and "k_ir_b16<" in cs.kernels16[0]
+    # one slice (no reduce launch) and several, in either precision
+    for field in ("kernels", "kernels16"):
+        assert {("k_ir_reduce(" in getattr(cs, field)) for cs in IR_FUSED} == {False, True}
+
+
+@pytest.mark.parametrize("form", ["f32", "b16"])
+@pytest.mark.parametrize("name", [k.name for k in IR_FUSED])
+def test_ir_restatement_inside_half_the_bar(name, form):
+    """Condition 1 on the inputs: each form's arithmetic, restated (tests/ir_ref.py),
+    is within half the bar of the oracle on every element — a kernel that
+    computes what it says has the other half for its own association."""
+    cs = OC.BY_NAME[name]
+    want, got, _ = _ir_restated(cs, form)
+    ratio = _err_over_bar(got, want)
+    print(f"{name} {form}: restatement err / bar {ratio:.4f}")
+    assert ratio <= 0.5, (name, form, ratio)
+
+
+@pytest.mark.parametrize("name", [k.name for k in IR_FUSED])
+def test_ir_clips_not_saturated(name):
+    """Condition 2 on the inputs: at least a quarter of the expand's outputs, and
+    of the depthwise's, lie strictly inside their Clip's range (a saturated
+    clip hides the errors of what feeds it).  A Clip without both bounds has
+    no range to saturate."""
+    cs = OC.BY_NAME[name]
+    _, _, clips = _ir_restated(cs, "f32")
+    assert len(clips) >= 2
+    for k, (v, lo, hi) in enumerate(clips):
+        if lo is None or hi is None:
+            continue
+        share = float(((v > lo) & (v < hi)).mean())
+        print(f"{name} clip {k}: {share:.3f} inside ({lo}, {hi})")
+        assert share >= 0.25, (name, k, share)
+
+
+@pytest.mark.parametrize("mutant,name,form", [
+    ("drop_wl_xh", "IR_96_96_res", "b16"),
+    ("pad_clip", "IR_24_24_res_clip0.5_4", "f32"),
+    ("pad_clip", "IR_24_24_res_clip0.5_4", "b16"),
+    ("swap_taps", "IR_24_24_res", "f32"),
+    ("swap_taps", "IR_16_24_s2", "b16"),
+    ("no_res", "IR_24_24_res", "f32"),
+    ("no_res", "IR_24_24_res_swapped", "b16"),
+    ("drop_last_chunk", "IR_24_24_res_hid48", "b16"),
+    ("drop_last_chunk", "IR_20_20_res", "f32"),
+    ("cout_tail", "IR_28_49_s2", "f32"),
+    ("cout_tail", "IR_84_81", "b16"),
+    ("cout_tail", "IR_148_305", "b16"),
+    ("cin_tail", "IR_20_20_res", "f32"),
+    ("cin_tail", "IR_148_305", "f32"),
+])
+def test_ir_mutant_leaves_the_bar(mutant, name, form):
+    """Each way the kernels could be wrong, applied to the restatement, is beyond
+    the bar on the case made for it (and the restatement itself is not)."""
+    cs = OC.BY_NAME[name]
+    want, good, _ = _ir_restated(cs, form)
+    _, bad, _ = _ir_restated(cs, form, mutant)
+    ratio = _err_over_bar(bad, want)
+    print(f"{name} {form} {mutant}: err / bar {ratio:.1f}")
+    assert _err_over_bar(good, want) <= 0.5 and ratio > 1.0, (mutant, name, form, ratio)
+
+
+def test_earlier_cases_build_as_before():
+    """build()'s reference operands and further graph outputs leave the models
+    and feeds of the cases without them as they were: a chain with fresh
+    inputs, one with constants, a `post` pair and a multi-output case, each
+    alone in its model (sha256 of the model's bytes, then of the feeds' names
+    and bytes in name order, taken before the ir family was added)."""
+    import hashlib
+    for name, want in (("Conv_dwpw_3x3_s2_C32_M20", "bdf7b536833092ee"), ("Conv_small_K27_relu", "cbaf9f1e75aa4dcd"),
+                       ("Conv_dwpw_7x7_C24_M20", "2aa72bb97bd375b2"), ("ConvPRelu_C11", "d9024db3b3f5c686"),
+                       ("Split_sizes_input", "af60f2da80681bf2")):
+        data, feeds, _ = OC.build([OC.BY_NAME[name]])
+        h = hashlib.sha256(data)
+        for k in sorted(feeds):
+            h.update(k.encode())
+            h.update(feeds[k].tobytes())
+        assert h.hexdigest()[:16] == want, name

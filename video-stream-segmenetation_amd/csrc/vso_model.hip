@@ -1070,6 +1070,9 @@ struct Planner {
     if (k5 >= 0 && g.nodes[k5].op == "Add") {
       const Node& ad = g.nodes[k5];
       const std::string& other = ad.in[0] == out ? ad.in[1] : ad.in[0];
+      // a strided residual find_residual_fusions left to the project's epilogue (its MaxPool / Pad
+      // nodes are done, nothing writes `other`): the generic plan, whose plan_conv reads the pool's input
+      if (res_fuse.count(other)) return 0;
       if (other == ex.in[0] && ad.in[0] != ad.in[1] && sd == 1 && CIN == COUT) {
         res = true;
         out = ad.out[0];
