@@ -710,16 +710,24 @@ def run(model: Model, feeds: dict, want=None, conv_operands=None) -> dict:
                 sizes = ins[3] if len(ins) > 3 and ins[3] is not None else None
                 y = _resize(x, scales, sizes, a)
         elif op == "InstanceNormalization":
+            # (what the session refuses at creation: vso_model.hip, plan_node / plan_norm)
+            if nd["inputs"][1] not in const or nd["inputs"][2] not in const:
+                raise ValueError("InstanceNormalization: constant scale/B only")
+            if x.ndim < 3:
+                raise ValueError("InstanceNormalization: rank >= 3 only")
+            if ins[1].size != x.shape[1] or ins[2].size != x.shape[1]:
+                raise ValueError("InstanceNormalization: scale/B size")
             xx = x.astype(np.float64)
             sp = tuple(range(2, x.ndim))
             per_c = (1, -1) + (1,) * (x.ndim - 2)
             mu = xx.mean(axis=sp, keepdims=True)
             var = ((xx - mu) ** 2).mean(axis=sp, keepdims=True)
-            y = _f32((xx - mu) / np.sqrt(var + a.get("epsilon", 1e-5)) * ins[1].astype(np.float64).reshape(per_c)
+            # (epsilon is a float32 attribute: its default is float32(1e-5), as the session's)
+            y = _f32((xx - mu) / np.sqrt(var + float(np.float32(a.get("epsilon", 1e-5)))) * ins[1].astype(np.float64).reshape(per_c)
                      + ins[2].astype(np.float64).reshape(per_c))
         elif op == "BatchNormalization":
             sc, bb, mu, var = (t.astype(np.float64).reshape((1, -1) + (1,) * (x.ndim - 2)) for t in ins[1:5])
-            y = _f32((x.astype(np.float64) - mu) / np.sqrt(var + a.get("epsilon", 1e-5)) * sc + bb)
+            y = _f32((x.astype(np.float64) - mu) / np.sqrt(var + float(np.float32(a.get("epsilon", 1e-5)))) * sc + bb)
         elif op == "MatMul":
             y = _f32(np.matmul(x.astype(np.float64), ins[1].astype(np.float64)))
         elif op == "Gemm":

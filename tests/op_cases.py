@@ -6,7 +6,8 @@ oracle).
 
 A case is one operator node (the conv family: with the nodes a session fuses
 behind it, `chain`; the ir family: one inverted-residual block, a chain whose
-nodes may name the case's input or each other): its attributes, its inputs in operator order
+nodes may name the case's input or each other; the inorm / ibn families: InstanceNormalization alone, or
+MODNet's IBNorm pattern with its consumer): its attributes, its inputs in operator order
 (graph inputs filled from a seeded generator, or constants where the operator
 needs them constant), the model's opset, and whether the session must compute
 it ("value") or refuse it at creation ("refused").  build() packs any number
@@ -50,9 +51,11 @@ class Case:
     # a chain operand may also be ("in", k): the case's own input k, or ("node", j): the output of the case's
     # node j (0: its operator, j: chain[j - 1]).  A chain node may carry a fourth element, {"whole": its
     # inputs are all listed, ("prev",) standing for the node before; "out": its output is one more graph
-    # output of the case, ahead of the last node's}.
+    # output of the case, ahead of the last node's; "n": it has that many outputs, ("node", j, q) its q-th}.
+    # Further input kinds (the norm families): "ramp", "off100", "small", "half" — see _generate.
     kernels16: tuple = ()   # `kernels` of a bf16 / f16 session (the ir family, whose fused forms differ by precision)
     echo: bool = False      # the case's input 0 is a graph output too (the first of the case's)
+    op_out: bool = False    # the operator's own output (node 0 of a chain) is a graph output too (behind echo's)
 
 
 CASES: list[Case] = []
@@ -699,6 +702,243 @@ ir("miss_pool_pad_residual", 16, 24, EVEN, GEN, GEN, s=2,
    tail=[POOL, then("Pad", ci(0, 0, 0, 0, 0, 8, 0, 0)), node("Add", [("node", 4), PREV])])
 
 # ---------------------------------------------------------------------------
+# InstanceNormalization alone (family inorm).  plan_norm (vso_model.hip) picks by the plane's element count:
+# k_norm_plane<16, 256> up to 4096, <48, 256> up to 12288, <36, 1024> up to 36864 — one workgroup per plane, two
+# passes over registers — and above that k_norm_stats ((mean, M2, count) per piece of 4096 elements) +
+# k_norm_apply (the pieces merged in order, Chan et al.).  Each moves float4s where the plane is a multiple of
+# 4 elements, single floats where not.  Planes on both sides of every limit, in either form; the pair at 10
+# pieces with a last piece of 1 / of 4 elements / full, at 65 and at 129 pieces.  Inputs: a ramp of +-3 across
+# the plane above 4096 elements (more than one piece, under VSO_NORM_PLANE=0 too), standard normal below.
+PLANE16, PLANE48, PLANE36 = "k_norm_plane<16, 256>(", "k_norm_plane<48, 256>(", "k_norm_plane<36, 1024>("
+STATS, APPLY = "k_norm_stats(", "k_norm_apply("
+
+
+def norm_launches(inner, plane=True):
+    """The launches of an InstanceNormalization of planes of `inner` elements (plane=False: VSO_NORM_PLANE=0)."""
+    if plane and inner <= 36864:
+        return (PLANE16 if inner <= 4096 else PLANE48 if inner <= 12288 else PLANE36,)
+    return (STATS, APPLY)
+
+
+def inorm(name, shape, kind=None, eps=1e-5, after=(), **kw):
+    inner = int(np.prod(shape[2:]))
+    case(f"IN_{name}", "inorm", "InstanceNormalization",
+         [(kind or ("ramp" if inner > 4096 else "x"), tuple(shape)), cf((shape[1],), 35, lo=0.5), cf((shape[1],), 36)],
+         {} if eps is None else {"epsilon": eps}, kernels=norm_launches(inner) + tuple(after), **kw)
+
+
+for hw_ in ((1, 1), (1, 2), (3, 1), (1, 5), (2, 2), (63, 65), (64, 64), (17, 241), (41, 100), (96, 128), (11, 1117),
+            (1, 12289), (28, 439), (192, 192), (191, 193)):
+    inorm(str(hw_[0] * hw_[1]), (2, 3 if hw_[0] * hw_[1] <= 4100 else 2, *hw_))
+inorm("36865", (2, 2, 73, 505))      # 10 pieces, the last of 1 element (scalar)
+inorm("36868", (2, 2, 52, 709))      # the last of 4 (float4)
+inorm("40960", (2, 2, 160, 256))     # 10 full pieces
+inorm("262656", (1, 2, 512, 513))    # 65 pieces (float4)
+inorm("525625", (1, 1, 725, 725))    # 129 pieces (scalar)
+inorm("rank3_257", (2, 3, 257))
+inorm("rank3_36865", (1, 2, 36865))
+inorm("rank5_105", (2, 3, 3, 5, 7))
+inorm("rank5_36865", (1, 2, 5, 73, 101))
+for tag_, shp_ in (("4095", (2, 3, 63, 65)), ("12288", (2, 2, 96, 128)), ("36863", (2, 2, 191, 193)),
+                   ("36868", (2, 2, 52, 709))):
+    inorm(f"{tag_}_off100", shp_, "off100")
+    inorm(f"{tag_}_small_eps1e-5", shp_, "small")
+    inorm(f"{tag_}_small_eps1e-3", shp_, "small", eps=1e-3)
+    inorm(f"{tag_}_half", shp_, "half", exact=True)
+inorm("default_eps", (2, 3, 7, 9), "small", eps=None)
+inorm("63_relu", (2, 3, 7, 9), after=("k_unary(",), chain=(then("Relu"),))
+inorm("rows1", (1, 1, 3, 5))
+inorm("rows257", (1, 257, 3, 5))
+
+# ---------------------------------------------------------------------------
+# MODNet's IBNorm (family ibn), one pattern per case, fused by find_ibnorm (vso_model.hip):
+#   c = Conv(x); Concat(BatchNorm(Slice(c, 0:nb)), InstanceNorm(Slice(c, nb:M)), axis 1) [-> Relu] [-> consumer]
+# The conv writes the concatenation (the BatchNorm folded into its first nb channels, the Relu on them in its
+# epilogue), the norm runs in place on channels nb .. M - 1 (c0 = nb, ctot = M).  Before a thin 1x1 head
+# (k_conv_thin, up to 4 outputs from up to 256 channels) only k_norm_stats runs: the head merges the pieces
+# (merge_stats) and normalises in its loads.  Before a Concat on axis 1 the conv writes into that Concat's
+# output and the norm runs there (ctot > M).  Chain layout of every case: Slice, Slice, BatchNormalization,
+# InstanceNormalization, Concat, [Relu], the consumer's nodes (IBN: the figures tests/norm_ref.py needs).
+_ibn_seed = [0]
+IBN = {}
+
+
+def _bw(shape, fan_in=None, lo=None, gain=1.0):
+    """A seeded float32 constant of the ibn family: a weight (normal / sqrt(fan_in)), gain * normal, or
+    uniform in [lo, lo + 1)."""
+    _ibn_seed[0] += 1
+    rng = np.random.default_rng(3000 + _ibn_seed[0])
+    if lo is not None:
+        a = rng.random(shape) + lo
+    else:
+        a = rng.standard_normal(shape) * (gain if fan_in is None else fan_in ** -0.5)
+    return ("c", a.astype(np.float32))
+
+
+def _slice(src, b, e, form="axes"):
+    """Slice(src, b:e) of the channels of M: form "axes" (starts, ends, axes), "steps" (and steps = [1]),
+    "both" (axes omitted: axis 0 whole, then the channels); b / e as given (negative, INT64_MAX)."""
+    if form == "both":
+        return node("Slice", [src, ci(0, b), ci(INT64_MAX, e)])
+    return node("Slice", [src, ci(b), ci(e), ci(1)] + ([ci(1)] if form == "steps" else []))
+
+
+def pw_name(m):
+    return f"k_conv_pw<{1 if m <= 16 else 2 if m <= 32 else 4}, 0>("
+
+
+def ibn(name, xs, m, nb, conv, ks=1, relu=True, bias=True, eps_bn=None, eps_in=None, var=None, slices=None, tail=(),
+        after=None, defer=False, cat=None, out=False, fused=True, order=(0, 1), c_in=None, axis=1, split=False,
+        conv_out=False, family="ibn", bn=None, kind=None, **kw):
+    """One pattern on a graph input `xs`: Conv (ks x ks, padded to keep the plane) onto m channels, nb of them
+    to the BatchNorm.  conv: the conv's launch; after: the launches behind it (default: the norm's by plane
+    size; defer: k_norm_stats alone); tail: the consumer's nodes; cat: (position of the pattern among a later
+    Concat's two inputs, the skip's channels); out: the pattern's output is a graph output too; slices: the two
+    Slice nodes where they are not 0:nb / nb:m; c_in: the InstanceNorm's channels where not m - nb; order: the
+    Concat's inputs; split: a Split for the Slices; conv_out: the conv's output is a graph output too; bn: the
+    BatchNorm's (scale, B, mean, var) where given; kind: the input's, where neither a ramp (planes above 4096
+    elements) nor standard normal."""
+    n, cch, h, w = xs
+    inner = h * w
+    c_in = m - nb if c_in is None else c_in
+    conv0 = ("node", 0)
+    if split:
+        chain = [node("Split", [conv0, ci(nb, m - nb)], axis=1)[:3] + ({"whole": True, "n": 2},)]
+        src_bn, src_in = ("node", 1), ("node", 1, 1)
+    else:
+        chain = list(slices or (_slice(conv0, 0, nb), _slice(conv0, nb, m)))
+        src_bn, src_in = ("node", 1), ("node", 2)
+    bn_c = bn or (_bw((nb,), lo=0.5), _bw((nb,), gain=0.5), _bw((nb,), gain=0.5),
+                  ("c", np.full(nb, var, np.float32)) if var is not None else _bw((nb,), lo=0.5))
+    i_bn = len(chain) + 1  # (node j is chain[j - 1])
+    chain.append(node("BatchNormalization", [src_bn, *bn_c], **({} if eps_bn is None else {"epsilon": eps_bn})))
+    chain.append(node("InstanceNormalization", [src_in, _bw((c_in,), lo=0.5), _bw((c_in,), gain=0.5)],
+                      **({} if eps_in is None else {"epsilon": eps_in})))
+    chain.append(node("Concat", [("node", i_bn + order[0]), ("node", i_bn + order[1])], axis=axis))
+    if relu:
+        chain.append(then("Relu"))
+    if out:
+        chain[-1] = also_out(chain[-1])
+    pos_ = len(chain)  # the pattern's output: node pos_
+    if cat is not None:
+        skip = ("ramp" if inner > 4096 else "x", (n, cat[1], h, w))
+        chain.append(node("Concat", [PREV, skip] if cat[0] == 0 else [skip, PREV], axis=1))
+    chain += list(tail)
+    if after is None:
+        after = (STATS,) if defer else norm_launches(inner)
+    n_out = 1 + bool(conv_out) + sum(1 for nd in chain[:-1] if len(nd) > 3 and nd[3].get("out"))
+    pad = (ks - 1) // 2
+    IBN[f"IBN_{name}"] = {"m": m, "nb": nb, "relu": relu, "defer": defer, "cat": cat, "fused": fused, "out": out,
+                          "i_bn": i_bn, "pos": pos_}
+    case(f"IBN_{name}", family, "Conv",
+         [(kind or ("ramp" if inner > 4096 else "x"), tuple(xs)), _bw((m, cch, ks, ks), cch * ks * ks)]
+         + ([_bw((m,), gain=0.5)] if bias else []),
+         {"pads": [pad] * 4} if ks > 1 else {}, kernels=(conv,) + tuple(after), chain=tuple(chain), n_out=n_out,
+         op_out=conv_out, **kw)
+
+
+def head(m_out, c_, **attrs):
+    """A 1x1 head onto m_out channels (with a bias)."""
+    return then("Conv", _bw((m_out, c_, 1, 1), c_), _bw((m_out,), gain=0.5), **attrs)
+
+
+THIN = "k_conv_thin<%d>("
+# (a) a graph output: every conv form, nb 1 / M - 1 / M / 2 / odd of M 5 / 24 / 32, with and without the Relu and
+# the bias, the epsilons default and explicit, planes on both sides of the norm's thresholds
+ibn("pw_M5_nb1_4", (2, 3, 2, 2), 5, 1, pw_name(5))
+ibn("pw_M5_nb4_63_neg", (2, 3, 7, 9), 5, 4, pw_name(5), relu=False, bias=False,
+    slices=(_slice(("node", 0), -5, -1), _slice(("node", 0), -1, INT64_MAX)))
+ibn("pw_M24_nb12_2304_eps", (2, 8, 36, 64), 24, 12, pw_name(24), eps_bn=1e-3, eps_in=1e-4,
+    slices=(_slice(("node", 0), 0, 12, "steps"), _slice(("node", 0), 12, INT64_MAX, "steps")))
+ibn("pw_M24_nb7_4100", (2, 8, 41, 100), 24, 7, pw_name(24))
+ibn("pw_M5_nb2_36868", (2, 3, 52, 709), 5, 2, pw_name(5))
+ibn("pw_M5_nb2_var0.01", (2, 3, 7, 9), 5, 2, pw_name(5), var=0.01, eps_bn=1e-3, relu=False)
+ibn("small3x3_M5_nb2_99", (2, 3, 9, 11), 5, 2, small(False, 8, False), ks=3)
+ibn("small3x3_M24_nb23_99", (2, 8, 9, 11), 24, 23, small(False, 32, False), ks=3, relu=False, bias=False)
+ibn("tile_M32_nb16_2304", (2, 16, 36, 64), 32, 16, "k_conv_tile<", ks=3)
+ibn("tile_M32_nb5_2304", (2, 16, 36, 64), 32, 5, "k_conv_tile<", ks=3, relu=False, bias=False, eps_in=1e-3)
+# (b) a thin 1x1 head of 1 .. 4 outputs: the apply step inside k_conv_thin.  1 piece, 10 pieces with a last one
+# of 1 element, 65, 129 (merge_stats' lane loop a second and a third time); its float4 and scalar pixel paths
+ibn("thin1_63", (2, 3, 7, 9), 5, 2, pw_name(5), tail=[head(1, 5)], after=(STATS, THIN % 1), defer=True)
+ibn("thin4_4096", (2, 4, 64, 64), 5, 3, pw_name(5), relu=False, tail=[head(4, 5)], after=(STATS, THIN % 4), defer=True)
+ibn("thin2_36865", (2, 3, 73, 505), 5, 1, pw_name(5), tail=[head(2, 5)], after=(STATS, THIN % 2), defer=True)
+ibn("thin3_262656", (1, 3, 512, 513), 2, 1, pw_name(2), tail=[head(3, 2)], after=(STATS, THIN % 3), defer=True)
+ibn("thin4_525625", (1, 3, 725, 725), 2, 1, pw_name(2), bias=False, tail=[head(4, 2)], after=(STATS, THIN % 4), defer=True)
+ibn("thin2_M256_nb1", (2, 3, 5, 7), 256, 1, pw_name(256), tail=[head(2, 256)], after=(STATS, THIN % 2), defer=True)
+# (inputs of variance 1e-4: the epsilon inside k_conv_thin's scale counts)
+ibn("thin2_63_small", (2, 3, 7, 9), 5, 2, pw_name(5), kind="small", tail=[head(2, 5)], after=(STATS, THIN % 2), defer=True)
+# 257 channels: beyond k_conv_thin — the norm's own launch, the head on k_conv_small
+ibn("head2_M257_nb1", (2, 3, 5, 7), 257, 1, pw_name(257), tail=[head(2, 257)], after=(PLANE16, small(True, 16, True)))
+ibn("tile_thin2_2304", (2, 16, 36, 64), 32, 16, "k_conv_tile<", ks=3, tail=[head(2, 32)], after=(STATS, THIN % 2),
+    defer=True)
+# (c) heads k_conv_thin does not take: the norm applies itself.  A head that is an IBNorm's conv is found thin
+# by feeds_thin and declined by plan_conv: its input's apply step is flush_norm's
+ibn("head_s2_63", (2, 3, 7, 9), 5, 2, pw_name(5), tail=[head(2, 5, strides=[2, 2])], after=(PLANE16, small(False, 8, False)))
+ibn("head5_63", (2, 3, 7, 9), 5, 2, pw_name(5), tail=[head(5, 5)], after=(PLANE16, pw_name(5)))
+ibn("head_g5_63", (2, 3, 7, 9), 5, 2, pw_name(5), tail=[then("Conv", _bw((5, 1, 1, 1), 1), group=5)],
+    after=(PLANE16, "k_conv_dw("))
+# (the head's conv is node 7: its slices name it)
+ibn("head_ibn_63", (2, 3, 7, 9), 5, 2, pw_name(5),
+    tail=[head(4, 5), _slice(("node", 7), 0, 2), _slice(("node", 7), 2, 4),
+          node("BatchNormalization", [("node", 8), _bw((2,), lo=0.5), _bw((2,), gain=0.5), _bw((2,), gain=0.5),
+                                      _bw((2,), lo=0.5)]),
+          node("InstanceNormalization", [("node", 9), _bw((2,), lo=0.5), _bw((2,), gain=0.5)]),
+          node("Concat", [("node", 10), ("node", 11)], axis=1)],
+    after=(STATS, APPLY, pw_name(4), PLANE16), defer=True)
+# (d) the pattern's output a graph output besides: not deferred
+ibn("thin2_and_out_63", (2, 3, 7, 9), 5, 2, pw_name(5), out=True, tail=[head(2, 5)], after=(PLANE16, THIN % 2))
+# (e) into a later Concat on axis 1, as its first and as its second input: the conv and the norm write in place
+# there (ctot 5 + 3), batch 2
+ibn("cat_first_63", (2, 3, 7, 9), 5, 2, pw_name(5), cat=(0, 3), after=(PLANE16, "k_copy_rows<"))
+ibn("cat_second_63", (2, 3, 7, 9), 5, 2, pw_name(5), cat=(1, 3), relu=False, after=(PLANE16, "k_copy_rows<"))
+ibn("cat_second_36868", (2, 3, 52, 709), 5, 2, pw_name(5), cat=(1, 1), after=(STATS, APPLY, "k_copy_rows<"))
+ibn("tile_cat_first_2304", (2, 16, 36, 64), 32, 16, "k_conv_tile<", ks=3, cat=(0, 2), after=(PLANE16, "k_copy_rows<"))
+# Near misses: left to the generic plan — the conv, a copy per Slice (Split: per output), k_affine, the norm, a
+# copy per Concat input, k_unary for the Relu
+GENERIC = ("k_copy_rows<", "k_copy_rows<", "k_affine(", PLANE16, "k_copy_rows<", "k_copy_rows<")
+RELU = ("k_unary(",)
+ibn("miss_split", (2, 3, 7, 9), 5, 2, pw_name(5), split=True, fused=False, after=GENERIC + RELU)
+ibn("miss_axes_omitted", (2, 3, 7, 9), 5, 2, pw_name(5), fused=False, after=GENERIC + RELU,
+    slices=(_slice(("node", 0), 0, 2, "both"), _slice(("node", 0), 2, INT64_MAX, "both")))
+ibn("miss_gap", (2, 3, 7, 9), 5, 2, pw_name(5), fused=False, c_in=2, after=GENERIC + RELU,
+    slices=(_slice(("node", 0), 0, 2), _slice(("node", 0), 3, 5)))
+ibn("miss_overlap", (2, 3, 7, 9), 5, 2, pw_name(5), fused=False, c_in=4, after=GENERIC + RELU,
+    slices=(_slice(("node", 0), 0, 2), _slice(("node", 0), 1, 5)))
+ibn("miss_in_then_bn", (2, 3, 7, 9), 5, 2, pw_name(5), fused=False, order=(1, 0), after=GENERIC + RELU)
+ibn("miss_third_consumer", (2, 3, 7, 9), 5, 2, pw_name(5), fused=False, after=GENERIC + RELU + RELU, out=True,
+    tail=[node("Relu", [("node", 0)])])
+ibn("miss_axes-3", (2, 3, 7, 9), 5, 2, pw_name(5), fused=False, after=GENERIC + RELU,
+    slices=(node("Slice", [("node", 0), ci(0), ci(2), ci(-3)]), node("Slice", [("node", 0), ci(2), ci(5), ci(-3)])))
+ibn("miss_step2", (2, 3, 7, 9), 5, 2, pw_name(5), fused=False, c_in=2,
+    after=("k_copy_rows<", "k_copy(", "k_affine(", PLANE16, "k_copy_rows<", "k_copy_rows<") + RELU,
+    slices=(_slice(("node", 0), 0, 2), node("Slice", [("node", 0), ci(2), ci(5), ci(1), ci(2)])))
+ibn("miss_concat_axis2", (2, 3, 7, 9), 6, 3, pw_name(6), fused=False, axis=2,
+    after=("k_copy_rows<", "k_copy_rows<", "k_affine(", PLANE16, "k_copy(", "k_copy(") + RELU)
+ibn("miss_slice_attr", (2, 3, 7, 9), 5, 2, pw_name(5), fused=False, family="ibn9", opset=9, after=GENERIC + RELU,
+    slices=(node("Slice", [("node", 0)], starts=[0], ends=[2], axes=[1]),
+            node("Slice", [("node", 0)], starts=[2], ends=[INT64_MAX], axes=[1])))
+# the conv's output a graph output too
+ibn("miss_conv_out", (2, 3, 7, 9), 5, 2, pw_name(5), fused=False, after=GENERIC + RELU, conv_out=True)
+
+# 16-bit sessions fold the BatchNorm into the weights, then round them; the oracle rounds the weights, then
+# applies the BatchNorm.  With epsilon 2^-10, var 1 - 2^-10 and power-of-two scales the fold factor is a power
+# of two: the two commute, and the dense 3x3 patterns (k_conv_tile in a 16-bit session whatever their size) meet
+# the oracle of R.run(conv_operands=...) at the matrix's bar (family ibn16)
+def _bn16(nb):
+    # (scales 1/2 .. 4; tests/test_op_matrix_oracle.py asserts the commutation on the weights drawn: a product in
+    # float16's subnormal range would not commute)
+    return (("c", (2.0 ** (np.arange(nb) % 4 - 1)).astype(np.float32)), _bw((nb,), gain=0.5), _bw((nb,), gain=0.5),
+            ("c", np.full(nb, 1 - 2.0 ** -10, np.float32)))
+
+
+ibn("b16_tile_M32_nb16_2304", (2, 16, 36, 64), 32, 16, "k_conv_tile<", ks=3, family="ibn16", bn=_bn16(16),
+    eps_bn=2.0 ** -10)
+ibn("b16_3x3_M5_nb2_99_thin2", (2, 3, 9, 11), 5, 2, small(False, 8, False), ks=3, family="ibn16", bn=_bn16(2),
+    eps_bn=2.0 ** -10, tail=[head(2, 5)], after=(STATS, THIN % 2), defer=True)
+ibn("b16_3x3_M24_nb7_cat_99", (2, 8, 9, 11), 24, 7, small(False, 32, False), ks=3, relu=False, family="ibn16",
+    bn=_bn16(7), eps_bn=2.0 ** -10, cat=(1, 3), after=(PLANE16, "k_copy_rows<"))
+
+# ---------------------------------------------------------------------------
 # what the session refuses at creation (and the oracle refuses to evaluate)
 case("refuse_Resize_antialias", "refused", "Resize", _resize_inputs(scale=0.5), {"mode": "linear", "antialias": 1},
      opset=18, expect="refused")
@@ -738,6 +978,15 @@ case("refuse_Conv_strides_length", "refused", "Conv", [x(2, 3, *P9), _cw(5, 3, 3
 case("refuse_Conv_dilations_length", "refused", "Conv", [x(2, 3, *P9), _cw(5, 3, 3, 3)], {"dilations": [2]},
      expect="refused")
 
+case("refuse_InstanceNormalization_runtime_scale", "refused", "InstanceNormalization",
+     [x(2, 3, 4, 5), x(3), cf((3,), 36)], expect="refused")
+case("refuse_InstanceNormalization_rank2", "refused", "InstanceNormalization", [x(2, 3), cf((3,), 35, lo=0.5), cf((3,), 36)],
+     expect="refused")
+case("refuse_InstanceNormalization_scale_size", "refused", "InstanceNormalization",
+     [x(2, 3, 4, 5), cf((2,), 35, lo=0.5), cf((3,), 36)], expect="refused")
+case("refuse_InstanceNormalization_B_size", "refused", "InstanceNormalization",
+     [x(2, 3, 4, 5), cf((3,), 35, lo=0.5), cf((4,), 36)], expect="refused")
+
 VALUE_CASES = [k for k in CASES if k.expect == "value"]
 REFUSED_CASES = [k for k in CASES if k.expect == "refused"]
 BY_NAME = {k.name: k for k in CASES}
@@ -769,6 +1018,17 @@ def _generate(name, kind, shape):
         a = rng.random(shape) + 0.5
     elif kind == "pm80":
         a = rng.choice([-80.0, 80.0], size=shape) + rng.standard_normal(shape)
+    elif kind == "ramp":  # a ramp of +-3 across each plane: the pieces' means differ by more than a standard deviation
+        inner = int(np.prod(shape[2:], dtype=np.int64))
+        a = rng.standard_normal(shape) + np.linspace(-3.0, 3.0, inner).reshape((1, 1) + tuple(shape[2:]))
+    elif kind == "off100":  # a mean far from 0: E[x^2] - E[x]^2 cancels
+        a = rng.standard_normal(shape) + 100.0
+    elif kind == "small":  # a variance of 1e-4: epsilon counts
+        a = 0.01 * rng.standard_normal(shape)
+    elif kind == "half":  # constant planes of a small multiple of 0.5 each: every float32 partial sum is exact
+        k = np.arange(int(np.prod(shape[:2])), dtype=np.int64)
+        a = np.broadcast_to((0.5 * (1 + k % 7) * (1 - 2 * (k % 2))).reshape(tuple(shape[:2]) + (1,) * (len(shape) - 2)),
+                            shape)
     else:  # "x", "x3", "x4": standard normal, times 3 / 4 (wider activations)
         a = rng.standard_normal(shape) * (float(kind[1:]) if len(kind) > 1 else 1.0)
     return a.astype(np.float32)
@@ -803,6 +1063,8 @@ def build(cases):
 
         def chain_operand(spec, k, pos_):
             if spec and spec[0] in ("prev", "in", "node"):
+                if spec[0] == "node" and len(spec) > 2 and spec[2]:  # a further output of a node with several
+                    return f"{made[spec[1]]}.{spec[2]}"
                 return made[-1] if spec[0] == "prev" else names[spec[1]] if spec[0] == "in" else made[spec[1]]
             return operand(spec, spec and spec[0] != "c" and _chain_input_name(cs, k, pos_))
 
@@ -811,13 +1073,14 @@ def build(cases):
         finals = output_names(cs)
         if cs.chain:
             extra = iter(finals[:-1])
-            made.append(b.name("mid"))
+            made.append(next(extra) if cs.op_out else b.name("mid"))
             b.nodes.append(R.make_node(cs.op, names, [made[0]], **cs.attrs))
             for k, nd in enumerate(cs.chain):
                 (op_, ins_, at_), opts = nd[:3], nd[3] if len(nd) > 3 else {}
                 more = [chain_operand(spec, k, pos_) for pos_, spec in enumerate(ins_)]
                 nxt = finals[-1] if k + 1 == len(cs.chain) else next(extra) if opts.get("out") else b.name("mid")
-                b.nodes.append(R.make_node(op_, more if opts.get("whole") else [made[-1]] + more, [nxt], **at_))
+                nxts = [nxt] + [f"{nxt}.{q}" for q in range(1, opts.get("n", 1))]  # "n": a node of several outputs
+                b.nodes.append(R.make_node(op_, more if opts.get("whole") else [made[-1]] + more, nxts, **at_))
                 made.append(nxt)
         elif cs.post:
             mid = b.name("mid")

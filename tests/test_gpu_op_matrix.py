@@ -31,6 +31,16 @@ near misses on the generic plan — and here in bf16 and f16 sessions
 under each of try_plan_ir's knobs in a child process.  Figures and three
 breaks of vso_ir.hip that only these tests catch: profiles/NOTES.md, "IR
 block matrix".
+
+The inorm and ibn families (InstanceNormalization alone; MODNet's IBNorm
+pattern, fused by find_ibnorm, through each of its consumers) run in f32 with
+the other families — every k_norm_plane instance in its float4 and scalar
+form, k_norm_stats + k_norm_apply up to 129 pieces, k_conv_thin behind a
+deferred norm — and here under VSO_NORM_PLANE=0 and VSO_THIN=0 in child
+processes and in bf16 and f16 sessions (the ibn16 cases against the oracle
+that rounds the conv's operands).  Figures and the value-only breaks of
+vso_kernels.hip / vso_model.hip that only these tests catch:
+profiles/NOTES.md, "Norm operator matrix".
 """
 import math
 import re
@@ -400,4 +410,170 @@ def test_ir_family_knob(ort, setting):
         assert len(moved) >= 20 and "IR_64_96" in moved and "IR_96_96_res" not in moved, moved
     if setting == "VSO_IR_KS1=1":
         assert KS1_KEEPS <= {cs.name for cs in IR_FUSED16}
+    assert not failures, "\n".join(failures)
+
+
+# ---- the norm families: 16-bit sessions and the planner's knobs -------------------
+NORM_FAMILIES = ("inorm", "ibn", "ibn9", "ibn16")  # (ibn9: the attribute-form Slice's opset; ibn16: see op_cases)
+NORM = [cs for fam in NORM_FAMILIES for cs in OC.groups()[fam]]
+_norm = {}
+
+
+def _norm_models():
+    """{family: (model, feeds, {case: its graph outputs})} and the f64 oracle's outputs of all of them."""
+    if "models" not in _norm:
+        _norm["models"] = {fam: OC.build(OC.groups()[fam]) for fam in NORM_FAMILIES}
+        _norm["outs"] = {k: v for m in _norm["models"].values() for k, v in m[2].items()}
+        _norm["want"] = {k: v for data, feeds, _ in _norm["models"].values() for k, v in R.run(R.load(data), feeds).items()}
+    return _norm["models"]
+
+
+def _norm_sessions(ort, prec):
+    """(outputs, launches in order, whether a second run was bitwise the same) of the families' sessions in
+    this process, once per precision."""
+    if prec not in _norm:
+        got, launches, same = {}, [], True
+        t0 = time.perf_counter()
+        for fam, (data, feeds, _) in _norm_models().items():
+            with ort.InferenceSession(data, precision=prec) as s:
+                out = s.run(feeds)
+                again = s.run(feeds)
+                same = same and all(np.array_equal(out[k], again[k], equal_nan=True) for k in out)
+                got.update(out)
+                launches += s.launches()
+        print(f"norm families, {prec} sessions: {time.perf_counter() - t0:.2f} s, {len(launches)} launches")
+        _norm[prec] = (got, launches, same)
+    return _norm[prec]
+
+
+def _split_launches(launches, expect):
+    """{case: its launches} by the number each case expects ({case: tuple}), in case order."""
+    assert len(launches) == sum(len(v) for v in expect.values()), (len(launches), launches)
+    names, k = {}, 0
+    for cs in NORM:
+        names[cs.name] = launches[k:k + len(expect[cs.name])]
+        k += len(expect[cs.name])
+    return names
+
+
+def _check_launches(names, expect, failures):
+    for cs in NORM:
+        if not all(k in n for k, n in zip(expect[cs.name], names[cs.name])):
+            failures.append(f"{cs.name}: launched {names[cs.name]}, expected {expect[cs.name]}")
+
+
+def _check_exact(got, failures):
+    for cs in NORM:
+        if cs.exact and not all(np.array_equal(got[o], _norm["want"][o]) for o in _norm["outs"][cs.name]):
+            failures.append(f"{cs.name}: not equal to the oracle")
+
+
+def _inner(cs):
+    return int(np.prod(cs.inputs[0][1][2:]))
+
+
+def _no_plane(cs):
+    """`kernels` under VSO_NORM_PLANE=0: the pair for every plane launch, one piece included."""
+    out = []
+    for k in cs.kernels:
+        out += [OC.STATS, OC.APPLY] if k.startswith("k_norm_plane<") else [k]
+    return tuple(out)
+
+
+def _no_thin(cs):
+    """`kernels` under VSO_THIN=0: nothing is deferred — the norm's own launches by plane size — and a head
+    of up to 4 outputs runs on k_conv_pw (up to 192 channels on these few workgroups) or k_conv_small."""
+    out, ks = [], list(cs.kernels)
+    deferred = cs.name in OC.IBN and OC.IBN[cs.name]["defer"]
+    for j, k in enumerate(ks):
+        if deferred and k == OC.STATS:
+            out += list(OC.norm_launches(_inner(cs)))
+        elif deferred and k == OC.APPLY and ks[j - 1] == OC.STATS:
+            continue  # (flush_norm's, of the head no precision defers to: part of the pair above or not launched)
+        elif k.startswith("k_conv_thin<"):
+            c_in = [nd[1][0][1].shape[1] for nd in cs.chain if nd[0] == "Conv"][0]
+            out.append(OC.pw_name(1) if c_in <= 192 else OC.small(True, 16, True))
+        else:
+            out.append(k)
+    return tuple(out)
+
+
+NORM_KNOBS = {"VSO_NORM_PLANE=0": _no_plane, "VSO_THIN=0": _no_thin}
+
+
+@pytest.mark.parametrize("setting", sorted(NORM_KNOBS))
+def test_norm_family_knob(ort, setting):
+    """The inorm and ibn families' f32 sessions in a child process under one A/B knob (read once per
+    process; one child at a time, none after an abnormal end): every case at the bar (the `half` cases
+    exactly B[c]) on the launches the setting implies.  VSO_NORM_PLANE=0: every plane case on
+    k_norm_stats + k_norm_apply, down to planes of one element in one piece.  VSO_THIN=0: every
+    deferred case launches its apply step and the head runs on another conv kernel.  A case the knob does
+    not move is bitwise this process's."""
+    _norm_models()
+    expect = {cs.name: NORM_KNOBS[setting](cs) for cs in NORM}
+    moved = [cs for cs in NORM if expect[cs.name] != cs.kernels]
+    knob, value = setting.split("=")
+    t0 = time.perf_counter()
+    outs, info = C.run_child(setting, {knob: value}, ";".join(f"op_{fam}:f32" for fam in NORM_FAMILIES))
+    print(f"norm families, {setting} f32 child: {time.perf_counter() - t0:.2f} s")
+    got = {o: outs[f"op_{cs.family}/f32/{o}"] for cs in NORM for o in _norm["outs"][cs.name]}
+    launches = [n for fam in NORM_FAMILIES for n in info[f"op_{fam}/f32"]["launches"]]
+    assert all(info[f"op_{fam}/f32"]["rerun_equal"] for fam in NORM_FAMILIES)
+    names = _split_launches(launches, expect)
+    failures = _beyond_bar(got, _norm["want"], setting, names, NORM, _norm["outs"])
+    _check_launches(names, expect, failures)
+    _check_exact(got, failures)
+    here = _norm_sessions(ort, "f32")[0]
+    for cs in NORM:
+        if cs not in moved and not all(np.array_equal(got[o], here[o]) for o in _norm["outs"][cs.name]):
+            failures.append(f"{cs.name}: differs from the default session's output")
+    if knob == "VSO_NORM_PLANE":
+        assert len(moved) >= 60 and {_inner(cs) for cs in moved} >= {1, 2, 3, 4, 5, 4096, 4097, 36864}
+        assert not any("k_norm_plane" in n for n in launches)
+    else:
+        assert {cs.name for cs in moved} >= {k for k, v in OC.IBN.items() if v["defer"]} and len(moved) >= 9
+        assert not any("k_conv_thin" in n for n in launches)
+    assert not failures, "\n".join(failures)
+
+
+def _norm_tiled(cs):
+    """Whether a 16-bit session runs the case's pattern conv on k_conv_tile (onnx_ref.tiled_conv: the oracle
+    rounds its operands); the 1x1 heads and the inorm family never are."""
+    convs = ([(cs.inputs[1][1], cs.attrs)] if cs.op == "Conv" else []) + \
+        [(nd[1][0][1], nd[2]) for nd in cs.chain if nd[0] == "Conv"]
+    assert not any(R.tiled_conv(w, at_) for w, at_ in convs[1:]), cs.name
+    return bool(convs) and R.tiled_conv(*convs[0])
+
+
+@pytest.mark.parametrize("prec", ["bf16", "f16"])
+def test_norm_families_16bit(ort, prec):
+    """bf16 / f16 sessions of the inorm and ibn families.  A case whose conv the oracle does not round
+    (onnx_ref.tiled_conv) launches the f32 session's kernels, its output bitwise the f32 session's.  The
+    dense 3x3 patterns run on k_conv_tile, the other launches as in f32; their BatchNorm is folded into
+    the weights before these are rounded, which the oracle (it rounds the weights first) matches only on
+    the ibn16 cases' constants (the fold factor a power of two: tests/test_op_matrix_oracle.py) — those
+    are held to the matrix's bar against R.run(conv_operands=prec), the ibn family's 3x3 cases to their
+    launches and a bitwise second run."""
+    models = _norm_models()
+    if ("want", prec) not in _norm:
+        data, feeds, _ = models["ibn16"]
+        _norm["want", prec] = R.run(R.load(data), feeds, conv_operands=prec)
+    f32_out, f32_launches, _ = _norm_sessions(ort, "f32")
+    got, launches, same = _norm_sessions(ort, prec)
+    assert same, "the second run differs from the first"
+    tiled = [cs for cs in NORM if _norm_tiled(cs)]
+    assert len(tiled) >= 9 and all(cs in tiled for cs in OC.groups()["ibn16"])
+    expect = {cs.name: (("k_conv_tile<",) + cs.kernels[1:]) if cs in tiled else cs.kernels for cs in NORM}
+    names = _split_launches(launches, expect)
+    f32_names = _split_launches(f32_launches, {cs.name: cs.kernels for cs in NORM})
+    b16 = OC.groups()["ibn16"]
+    failures = _beyond_bar(got, _norm["want", prec], prec, names, b16, _norm["outs"])
+    _check_launches(names, expect, failures)
+    for cs in NORM:
+        if cs in tiled:
+            continue
+        if names[cs.name] != f32_names[cs.name]:
+            failures.append(f"{cs.name}: launched {names[cs.name]}, in f32 {f32_names[cs.name]}")
+        if not all(np.array_equal(got[o], f32_out[o], equal_nan=True) for o in _norm["outs"][cs.name]):
+            failures.append(f"{cs.name}: differs from the f32 session's output")
     assert not failures, "\n".join(failures)

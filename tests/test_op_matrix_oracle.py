@@ -10,6 +10,12 @@ Bars: data movement, MaxPool and nearest Resize compare equal; the rest agree
 to 1e-6 * max(1, |want|) per element (float64 against float64, both rounded
 to float32 once).  The refused cases must raise in the oracle too.
 
+The inorm and ibn families (InstanceNormalization alone, MODNet's IBNorm
+fusion) are pinned to 1e-12 and carry their own conditions: a float32
+restatement of the kernels' arithmetic (tests/norm_ref.py) within half the
+GPU bar, a Relu that leaves a quarter of the normalised values, and every
+mutant of the restatement beyond the bar on the case made for it.
+
 The ir family (inverted-residual blocks) is pinned to 1e-12 besides, and
 carries the conditions its GPU bar rests on: a numpy restatement of the fused
 kernels' arithmetic (tests/ir_ref.py) within half the bar, no saturated Clip,
@@ -239,12 +245,69 @@ def _conv_f64(xt, w, b, at):
     return y.float().double()
 
 
+NORM_FAMILIES = ("inorm", "ibn", "ibn9", "ibn16")
+
+
+def _ev64(op, ins, at, opset):
+    """One node of the norm families in double precision, its output rounded to float32 once: Conv by
+    _conv_f64, the norms by their definition (two-pass sums), the rest by torch's own operators."""
+    import torch
+    import torch.nn.functional as F
+
+    def T(v):
+        return v if torch.is_tensor(v) else _t(v)
+    x = T(ins[0])
+    if op == "Conv":
+        y = _conv_f64(x, ins[1], ins[2] if len(ins) > 2 else None, at)
+    elif op == "InstanceNormalization":
+        per_c = (1, -1) + (1,) * (x.ndim - 2)
+        # a two-pass sum (torch.var_mean's running update errs by 4e-13 on a mean of 100: enough to cross
+        # float32 ties on a few elements of a plane)
+        plane = x.shape[:2] + (1,) * (x.ndim - 2)
+        mean = (x.flatten(2).sum(dim=2) / x.flatten(2).shape[2]).reshape(plane)
+        var = (((x - mean) ** 2).flatten(2).sum(dim=2) / x.flatten(2).shape[2]).reshape(plane)
+        y = (x - mean) / torch.sqrt(var + float(np.float32(at.get("epsilon", 1e-5)))) * T(ins[1]).reshape(per_c) \
+            + T(ins[2]).reshape(per_c)
+    elif op == "BatchNormalization":
+        sc, bb, mu, var = (T(v).reshape((1, -1) + (1,) * (x.ndim - 2)) for v in ins[1:5])
+        y = (x - mu) / torch.sqrt(var + float(np.float32(at.get("epsilon", 1e-5)))) * sc + bb
+    elif op == "Slice":
+        if len(ins) > 1:
+            starts, ends = ins[1], ins[2]
+            axes = ins[3] if len(ins) > 3 else None
+            steps = ins[4] if len(ins) > 4 else None
+        else:
+            starts, ends, axes, steps = at["starts"], at["ends"], at.get("axes"), None
+        axes = list(range(len(starts))) if axes is None else axes
+        steps = [1] * len(starts) if steps is None else steps
+        y = x
+        for b, e, ax, st in zip(starts, ends, axes, steps):
+            ax = int(ax) % x.ndim
+            idx = _onnx_slice_indices(y.shape[ax], int(b), int(e), int(st))
+            y = y.index_select(ax, torch.tensor(idx, dtype=torch.long))
+    elif op == "Split":
+        return tuple(torch.split(x, [int(v) for v in ins[1]], dim=at["axis"]))
+    elif op == "Concat":
+        y = torch.cat([T(v) for v in ins], dim=at["axis"])
+    else:
+        assert op == "Relu", op
+        y = F.relu(x)
+    return y.float().double()
+
+
+def _norm_expected(cs, ops, chain_ops):
+    import norm_ref
+    return [_f32(o) for o in norm_ref.walk(cs, ops, chain_ops, _ev64)]
+
+
 def expected(cs, ops, chain_ops=()):
     """Outputs of the case (a list), evaluated independently of onnx_ref."""
     import torch
     import torch.nn.functional as F
     op, at = cs.op, cs.attrs
     xv = ops[0]
+    if cs.family in NORM_FAMILIES:
+        return _norm_expected(cs, ops, chain_ops)
     if op in ("MaxPool", "AveragePool"):
         return [_pool_expected(cs, xv)]
     if op in ("Resize", "Upsample"):
@@ -588,6 +651,149 @@ def test_ir_mutant_leaves_the_bar(mutant, name, form):
     ratio = _err_over_bar(bad, want)
     print(f"{name} {form} {mutant}: err / bar {ratio:.1f}")
     assert _err_over_bar(good, want) <= 0.5 and ratio > 1.0, (mutant, name, form, ratio)
+
+
+# ---- the norm families: InstanceNormalization alone and the IBNorm fusion -----------
+NORM = [k for k in OC.VALUE_CASES if k.family in NORM_FAMILIES]
+IBN_FUSED = [k for k in NORM if k.name in OC.IBN and OC.IBN[k.name]["fused"]]
+_norm_memo = {}
+
+
+def _norm_restated(cs, mutant=None, plane=True, thin=True):
+    """(the oracle's outputs, the restatement's (tests/norm_ref.py), what it kept) of a case."""
+    import norm_ref as NR
+    key = (cs.name, mutant, plane, thin)
+    if key not in _norm_memo:
+        feeds, want = _oracle_outputs(cs)
+        ops, chain_ops, keep = OC.operands(cs, feeds), OC.chain_operands(cs, feeds), {}
+        if cs in IBN_FUSED:
+            got = NR.run_ibn(cs, OC.IBN[cs.name], ops, chain_ops, mutant, plane, thin, keep)
+        elif cs.family == "inorm":
+            y = NR.inorm(ops[0], ops[1], ops[2], float(np.float32(cs.attrs.get("epsilon", 1e-5))), mutant, plane)
+            got = [np.maximum(y, np.float32(0)) if cs.chain else y]
+        else:
+            assert mutant is None
+            got = NR.walk(cs, ops, chain_ops, NR.ev32(plane))
+        _norm_memo[key] = (want, got, keep)
+    return _norm_memo[key]
+
+
+@pytest.mark.parametrize("name", [k.name for k in NORM])
+def test_norm_oracle_pinned_to_f64(name):
+    """onnx_ref on every case of the inorm and ibn families against the independent float64 evaluation
+    above (_ev64: conv2d in double on an input padded here, a two-pass mean and variance), to 1e-12 relative."""
+    cs = OC.BY_NAME[name]
+    feeds, got = _oracle_outputs(cs)
+    want = expected(cs, OC.operands(cs, feeds), OC.chain_operands(cs, feeds))
+    assert len(got) == len(want) == cs.n_out
+    for g, w in zip(got, want):
+        assert g.shape == w.shape and g.dtype == w.dtype == np.float32
+        assert (np.abs(g.astype(np.float64) - w) <= 1e-12 * np.maximum(1.0, np.abs(w))).all(), \
+            (name, float(np.abs(g.astype(np.float64) - w).max()))
+
+
+@pytest.mark.parametrize("name", [k.name for k in NORM])
+def test_norm_restatement_inside_half_the_bar(name):
+    """Each form's arithmetic, restated in float32, is within half the bar of the oracle on every element
+    (a `half` case: exactly B[c], as the oracle); where a Relu follows the norm, at least a quarter of the
+    normalised outputs are positive (a Relu that clips nearly all of them hides the norm's errors)."""
+    cs = OC.BY_NAME[name]
+    want, got, keep = _norm_restated(cs)
+    ratio = _err_over_bar(got, want)
+    print(f"{name}: restatement err / bar {ratio:.4f}")
+    assert ratio <= 0.5, (name, ratio)
+    if cs.exact:
+        b = cs.inputs[2][1].reshape((1, -1) + (1,) * (got[0].ndim - 2))
+        assert np.array_equal(got[0], np.broadcast_to(b, got[0].shape)) and np.array_equal(want[0], got[0])
+    relu = OC.IBN[name]["relu"] if name in OC.IBN else bool(cs.chain)
+    if relu and (cs.family == "inorm" or cs in IBN_FUSED):
+        v = keep["normalised"] if cs in IBN_FUSED else got[0]
+        share = float((v > 0).mean())
+        print(f"{name}: {share:.3f} of the normalised outputs positive")
+        assert share >= 0.25, (name, share)
+
+
+def test_norm_families_cover_the_forms():
+    """Every launch the GPU file asserts has a case naming it: the plane instances in their float4 and scalar
+    forms on both sides of each limit, the pair, and k_conv_thin<1..4> behind a deferred norm."""
+    inn = [k for k in NORM if k.family == "inorm"]
+    inner = lambda k: int(np.prod(k.inputs[0][1][2:]))
+    for form, lo, hi in ((OC.PLANE16, 1, 4096), (OC.PLANE48, 4097, 12288), (OC.PLANE36, 12289, 36864)):
+        sizes = {inner(k) for k in inn if k.kernels[0] == form}
+        assert {lo, hi} <= sizes and all(lo <= v <= hi for v in sizes), (form, sizes)
+        assert {v % 4 == 0 for v in sizes} == {False, True}
+    pair = {inner(k) for k in inn if k.kernels[:2] == (OC.STATS, OC.APPLY)}
+    assert {36865, 36868, 40960, 262656, 525625} <= pair and min(pair) == 36865
+    deferred = [k for k in IBN_FUSED if OC.IBN[k.name]["defer"]]
+    assert {k.kernels[-1] for k in deferred} >= {OC.THIN % m for m in (1, 2, 3, 4)}
+    assert all(k.kernels[1] == OC.STATS and OC.APPLY not in k.kernels for k in deferred if k.name != "IBN_head_ibn_63")
+    planes = {inner(k) for k in deferred}
+    assert {63, 4096, 36865, 262656, 525625} <= planes  # 1 piece, 10 (the last of 1), 65, 129
+    assert any(OC.IBN[k.name]["cat"] and OC.IBN[k.name]["cat"][0] == q for k in IBN_FUSED for q in (0, 1))
+    convs = {k.kernels[0] for k in IBN_FUSED}
+    assert {"k_conv_tile<", OC.small(False, 8, False), OC.pw_name(5), OC.pw_name(24), OC.pw_name(256)} <= convs
+    m_nb = {(OC.IBN[k.name]["m"], OC.IBN[k.name]["nb"]) for k in IBN_FUSED}
+    assert m_nb >= {(5, 1), (5, 4), (24, 12), (24, 7), (32, 16), (32, 5)}
+    for k in NORM:
+        assert k.kernels, k.name
+
+
+NORM_MUTANTS = [
+    ("cnt_m1", "IN_2"), ("cnt_m1", "IN_3"), ("cnt_m1", "IN_5"),
+    ("last_full", "IN_36865"), ("last_full", "IBN_thin2_36865"),
+    ("no_between", "IN_40960"), ("no_between", "IN_262656"), ("no_between", "IBN_thin2_36865"),
+    ("no_between", "IBN_thin3_262656"),
+    ("drop64", "IBN_thin3_262656"), ("drop64", "IBN_thin4_525625"),
+    ("one_pass", "IN_4095_off100"), ("one_pass", "IN_12288_off100"), ("one_pass", "IN_36863_off100"),
+    ("one_pass", "IN_36868_off100"),
+    ("no_eps", "IN_4095_small_eps1e-5"), ("no_eps", "IN_12288_small_eps1e-3"), ("no_eps", "IN_36863_small_eps1e-5"),
+    ("no_eps", "IN_36868_small_eps1e-3"), ("no_eps", "IN_default_eps"), ("no_eps", "IBN_thin2_63_small"),
+    ("bn_no_eps", "IBN_pw_M5_nb2_var0.01"),
+    ("c0_zero", "IBN_pw_M5_nb1_4"), ("c0_zero", "IBN_thin1_63"), ("c0_zero", "IBN_tile_M32_nb16_2304"),
+    ("c0_zero", "IBN_cat_second_63"),
+    ("ctot_M", "IBN_cat_first_63"), ("ctot_M", "IBN_cat_second_63"), ("ctot_M", "IBN_cat_second_36868"),
+    ("stats_img0", "IN_63_relu"), ("stats_img0", "IN_36868"), ("stats_img0", "IBN_thin2_36865"),
+    ("stats_img0", "IBN_cat_first_63"),
+    ("relu_all", "IBN_pw_M5_nb4_63_neg"), ("relu_all", "IBN_thin4_4096"), ("relu_all", "IBN_cat_second_63"),
+    ("no_relu_norm", "IBN_pw_M5_nb1_4"), ("no_relu_norm", "IBN_thin1_63"), ("no_relu_norm", "IBN_cat_first_63"),
+    ("no_relu_norm", "IBN_tile_thin2_2304"),
+]
+
+
+@pytest.mark.parametrize("mutant,name", NORM_MUTANTS)
+def test_norm_mutant_leaves_the_bar(mutant, name):
+    """Each way the norm kernels or the fusion could be wrong, applied to the restatement, is beyond the bar
+    on the case made for it, while the restatement itself stays within half of it."""
+    cs = OC.BY_NAME[name]
+    want, good, _ = _norm_restated(cs)
+    _, bad, _ = _norm_restated(cs, mutant)
+    ratio = _err_over_bar(bad, want)
+    print(f"{name} {mutant}: err / bar {ratio:.1f} (the restatement: {_err_over_bar(good, want):.4f})")
+    assert _err_over_bar(good, want) <= 0.5 and ratio > 1.0, (mutant, name, ratio)
+
+
+def test_every_norm_mutant_has_a_case():
+    import norm_ref as NR
+    assert {m for m, _ in NORM_MUTANTS} == set(NR.MUTANTS)
+
+
+@pytest.mark.parametrize("name", [k.name for k in NORM if k.family == "ibn16"])
+def test_ibn16_fold_commutes_with_rounding(name):
+    """A 16-bit session folds the BatchNorm into the conv's weights and then rounds them; the oracle
+    (R.run(conv_operands=...)) rounds the weights and then applies the BatchNorm.  With the family's
+    constants the fold factor is a power of two, so the two orders give the same weights bit for bit."""
+    cs = OC.BY_NAME[name]
+    meta = OC.IBN[name]
+    w = cs.inputs[1][1]
+    sc, _, _, var = (spec[1].astype(np.float64) for spec in cs.chain[meta["i_bn"] - 1][1][1:5])
+    a = sc / np.sqrt(var + float(np.float32(cs.chain[meta["i_bn"] - 1][2]["epsilon"])))
+    assert np.array_equal(a, 2.0 ** np.round(np.log2(a))) and len(set(a.tolist())) > 1, a
+    assert R.tiled_conv(w, cs.attrs)
+    a4 = a.reshape(-1, 1, 1, 1)
+    for prec in ("bf16", "f16"):
+        folded_then_rounded = R.round_operand((w[:meta["nb"]].astype(np.float64) * a4).astype(np.float32), prec)
+        rounded_then_folded = (R.round_operand(w[:meta["nb"]], prec).astype(np.float64) * a4).astype(np.float32)
+        assert np.array_equal(folded_then_rounded, rounded_then_folded), (name, prec)
 
 
 def test_earlier_cases_build_as_before():
