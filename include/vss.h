@@ -525,7 +525,10 @@ int vss_background_set_color(vss_background* bg, int r, int g, int b);
  * bytes per row; copied to the GPU before the call returns. */
 int vss_background_set_image(vss_background* bg, const uint8_t* pixels, int height, int width, int channels,
                              size_t row_stride);
-/* radius in 1..32, sigma > 0 (and large enough for one off-centre weight >= 1). */
+/* radius in 1..32, sigma > 0 (and large enough for one off-centre weight >= 1).
+ * Like vss_background_set_image it waits on the host for the object's latest
+ * composite and copies to the GPU before it returns: the taps also live in a
+ * 66-byte device buffer of the object, which the calls of vss_streams.h read. */
 int vss_background_set_blur(vss_background* bg, int radius, double sigma);
 /* Back to a mode with the colour, image or blur it was last given (a user
  * toggling between them: the image is not uploaded again).  A composite in
@@ -608,5 +611,6 @@ int vss_segment_background(vss_handle* h, vss_post_state* st, vss_background* bg
 #include "vss_video.h"
 #include "vss_pool.h"
 #include "vss_layers.h"
+#include "vss_streams.h"
 
 #endif /* VSS_H_ */

@@ -214,6 +214,11 @@ def lib() -> ctypes.CDLL:
                 "vss_post_pool_reset": ([P, I], I),
                 "vss_post_pool_process_device": ([P, P, I, P, I, I, I, S, S, P, P, P, P, P], I),
                 "vss_segment_post_pool": ([P, P, P, P, I, I, I, I, S, P, P], I),
+                "vss_background_composite_streams_device": ([P, P, I, P, I, I, I, S, S, P, P, S, S, P], I),
+                "vss_segment_background_streams": ([P, P, P, P, P, I, I, I, I, S, P], I),
+                "vss_video_process_streams_device": ([P, P, P, P, P, P, S, S, P, S, S, I, I, I, P, S, S, P, S, S, P],
+                                                     I),
+                "vss_video_process_streams": ([P, P, P, P, P, P, I, I, I, P, P], I),
             }
             for name, (args, res) in sig.items():
                 fn = getattr(L, name)
@@ -722,6 +727,25 @@ class PostPool:
                                            a.ctypes.data, u.ctypes.data), s._h)
         return a, u, s.mask_w, s.mask_h
 
+    def replace_backgrounds(self, ids, frames: np.ndarray, bgs) -> np.ndarray:
+        """frames [N,H,W,3|4] u8, frame t the next frame of stream ids[t] -> that person over
+        bgs[t] (include/vss_streams.h): opaque RGBA u8 [N,H,W,4].  One Background may stand
+        for several frames."""
+        s = self.session
+        f = _as_frames(frames)
+        n, hh, ww, c = f.shape
+        out = np.empty((n, hh, ww, 4), np.uint8)
+        _check(lib().vss_segment_background_streams(s._h, self._p, self._ids(ids, n), _bgs(bgs, n), f.ctypes.data, n,
+                                                    hh, ww, c, ww * c, out.ctypes.data), s._h)
+        return out
+
+
+def _bgs(bgs, n: int):
+    """n Background objects (None stays a null pointer, for the library to refuse) as a vss_background* array."""
+    if len(bgs) != n:
+        raise VssError(VSS_E_INVALID_ARG, f"{len(bgs)} backgrounds for {n} frames")
+    return (ctypes.c_void_p * n)(*(b._bg if b is not None else None for b in bgs))
+
 
 def composite_device(session: Session, frames_ptr: int, n: int, h: int, w: int, c: int, row_stride: int,
                      frame_stride: int, alpha_u8_ptr: int, out_ptr: int, out_row_stride: int = 0,
@@ -922,6 +946,18 @@ def background_composite_device(session: Session, bg: Background, frames_ptr: in
                                                  out_frame_stride or ors * h, stream or None), session._h)
 
 
+def composite_streams_device(session: Session, bgs, frames_ptr: int, n: int, h: int, w: int, c: int, row_stride: int,
+                             frame_stride: int, alpha_u8_ptr: int, out_ptr: int, out_row_stride: int = 0,
+                             out_frame_stride: int = 0, stream: int = 0):
+    """HBM in/out, one frame per stream (include/vss_streams.h): frame t over bgs[t], each
+    frame's bytes those of background_composite_device with n = 1."""
+    ors = out_row_stride or w * 4
+    _check(lib().vss_background_composite_streams_device(session._h, _bgs(bgs, n), n, frames_ptr or None, h, w, c,
+                                                         row_stride, frame_stride, alpha_u8_ptr or None,
+                                                         out_ptr or None, ors, out_frame_stride or ors * h,
+                                                         stream or None), session._h)
+
+
 def background_alpha_device(session: Session, bg: Background, frames_ptr: int, n: int, h: int, w: int, c: int,
                             row_stride: int, frame_stride: int, alpha_u8_ptr: int, out_ptr: int,
                             out_row_stride: int = 0, out_frame_stride: int = 0, stream: int = 0, mask_hw=None):
@@ -1027,6 +1063,31 @@ class Video:
                                               y_frame_stride, uv_ptr or None, uv_pitch, uv_frame_stride, n, h, w,
                                               out_y_ptr or None, out_y_pitch, out_y_frame_stride, out_uv_ptr or None,
                                               out_uv_pitch, out_uv_frame_stride, stream or None), self.session._h)
+
+    def process_streams(self, y: np.ndarray, uv: np.ndarray, pool: PostPool, ids, bgs):
+        """Host NV12, one frame per stream (include/vss_streams.h): frame t the next frame of
+        pool's stream ids[t] -> (y, uv) of that person over bgs[t]; synchronous."""
+        ya, ua = _as_nv12(y, uv)
+        n, hh, ww = ya.shape
+        oy, ouv = np.empty_like(ya), np.empty_like(ua)
+        _check(lib().vss_video_process_streams(self._v, pool._p, PostPool._ids(ids, n), _bgs(bgs, n), ya.ctypes.data,
+                                               ua.ctypes.data, n, hh, ww, oy.ctypes.data, ouv.ctypes.data),
+               self.session._h)
+        return oy, ouv
+
+    def process_streams_device(self, pool: PostPool, ids, bgs, y_ptr: int, y_pitch: int, y_frame_stride: int,
+                               uv_ptr: int, uv_pitch: int, uv_frame_stride: int, n: int, h: int, w: int,
+                               out_y_ptr: int, out_y_pitch: int, out_y_frame_stride: int, out_uv_ptr: int,
+                               out_uv_pitch: int, out_uv_frame_stride: int, stream: int = 0, faces_ptr: int = 0):
+        """HBM in/out, one frame per stream, everything enqueued on `stream`, nothing waited
+        for; faces_ptr = n vss_face_frame in device memory."""
+        _check(lib().vss_video_process_streams_device(self._v, pool._p if pool is not None else None,
+                                                      PostPool._ids(ids, n), _bgs(bgs, n), faces_ptr or None,
+                                                      y_ptr or None, y_pitch, y_frame_stride, uv_ptr or None,
+                                                      uv_pitch, uv_frame_stride, n, h, w, out_y_ptr or None,
+                                                      out_y_pitch, out_y_frame_stride, out_uv_ptr or None,
+                                                      out_uv_pitch, out_uv_frame_stride, stream or None),
+               self.session._h)
 
 
 def blur_weights(radius: int, sigma: float) -> np.ndarray:

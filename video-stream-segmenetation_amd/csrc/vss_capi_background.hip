@@ -180,7 +180,162 @@ int plate_enqueue(vss_handle* h, vss_background* bg, int fh, int fw, hipStream_t
   return VSS_OK;
 }
 
+// bg->mu held; image mode, or colour mode under visible layers (`layered`: O is
+// built).  The cached plate d_img for a frame fh x fw: the scaled image, or with
+// layers bg' = O over the image or the colour; rebuilt on s when it is stale.
+int image_enqueue(vss_handle* h, vss_background* bg, bool layered, int fh, int fw, hipStream_t s) {
+  const int mode = bg->mode;
+  if (bg->img_fh == fh && bg->img_fw == fw && bg->img_mode == mode && bg->img_layered == layered &&
+      !(mode == VSS_BG_COLOR && bg->img_color != bg->color))
+    return VSS_OK;
+  if (int rc = bg_grow(bg, &bg->d_img, &bg->img_bytes, (size_t)bg_image_stride(fw) * fh)) return rc;
+  bg->img_fh = bg->img_fw = 0;
+  if (mode == VSS_BG_IMAGE) {
+    BgResizeParams r{};
+    r.src = bg->d_src;
+    r.sh = bg->sh; r.sw = bg->sw; r.sc = bg->sc;
+    r.sy = (float)bg->sh / (float)fh;
+    r.sx = (float)bg->sw / (float)fw;
+    r.out = bg->d_img;
+    r.fh = fh; r.fw = fw;
+    launch_bg_resize(r, s);
+    bg->img_for_image = true;
+  }
+  if (layered) {
+    BgBakeParams b{};
+    b.image = bg->d_img;
+    b.overlay = bg->d_plate;
+    b.fh = fh; b.fw = fw;
+    b.from_color = mode == VSS_BG_COLOR;
+    b.color = bg->color;
+    launch_bg_bake(b, s);
+  }
+  bg->img_fh = fh;
+  bg->img_fw = fw;
+  bg->img_mode = mode;
+  bg->img_layered = layered;
+  bg->img_color = bg->color;
+  return VSS_OK;
+}
+
+// what a composite refuses an object's settings for, frames fh x fw over a mask H x W (bg->mu held)
+int settings_check(vss_handle* h, const vss_background* bg, int fh, int fw, int H, int W) {
+  if (bg->mode == VSS_BG_IMAGE && !bg->d_src)
+    return fail(h, VSS_E_INVALID_ARG, "background is in image mode but no image was set");
+  if (bg->mode == VSS_BG_BLUR && !bg->radius)
+    return fail(h, VSS_E_INVALID_ARG, "background is in blur mode but no blur was set");
+  if (bg->refine_radius && (fh < H || fw < W))
+    return fail(h, VSS_E_INVALID_ARG, "refinement needs a frame no smaller than the mask (" + std::to_string(H) +
+                                          " x " + std::to_string(W) + "); turn it off for smaller frames");
+  if (bg->refine_radius && W > 16384) return fail(h, VSS_E_INVALID_ARG, "refinement: mask wider than 16384");
+  return VSS_OK;
+}
+
 }  // namespace
+
+int vss_engine::bg_streams_args(vss_handle* h, vss_background* const* bgs, int n) {
+  if (!bgs) return fail(h, VSS_E_INVALID_ARG, "null background array");
+  for (int t = 0; t < n; ++t)
+    if (!bgs[t] || bgs[t]->h != h)
+      return fail(h, VSS_E_INVALID_ARG, "handle / background mismatch at frame " + std::to_string(t));
+  return VSS_OK;
+}
+
+int vss_engine::bg_streams_check(vss_handle* h, vss_background* const* bgs, int n, int fh, int fw) {
+  for (int t = 0; t < n; ++t)
+    if (int rc = settings_check(h, bgs[t], fh, fw, h->cfg.model_h, h->cfg.model_w)) return rc;
+  return VSS_OK;
+}
+
+// Every object's scratch holds one slot per frame of the call that names it;
+// frame t uses the slot of its rank among them.  Stale caches are rebuilt per
+// object; after that the launch count depends on neither n nor the number of
+// objects: per kBgStreamFrames frames the matte stage over the refined frames,
+// k_blur_h and the blur form over the blur frames, the flat form over the rest.
+int vss_engine::bg_streams_enqueue(vss_handle* h, const BgStreamsLock& lk, vss_background* const* bgs, int n,
+                                   const uint8_t* d_frames, int fh, int fw, int fc, size_t rs, size_t fs,
+                                   const uint8_t* d_alpha, uint8_t* d_out, size_t ors, size_t ofs, hipStream_t s) {
+  const int H = h->cfg.model_h, W = h->cfg.model_w;
+  const size_t P = (size_t)H * W, fpx = (size_t)fh * fw;
+  // per distinct object: the frames of the call that use it
+  std::vector<int> uses(lk.objs.size(), 0), rank((size_t)n), obj((size_t)n);
+  for (int t = 0; t < n; ++t) {
+    obj[t] = (int)(std::lower_bound(lk.objs.begin(), lk.objs.end(), bgs[t], std::less<vss_background*>()) -
+                   lk.objs.begin());
+    rank[t] = uses[obj[t]]++;
+  }
+  std::vector<char> layered(lk.objs.size());
+  for (size_t i = 0; i < lk.objs.size(); ++i) {
+    vss_background* bg = lk.objs[i];
+    // the object's previous composite (and the caches it may have built) may have run on another stream
+    int rc = bg->fence.wait_on(h, s);
+    if (!rc && bg->refine_radius) rc = bg_grow(bg, &bg->d_matte, &bg->matte_bytes, (size_t)uses[i] * P * 17);
+    layered[i] = layers_visible(bg);
+    if (!rc && layered[i]) rc = plate_enqueue(h, bg, fh, fw, s);
+    if (!rc && (bg->mode == VSS_BG_IMAGE || (bg->mode == VSS_BG_COLOR && layered[i])))
+      rc = image_enqueue(h, bg, layered[i], fh, fw, s);
+    if (!rc && bg->mode == VSS_BG_BLUR) rc = bg_grow(bg, &bg->d_hblur, &bg->hblur_bytes, (size_t)uses[i] * fpx * 4);
+    if (rc) return rc;
+  }
+  int rc = VSS_OK;
+  for (int t0 = 0; t0 < n && !rc; t0 += kBgStreamFrames) {
+    const int m = std::min(kBgStreamFrames, n - t0);
+    BgStreamsParams p{};
+    MatteStreamsParams mp{};
+    composite_params(&p.c, d_frames + (size_t)t0 * fs, fh, fw, fc, rs, fs, d_alpha + (size_t)t0 * P, H, W,
+                     d_out + (size_t)t0 * ofs, ors, ofs);
+    int nflat = 0, nblur = 0, nmatte = 0, max_radius = 0;
+    for (int t = 0; t < m; ++t) {
+      const vss_background* bg = bgs[t0 + t];
+      const size_t k = (size_t)rank[t0 + t], of = (size_t)uses[obj[t0 + t]];  // slot k of `of`
+      BgStreamEntry& e = p.entry[t];
+      e.color = bg->color;
+      if (bg->refine_radius) {
+        // the object's planes as for a batch of `of` frames: (abar, bbar), (a_q, b_q), L
+        MatteStreamEntry& me = mp.entry[t];
+        me.ab = reinterpret_cast<float2*>(bg->d_matte) + k * P;
+        me.q = reinterpret_cast<int2*>(bg->d_matte + of * P * 8) + k * P;
+        me.L = bg->d_matte + of * P * 16 + k * P;
+        me.eps = bg->refine_eps;
+        me.radius = bg->refine_radius;
+        e.ab = me.ab;
+        stream_list_set(mp.list, nmatte++, t);
+      }
+      if (bg->mode == VSS_BG_BLUR) {
+        e.hblur = bg->d_hblur + k * fpx;
+        e.overlay = layered[obj[t0 + t]] ? bg->d_plate : nullptr;
+        e.taps = bg->d_taps;
+        e.radius = bg->radius;
+        max_radius = std::max(max_radius, bg->radius);
+        stream_list_set(p.blur, nblur++, t);
+      } else {
+        if (bg->mode == VSS_BG_IMAGE || layered[obj[t0 + t]]) e.image = bg->d_img;  // a colour under layers is a plate too
+        stream_list_set(p.flat, nflat++, t);
+      }
+    }
+    if (nmatte) {
+      MatteParams& g = mp.m;
+      g.frames = p.c.frames;
+      g.row_stride = (long)rs;
+      g.frame_stride = (long)fs;
+      g.fh = fh; g.fw = fw; g.fc = fc;
+      g.alpha = p.c.alpha;
+      g.H = H; g.W = W;
+      launch_matte_streams(mp, nmatte, s);
+    }
+    launch_bg_streams(p, nflat, nblur, max_radius, s);
+    rc = launched(h, "background streams");
+  }
+  // One event for the call: the first object records it, the others follow it (Fence, vss_engine.h).  Also after
+  // a failed launch: what did go out reads the objects' taps, caches and scratch, which a setter may rewrite
+  // only after waiting for this event.
+  vss_background* first = lk.objs.front();
+  const int rr = first->fence.record(h, s);
+  if (rr) return rr;
+  for (vss_background* bg : lk.objs)
+    if (bg != first) bg->fence.follow(first->fence);
+  return rc;
+}
 
 // bg->mu held.  The fence is recorded only after a composite that went out whole.
 int vss_engine::bg_enqueue(vss_handle* h, vss_background* bg, const uint8_t* d_frames, int n, int fh, int fw, int fc,
@@ -207,37 +362,7 @@ int vss_engine::bg_enqueue(vss_handle* h, vss_background* bg, const uint8_t* d_f
   }
   int mode = bg->mode;
   if (mode == VSS_BG_IMAGE || (mode == VSS_BG_COLOR && layered)) {
-    // the cached plate: the scaled image, or with layers bg' = O over the image or the colour
-    if (bg->img_fh != fh || bg->img_fw != fw || bg->img_mode != mode || bg->img_layered != layered ||
-        (mode == VSS_BG_COLOR && bg->img_color != bg->color)) {
-      if (int rc = bg_grow(bg, &bg->d_img, &bg->img_bytes, (size_t)bg_image_stride(fw) * fh)) return rc;
-      bg->img_fh = bg->img_fw = 0;
-      if (mode == VSS_BG_IMAGE) {
-        BgResizeParams r{};
-        r.src = bg->d_src;
-        r.sh = bg->sh; r.sw = bg->sw; r.sc = bg->sc;
-        r.sy = (float)bg->sh / (float)fh;
-        r.sx = (float)bg->sw / (float)fw;
-        r.out = bg->d_img;
-        r.fh = fh; r.fw = fw;
-        launch_bg_resize(r, s);
-        bg->img_for_image = true;
-      }
-      if (layered) {
-        BgBakeParams b{};
-        b.image = bg->d_img;
-        b.overlay = bg->d_plate;
-        b.fh = fh; b.fw = fw;
-        b.from_color = mode == VSS_BG_COLOR;
-        b.color = bg->color;
-        launch_bg_bake(b, s);
-      }
-      bg->img_fh = fh;
-      bg->img_fw = fw;
-      bg->img_mode = mode;
-      bg->img_layered = layered;
-      bg->img_color = bg->color;
-    }
+    if (int rc = image_enqueue(h, bg, layered, fh, fw, s)) return rc;
     p.image = bg->d_img;
     mode = VSS_BG_IMAGE;  // a colour under layers is a plate too
   } else if (bg->mode == VSS_BG_BLUR) {
@@ -294,6 +419,7 @@ void vss_background_destroy(vss_background* bg) {
   (void)counted_alloc(bg->h, &bg->d_src, &bg->src_bytes, 0);
   (void)counted_alloc(bg->h, &bg->d_img, &bg->img_bytes, 0);
   (void)counted_alloc(bg->h, &bg->d_hblur, &bg->hblur_bytes, 0);
+  (void)counted_alloc(bg->h, &bg->d_taps, &bg->taps_bytes, 0);
   (void)counted_alloc(bg->h, &bg->d_matte, &bg->matte_bytes, 0);
   (void)counted_alloc(bg->h, &bg->d_sprites, &bg->sprites_bytes, 0);
   (void)counted_alloc(bg->h, &bg->d_plate, &bg->plate_bytes, 0);
@@ -355,7 +481,17 @@ int vss_background_set_blur(vss_background* bg, int radius, double sigma) {
   const int rc = blur_weights(radius, sigma, w, &why);
   if (rc) return fail(bg->h, rc, why);
   std::lock_guard<std::mutex> lk(bg->mu);
-  for (int k = 0; k <= radius; ++k) bg->w[k] = w[radius + k];
+  // The device copy of the taps, which the calls over many streams read: the object's latest composite may
+  // still read the old ones, so this setter waits for it on the host (the others that rewrite device data,
+  // set_image and set_layers, always did).
+  int rc2 = bg->fence.quiesce(bg->h);
+  if (!rc2 && !bg->d_taps) rc2 = counted_alloc(bg->h, &bg->d_taps, &bg->taps_bytes, sizeof(bg->w));
+  if (rc2) return rc2;
+  uint16_t half[kBlurMaxRadius + 1] = {};
+  for (int k = 0; k <= radius; ++k) half[k] = w[radius + k];
+  const hipError_t e = hipMemcpy(bg->d_taps, half, sizeof(half), hipMemcpyHostToDevice);
+  if (e != hipSuccess) return fail(bg->h, VSS_E_HIP, std::string("taps upload: ") + hipGetErrorString(e));
+  for (int k = 0; k <= radius; ++k) bg->w[k] = half[k];
   bg->radius = radius;
   bg->mode = VSS_BG_BLUR;
   return VSS_OK;

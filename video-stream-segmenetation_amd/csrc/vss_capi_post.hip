@@ -339,26 +339,8 @@ int vss_segment_composite(vss_handle* h, vss_post_state* st, const uint8_t* fram
 }  // extern "C"
 
 // ---- the post chain over many streams (vss_post.hip k_post_pool; include/vss_pool.h) ----
-struct vss_post_pool {
-  vss_handle* h = nullptr;
-  std::mutex mu;                  // calls, resets and setters of one pool are serialised
-  vss_post_config cfg{};
-  int capacity = 0;
-  float* planes = nullptr;        // [capacity][2][P] prevAlpha, double-buffered per stream
-  size_t planes_bytes = 0;
-  PostTables tab;                 // one range table for every stream
-  size_t rtab_bytes = 0;
-  std::vector<uint8_t> seen;      // per stream: it has seen a frame (prevAlpha exists)
-  std::vector<uint8_t> cur;       // per stream: the plane that holds its prevAlpha
-  std::vector<uint64_t> stamp;    // per stream: the last call that named it (duplicate ids)
-  uint64_t calls = 0;
-  Fence fence;                    // recorded after every call
-};
-
-namespace {
-
 // p->mu held.  What a call may be refused for, before anything is enqueued.
-int pool_check(vss_post_pool* p, const int* ids, int n, const uint8_t* d_frames, int fh, int fw, int fc, size_t rs,
+int vss_engine::pool_check(vss_post_pool* p, const int* ids, int n, const uint8_t* d_frames, int fh, int fw, int fc, size_t rs,
                size_t fs, int max_n) {
   vss_handle* h = p->h;
   if (!ids) return fail(h, VSS_E_INVALID_ARG, "pool: null stream ids");
@@ -377,7 +359,7 @@ int pool_check(vss_post_pool* p, const int* ids, int n, const uint8_t* d_frames,
 }
 
 // p->mu held; arguments checked.  ceil(n / kPoolFrames) launches and the ordering event.
-int pool_enqueue(vss_post_pool* p, const int* ids, int n, const uint8_t* d_frames, int fh, int fw, int fc, size_t rs,
+int vss_engine::pool_enqueue(vss_post_pool* p, const int* ids, int n, const uint8_t* d_frames, int fh, int fw, int fc, size_t rs,
                  size_t fs, const float* d_masks, const FaceFrame* d_faces, float* d_alpha, uint8_t* d_u8,
                  hipStream_t s) {
   vss_handle* h = p->h;
@@ -413,8 +395,6 @@ int pool_enqueue(vss_post_pool* p, const int* ids, int n, const uint8_t* d_frame
   const int rr = p->fence.record(h, s);
   return rr ? rr : rc;
 }
-
-}  // namespace
 
 extern "C" {
 

@@ -6,18 +6,6 @@
 using namespace vss;
 using namespace vss_engine;
 
-struct vss_video {
-  vss_handle* h = nullptr;
-  std::mutex mu;                 // setters and calls of one object are serialised
-  int std_ = VSS_CSC_BT709_LIMITED;
-  uint8_t* d_buf = nullptr;      // RGBA in | RGBA out (px_cap pixels each) | masks f32 | alpha u8 (max_batch frames)
-  size_t buf_bytes = 0, px_cap = 0;
-  uint8_t* d_nv = nullptr;       // the host call's device planes: Y in | UV in | Y out | UV out
-  size_t nv_bytes = 0;
-  int slot = -1;                 // the handle slot whose executable graph is bound to d_buf (taken by the first call)
-  Fence fence;                   // recorded after every call
-};
-
 namespace {
 
 constexpr CscCoef kCsc[4] = {
@@ -32,8 +20,10 @@ int check_std(vss_handle* h, int std) {
   return VSS_OK;
 }
 
+}  // namespace
+
 // one NV12 batch's geometry; `what` names the planes in the message
-int check_nv12(vss_handle* h, const char* what, const uint8_t* y, size_t yp, size_t yfs, const uint8_t* uv, size_t up,
+int vss_engine::check_nv12(vss_handle* h, const char* what, const uint8_t* y, size_t yp, size_t yfs, const uint8_t* uv, size_t up,
                size_t ufs, int n, int fh, int fw, int max_n) {
   const std::string w(what);
   if (!y || !uv) return fail(h, VSS_E_INVALID_ARG, w + ": null plane pointer");
@@ -46,6 +36,8 @@ int check_nv12(vss_handle* h, const char* what, const uint8_t* y, size_t yp, siz
   return VSS_OK;
 }
 
+namespace {
+
 int check_rgba(vss_handle* h, const uint8_t* p, size_t rs, size_t fs, int fh, int fw) {
   if (!p) return fail(h, VSS_E_INVALID_ARG, "null RGBA pointer");
   if (!rgba_geometry_ok(p, rs, fs, fh, fw, true))
@@ -54,7 +46,9 @@ int check_rgba(vss_handle* h, const uint8_t* p, size_t rs, size_t fs, int fh, in
   return VSS_OK;
 }
 
-Nv12Params nv12_params(int std, const uint8_t* y, size_t yp, size_t yfs, const uint8_t* uv, size_t up, size_t ufs,
+}  // namespace
+
+Nv12Params vss_engine::nv12_params(int std, const uint8_t* y, size_t yp, size_t yfs, const uint8_t* uv, size_t up, size_t ufs,
                        const uint8_t* rgba, size_t rs, size_t fs, int fh, int fw) {
   Nv12Params p{};
   p.y = const_cast<uint8_t*>(y);
@@ -68,20 +62,30 @@ Nv12Params nv12_params(int std, const uint8_t* y, size_t yp, size_t yfs, const u
   return p;
 }
 
+// v->mu held: the scratch for n frames fh x fw
+int vss_engine::video_reserve(vss_video* v, int n, int fh, int fw) {
+  vss_handle* h = v->h;
+  const size_t px = (size_t)n * fh * fw, P = (size_t)h->cfg.model_h * h->cfg.model_w;
+  const size_t nb = (size_t)max_frames(h);
+  if (px <= v->px_cap) return VSS_OK;
+  int rc = v->fence.quiesce(h);  // the scratch is freed: v's latest call has ended
+  if (rc) return rc;
+  v->px_cap = 0;
+  if ((rc = counted_alloc(h, &v->d_buf, &v->buf_bytes, px * 8 + nb * P * 5))) return rc;
+  v->px_cap = px;
+  return VSS_OK;
+}
+
+namespace {
+
 // v->mu held; arguments checked.  The whole chain on s.
 int video_enqueue(vss_video* v, vss_post_state* st, vss_background* bg, const uint8_t* d_y, size_t yp, size_t yfs,
                   const uint8_t* d_uv, size_t up, size_t ufs, int n, int fh, int fw, uint8_t* d_oy, size_t oyp,
                   size_t oyfs, uint8_t* d_ouv, size_t oup, size_t oufs, hipStream_t s) {
   vss_handle* h = v->h;
-  const size_t px = (size_t)n * fh * fw, P = (size_t)h->cfg.model_h * h->cfg.model_w;
-  const size_t nb = (size_t)max_frames(h);
-  int rc;
-  if (px > v->px_cap) {
-    if ((rc = v->fence.quiesce(h))) return rc;  // the scratch is freed: v's latest call has ended
-    v->px_cap = 0;
-    if ((rc = counted_alloc(h, &v->d_buf, &v->buf_bytes, px * 8 + nb * P * 5))) return rc;
-    v->px_cap = px;
-  }
+  const size_t P = (size_t)h->cfg.model_h * h->cfg.model_w, nb = (size_t)max_frames(h);
+  int rc = video_reserve(v, n, fh, fw);
+  if (rc) return rc;
   if ((rc = v->fence.wait_on(h, s))) return rc;
   uint8_t* d_in = v->d_buf;
   uint8_t* d_out = v->d_buf + v->px_cap * 4;

@@ -3,8 +3,9 @@
 // vss_capi.hip is the engine: planner, slots, graphs, forward, the queued host
 // path.  The feature objects live in units of their own — vss_capi_post.hip
 // (vss_post_state, compositing, vss_post_pool), vss_capi_background.hip
-// (vss_background, matte, layers), vss_capi_video.hip (vss_video) — and see the
-// engine through this header.  Everything here is in vss_engine, a namespace of
+// (vss_background, matte, layers), vss_capi_video.hip (vss_video),
+// vss_capi_streams.hip (the calls over many streams, which use all three) — and
+// see the engine through this header.  Everything here is in vss_engine, a namespace of
 // hidden visibility: none of it enters the library's export table.
 // Slot and vss_handle change layout under -DVSS_TRACE, so the trace library
 // compiles every unit that includes this header with it (Makefile: CAPI_UNITS).
@@ -17,7 +18,9 @@
 #include <atomic>
 #include <condition_variable>
 #include <deque>
+#include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -327,27 +330,53 @@ int counted_alloc(vss_handle* h, T** p, size_t* have, size_t bytes) {
 // recorded after the object's latest call.  A call on another stream waits for
 // it on the device; the host waits for it (quiesce) before a buffer the call
 // may use is freed, reallocated or rewritten.
+//
+// A call over several objects (include/vss_streams.h) records ONE event, its
+// first object's, and the others follow it: an event record costs the device
+// about 4.8 us, eight of them more than the composite itself.
+// So the event sits in a box that outlives its object while another follows it.
+// Following stays correct when the box is recorded again: its owner records
+// only on a stream that waited for its own latest call, so every later record
+// of a box completes after all the earlier ones.
 struct Fence {
-  hipEvent_t event = nullptr;
+  struct Box {
+    hipEvent_t event = nullptr;
+    ~Box() {
+      if (event) (void)hipEventDestroy(event);
+    }
+  };
+  std::shared_ptr<Box> own;     // the event this object records
+  std::shared_ptr<Box> latest;  // the event that covers this object's latest call: own, or the one it follows
   hipStream_t last_stream = nullptr;
   bool used = false;
-  hipError_t create() { return hipEventCreateWithFlags(&event, hipEventDisableTiming); }
+  hipError_t create() {
+    latest = own = std::make_shared<Box>();
+    return hipEventCreateWithFlags(&own->event, hipEventDisableTiming);
+  }
   void destroy() {
-    if (event) (void)hipEventDestroy(event);
+    latest.reset();
+    own.reset();
   }
   int wait_on(vss_handle* h, hipStream_t s) const {
-    if (used && last_stream != s) HIP_TRY(h, hipStreamWaitEvent(s, event, 0));
+    if (used && last_stream != s) HIP_TRY(h, hipStreamWaitEvent(s, latest->event, 0));
     return VSS_OK;
   }
   int record(vss_handle* h, hipStream_t s) {
-    HIP_TRY(h, hipEventRecord(event, s));
+    HIP_TRY(h, hipEventRecord(own->event, s));
+    latest = own;
     last_stream = s;
     used = true;
     return VSS_OK;
   }
+  // this object's latest call is the one `leader` has just recorded
+  void follow(const Fence& leader) {
+    latest = leader.latest;
+    last_stream = leader.last_stream;
+    used = true;
+  }
   int quiesce(vss_handle* h) const {
     HIP_TRY(h, hipSetDevice(h->device));
-    if (used) HIP_TRY(h, hipEventSynchronize(event));
+    if (used) HIP_TRY(h, hipEventSynchronize(latest->event));
     return VSS_OK;
   }
 };
@@ -394,6 +423,8 @@ struct vss_background {
   size_t hblur_bytes = 0;
   int radius = 0;
   uint16_t w[vss::kBlurMaxRadius + 1] = {};  // taps 0 (centre) .. radius
+  uint16_t* d_taps = nullptr;    // w on the device, for the calls over many streams (vss_background_set_blur)
+  size_t taps_bytes = 0;
   int refine_radius = 0;         // the edge-aware matte: 0 = off
   double refine_eps = 0.0;
   uint8_t* d_matte = nullptr;    // its planes for n frames: (abar, bbar), (a_q, b_q), L; grown on demand
@@ -420,9 +451,46 @@ struct vss_background {
   vss_engine::Fence fence;       // recorded after every composite
 };
 
+// the post chain over many streams (vss_post.hip k_post_pool; include/vss_pool.h)
+struct vss_post_pool {
+  vss_handle* h = nullptr;
+  std::mutex mu;                  // calls, resets and setters of one pool are serialised
+  vss_post_config cfg{};
+  int capacity = 0;
+  float* planes = nullptr;        // [capacity][2][P] prevAlpha, double-buffered per stream
+  size_t planes_bytes = 0;
+  vss_engine::PostTables tab;     // one range table for every stream
+  size_t rtab_bytes = 0;
+  std::vector<uint8_t> seen;      // per stream: it has seen a frame (prevAlpha exists)
+  std::vector<uint8_t> cur;       // per stream: the plane that holds its prevAlpha
+  std::vector<uint64_t> stamp;    // per stream: the last call that named it (duplicate ids)
+  uint64_t calls = 0;
+  vss_engine::Fence fence;        // recorded after every call
+};
+
+// NV12 video I/O (vss_video.hip; include/vss_video.h)
+struct vss_video {
+  vss_handle* h = nullptr;
+  std::mutex mu;                 // setters and calls of one object are serialised
+  int std_ = VSS_CSC_BT709_LIMITED;
+  uint8_t* d_buf = nullptr;      // RGBA in | RGBA out (px_cap pixels each) | masks f32 | alpha u8 (max_batch frames)
+  size_t buf_bytes = 0, px_cap = 0;
+  uint8_t* d_nv = nullptr;       // the host call's device planes: Y in | UV in | Y out | UV out
+  size_t nv_bytes = 0;
+  int slot = -1;                 // the handle slot whose executable graph is bound to d_buf (taken by the first call)
+  vss_engine::Fence fence;       // recorded after every call
+};
+
 namespace vss_engine __attribute__((visibility("hidden"))) {
 
 // ---- vss_capi_post.hip ----
+// p->mu held.  What a pooled call may be refused for, before anything is enqueued.
+int pool_check(vss_post_pool* p, const int* ids, int n, const uint8_t* d_frames, int fh, int fw, int fc, size_t rs,
+               size_t fs, int max_n);
+// p->mu held; arguments checked.  ceil(n / kPoolFrames) launches and the ordering event.
+int pool_enqueue(vss_post_pool* p, const int* ids, int n, const uint8_t* d_frames, int fh, int fw, int fc, size_t rs,
+                 size_t fs, const float* d_masks, const vss::FaceFrame* d_faces, float* d_alpha, uint8_t* d_u8,
+                 hipStream_t s);
 // the post chain for n frames on s (the state's stream order is the caller's)
 int post_enqueue(vss_post_state* st, const uint8_t* d_frames, int n, int fh, int fw, int fc, size_t rs, size_t fs,
                  const float* d_masks, float* d_alpha, uint8_t* d_u8, hipStream_t s);
@@ -439,5 +507,39 @@ int comp_to_host(vss_handle* h, int rc, uint8_t* out_rgba, size_t bytes);
 // bg->mu held: the composite over the background for n frames on s
 int bg_enqueue(vss_handle* h, vss_background* bg, const uint8_t* d_frames, int n, int fh, int fw, int fc, size_t rs,
                size_t fs, const uint8_t* d_alpha, uint8_t* d_out, size_t ors, size_t ofs, hipStream_t s);
+
+// One frame per stream, frame t over bgs[t] (include/vss_streams.h).  The
+// distinct objects of a call, locked in address order: two calls that name the
+// same objects in different orders cannot deadlock.  bgs: n non-null pointers.
+struct BgStreamsLock {
+  std::vector<vss_background*> objs;  // distinct, ascending
+  BgStreamsLock(vss_background* const* bgs, int n) : objs(bgs, bgs + n) {
+    std::sort(objs.begin(), objs.end(), std::less<vss_background*>());
+    objs.erase(std::unique(objs.begin(), objs.end()), objs.end());
+    for (vss_background* b : objs) b->mu.lock();
+  }
+  ~BgStreamsLock() {
+    for (auto it = objs.rbegin(); it != objs.rend(); ++it) (*it)->mu.unlock();
+  }
+  BgStreamsLock(const BgStreamsLock&) = delete;
+  BgStreamsLock& operator=(const BgStreamsLock&) = delete;
+};
+// no lock needed: bgs and its n entries are non-null objects of h
+int bg_streams_args(vss_handle* h, vss_background* const* bgs, int n);
+// the objects' mutexes held: what their settings refuse for frames fh x fw, before anything is enqueued
+int bg_streams_check(vss_handle* h, vss_background* const* bgs, int n, int fh, int fw);
+// the objects' mutexes held (lk), bg_streams_check passed: the composites on s, and each object's fence
+int bg_streams_enqueue(vss_handle* h, const BgStreamsLock& lk, vss_background* const* bgs, int n,
+                       const uint8_t* d_frames, int fh, int fw, int fc, size_t rs, size_t fs, const uint8_t* d_alpha,
+                       uint8_t* d_out, size_t ors, size_t ofs, hipStream_t s);
+
+// ---- vss_capi_video.hip ----
+// one NV12 batch's geometry; `what` names the planes in the message
+int check_nv12(vss_handle* h, const char* what, const uint8_t* y, size_t yp, size_t yfs, const uint8_t* uv, size_t up,
+               size_t ufs, int n, int fh, int fw, int max_n);
+vss::Nv12Params nv12_params(int std, const uint8_t* y, size_t yp, size_t yfs, const uint8_t* uv, size_t up, size_t ufs,
+                            const uint8_t* rgba, size_t rs, size_t fs, int fh, int fw);
+// v->mu held: v's scratch holds n frames fh x fw (it is regrown once v's latest call has ended)
+int video_reserve(vss_video* v, int n, int fh, int fw);
 
 }  // namespace vss_engine

@@ -663,6 +663,34 @@ struct BgCompositeParams {
 };
 void launch_bg_composite(const BgCompositeParams& p, int mode, int n, hipStream_t s);
 
+// Backgrounds over many streams (include/vss_streams.h): frame t
+// of a launch is composited over its own background.  The per-frame table
+// travels by value and is indexed by a blockIdx expression, so its loads are
+// scalar and nothing of the caller's arrays is read after the launch.  The flat
+// form (colour, scaled image, baked plate) runs over the frames of `flat`, the
+// blur form and the pooled k_blur_h over those of `blur`: blockIdx.z -> frame.
+constexpr int kBgStreamFrames = 32;  // frames per launch
+struct BgStreamEntry {
+  const uint8_t* image;    // flat form: the scaled image or baked plate; null = the colour
+  uint32_t* hblur;         // blur form: this frame's [fh][fw] slot of its object's horizontal pass
+  const uint32_t* overlay; // blur form with visible layers: the object's plate O; else null
+  const float2* ab;        // refinement on: this frame's [H][W] (abar, bbar) slot; else null
+  const uint16_t* taps;    // blur form: the object's device taps 0 (centre) .. radius
+  uint32_t color;
+  int radius;              // blur form
+};
+struct BgStreamsParams {
+  CompositeParams c;       // frames, alpha and output point at the launch's first frame
+  BgStreamEntry entry[kBgStreamFrames];
+  unsigned flat[kBgStreamFrames / 4], blur[kBgStreamFrames / 4];  // frame indices, one byte each
+};
+__host__ __device__ __forceinline__ int stream_list_at(const unsigned* list, int z) {
+  return (int)((list[z >> 2] >> (8 * (z & 3))) & 255u);
+}
+inline void stream_list_set(unsigned* list, int z, int t) { list[z >> 2] |= (unsigned)t << (8 * (z & 3)); }
+// nflat / nblur frames in the lists (either may be 0: that form is not launched); max_radius over the blur frames
+void launch_bg_streams(const BgStreamsParams& p, int nflat, int nblur, int max_radius, hipStream_t s);
+
 struct BlurHParams {
   const uint8_t* frames;   // [n] frames, row_stride / frame_stride bytes, fc = 3 or 4
   long row_stride, frame_stride;
@@ -765,6 +793,22 @@ struct MatteParams {
   float2* ab;              // [n][H][W] out: (abar, bbar)
 };
 void launch_matte_stage(const MatteParams& p, int n, hipStream_t s);
+
+// The mask-resolution stage over many streams: frame list[z] of the launch with
+// its own radius, eps and plane slot (the three kernels, one launch each).
+struct MatteStreamEntry {
+  float2* ab;
+  int2* q;
+  uint8_t* L;
+  double eps;
+  int radius;
+};
+struct MatteStreamsParams {
+  MatteParams m;           // frames, alpha and geometry (first frame of the launch); radius, eps and planes unused
+  MatteStreamEntry entry[kBgStreamFrames];
+  unsigned list[kBgStreamFrames / 4];
+};
+void launch_matte_streams(const MatteStreamsParams& p, int n, hipStream_t s);
 
 // The frame-resolution alpha plane alone: ab != null the refined alpha, else k_composite's.
 struct MatteAlphaParams {

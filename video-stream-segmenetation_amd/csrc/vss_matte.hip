@@ -34,15 +34,15 @@ __host__ __device__ constexpr int matte_ld(int R) { return matte_side(R) + 1; }
 // pixels of [i - r, i + r] inside [0, n)
 __device__ __forceinline__ int clipped(int i, int r, int n) { return min(i + r, n - 1) - max(i - r, 0) + 1; }
 
-}  // namespace
-
-__global__ __launch_bounds__(256) void k_matte_guide(MatteParams p) {
-  extern __shared__ __align__(16) uint32_t acc[];  // [W] luma sums of this mask row's footprints
-  const int i = blockIdx.x, t = blockIdx.y, tid = threadIdx.x;
+// k_matte_guide's workgroup: mask row i of one frame (`frame`: its bytes, Lp:
+// its guide plane); p gives the geometry.  acc: [W] luma sums of the row's footprints.
+__device__ __forceinline__ void matte_guide_row(const MatteParams& p, const uint8_t* frame, uint8_t* Lp, int i,
+                                                uint32_t* acc) {
+  const int tid = threadIdx.x;
   const int r0 = (int)((long)i * p.fh / p.H), r1 = (int)((long)(i + 1) * p.fh / p.H);
   for (int j = tid; j < p.W; j += 256) acc[j] = 0;
   __syncthreads();
-  const uint8_t* f = p.frames + (long)t * p.frame_stride + (long)r0 * p.row_stride;
+  const uint8_t* f = frame + (long)r0 * p.row_stride;
   // the mask column whose footprint [j*fw/W, (j+1)*fw/W) holds x: the largest j with j*fw/W <= x
   const auto column = [&](int x) { return (int)((((long)x + 1) * p.W - 1) / p.fw); };
   // RGB rows that start on dwords: 4 pixels = 3 dwords per thread and row; the
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void k_matte_guide(MatteParams p) {
     atomicAdd(&acc[column(x)], s);
   }
   __syncthreads();
-  uint8_t* L = p.L + ((long)t * p.H + i) * p.W;
+  uint8_t* L = Lp + (long)i * p.W;
   for (int j = tid; j < p.W; j += 256) {
     const int c0 = (int)((long)j * p.fw / p.W), c1 = (int)((long)(j + 1) * p.fw / p.W);
     const uint32_t cnt = (uint32_t)(r1 - r0) * (uint32_t)(c1 - c0);
@@ -89,29 +89,29 @@ __global__ __launch_bounds__(256) void k_matte_guide(MatteParams p) {
   }
 }
 
-// The radius is a template argument (launch_matte_stage switches over 1 .. 8):
-// the window loops have constant bounds, so the compiler unrolls the rows and
-// keeps their LDS reads in flight instead of waiting for one at a time.
+// k_matte_coeff's workgroup on one frame's planes (Lp, ap: guide and alpha
+// bytes, qp: out).  The radius is a template argument: the window loops have
+// constant bounds, so the compiler unrolls the rows and keeps their LDS reads
+// in flight instead of waiting for one at a time.  tile: side * matte_ld(R) dwords.
 template <int R>
-__global__ __launch_bounds__(256) void k_matte_coeff(MatteParams p) {
+__device__ __forceinline__ void matte_coeff_tile(int H, int W, const uint8_t* Lp, const uint8_t* ap, int2* qp,
+                                                 double eps, uint32_t* tile) {
 #pragma clang fp contract(off)
   constexpr int r = R, side = matte_side(R), kMatteLd = matte_ld(R);
-  __shared__ uint32_t tile[side * kMatteLd];  // L | p << 8, 0 outside the mask
   const int tid = threadIdx.x;
   const int X0 = blockIdx.x * kMatteT, Y0 = blockIdx.y * kMatteT;
-  const long base = (long)blockIdx.z * p.H * p.W;
   for (int k = tid; k < side * side; k += 256) {
     const int ly = k / side, lx = k - ly * side, yy = Y0 - r + ly, xx = X0 - r + lx;
-    uint32_t v = 0;
-    if (yy >= 0 && yy < p.H && xx >= 0 && xx < p.W) {
-      const long o = base + (long)yy * p.W + xx;
-      v = (uint32_t)p.L[o] | ((uint32_t)p.alpha[o] << 8);
+    uint32_t v = 0;  // L | p << 8, 0 outside the mask
+    if (yy >= 0 && yy < H && xx >= 0 && xx < W) {
+      const long o = (long)yy * W + xx;
+      v = (uint32_t)Lp[o] | ((uint32_t)ap[o] << 8);
     }
     tile[ly * kMatteLd + lx] = v;
   }
   __syncthreads();
   const int tx = tid & 15, ty = tid >> 4, j = X0 + tx, i = Y0 + ty;
-  if (i >= p.H || j >= p.W) return;
+  if (i >= H || j >= W) return;
   uint32_t sL = 0, sp = 0, sLp = 0, sLL = 0;  // 289 * 65025 < 2^25
   for (int dy = 0; dy <= 2 * r; ++dy)
 #pragma unroll
@@ -122,31 +122,30 @@ __global__ __launch_bounds__(256) void k_matte_coeff(MatteParams p) {
       sLp += l * a;
       sLL += l * l;
     }
-  const long N = (long)clipped(i, r, p.H) * clipped(j, r, p.W);
+  const long N = (long)clipped(i, r, H) * clipped(j, r, W);
   const long cov = N * (long)sLp - (long)sL * (long)sp;
   const long var = N * (long)sLL - (long)sL * (long)sL;
-  const double a = (double)cov / ((double)var + p.eps * (double)(N * N));
+  const double a = (double)cov / ((double)var + eps * (double)(N * N));
   const double prod = a * (double)sL;
   const double b = ((double)sp - prod) / (double)N;
-  p.q[base + (long)i * p.W + j] = make_int2((int)floor(a * 65536.0 + 0.5), (int)floor(b * 256.0 + 0.5));
+  qp[(long)i * W + j] = make_int2((int)floor(a * 65536.0 + 0.5), (int)floor(b * 256.0 + 0.5));
 }
 
+// k_matte_mean's workgroup on one frame's planes.  tile: side * matte_ld(R) int2, (a_q, b_q), 0 outside the mask.
 template <int R>
-__global__ __launch_bounds__(256) void k_matte_mean(MatteParams p) {
+__device__ __forceinline__ void matte_mean_tile(int H, int W, const int2* qp, float2* abp, int2* tile) {
   constexpr int r = R, side = matte_side(R), kMatteLd = matte_ld(R);
-  __shared__ int2 tile[side * kMatteLd];  // (a_q, b_q), 0 outside the mask
   const int tid = threadIdx.x;
   const int X0 = blockIdx.x * kMatteT, Y0 = blockIdx.y * kMatteT;
-  const long base = (long)blockIdx.z * p.H * p.W;
   for (int k = tid; k < side * side; k += 256) {
     const int ly = k / side, lx = k - ly * side, yy = Y0 - r + ly, xx = X0 - r + lx;
     int2 v = make_int2(0, 0);
-    if (yy >= 0 && yy < p.H && xx >= 0 && xx < p.W) v = p.q[base + (long)yy * p.W + xx];
+    if (yy >= 0 && yy < H && xx >= 0 && xx < W) v = qp[(long)yy * W + xx];
     tile[ly * kMatteLd + lx] = v;
   }
   __syncthreads();
   const int tx = tid & 15, ty = tid >> 4, j = X0 + tx, i = Y0 + ty;
-  if (i >= p.H || j >= p.W) return;
+  if (i >= H || j >= W) return;
   int sa = 0, sb = 0;  // |a_q| <= 2^22, |b_q| <= 2^23: 289 terms fit int32
   for (int dy = 0; dy <= 2 * r; ++dy)
 #pragma unroll
@@ -155,9 +154,73 @@ __global__ __launch_bounds__(256) void k_matte_mean(MatteParams p) {
       sa += v.x;
       sb += v.y;
     }
-  const long N = (long)clipped(i, r, p.H) * clipped(j, r, p.W);
-  p.ab[base + (long)i * p.W + j] =
+  const long N = (long)clipped(i, r, H) * clipped(j, r, W);
+  abp[(long)i * W + j] =
       make_float2((float)((double)sa / (double)(N * 65536)), (float)((double)sb / (double)(N * 256)));
+}
+
+// the pooled forms' per-frame radius: one instantiation of `body` per radius, the branch workgroup-uniform
+#define VSS_MATTE_RADIUS_SWITCH(radius, body) \
+  switch (radius) {                           \
+    case 1: body(1); break;                   \
+    case 2: body(2); break;                   \
+    case 3: body(3); break;                   \
+    case 4: body(4); break;                   \
+    case 5: body(5); break;                   \
+    case 6: body(6); break;                   \
+    case 7: body(7); break;                   \
+    default: body(8); break;                  \
+  }
+
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_matte_guide(MatteParams p) {
+  extern __shared__ __align__(16) uint32_t acc[];
+  const int t = blockIdx.y;
+  matte_guide_row(p, p.frames + (long)t * p.frame_stride, p.L + (long)t * p.H * p.W, blockIdx.x, acc);
+}
+
+template <int R>
+__global__ __launch_bounds__(256) void k_matte_coeff(MatteParams p) {
+  __shared__ uint32_t tile[matte_side(R) * matte_ld(R)];
+  const long base = (long)blockIdx.z * p.H * p.W;
+  matte_coeff_tile<R>(p.H, p.W, p.L + base, p.alpha + base, p.q + base, p.eps, tile);
+}
+
+template <int R>
+__global__ __launch_bounds__(256) void k_matte_mean(MatteParams p) {
+  __shared__ int2 tile[matte_side(R) * matte_ld(R)];
+  const long base = (long)blockIdx.z * p.H * p.W;
+  matte_mean_tile<R>(p.H, p.W, p.q + base, p.ab + base, tile);
+}
+
+// ---- many streams: frame list[z] with its own radius, eps and planes (MatteStreamsParams) ----
+__global__ __launch_bounds__(256) void k_matte_guide_streams(MatteStreamsParams p) {
+  extern __shared__ __align__(16) uint32_t acc[];
+  const int t = stream_list_at(p.list, blockIdx.y);
+  matte_guide_row(p.m, p.m.frames + (long)t * p.m.frame_stride, p.entry[t].L, blockIdx.x, acc);
+}
+
+__global__ __launch_bounds__(256) void k_matte_coeff_streams(MatteStreamsParams p) {
+  __shared__ uint32_t tile[matte_side(kMatteMaxRadius) * matte_ld(kMatteMaxRadius)];
+  const int t = stream_list_at(p.list, blockIdx.z), H = p.m.H, W = p.m.W;
+  const uint8_t* Lp = p.entry[t].L;
+  const uint8_t* ap = p.m.alpha + (long)t * H * W;
+  int2* qp = p.entry[t].q;
+  const double eps = p.entry[t].eps;
+#define VSS_BODY(R) matte_coeff_tile<R>(H, W, Lp, ap, qp, eps, tile)
+  VSS_MATTE_RADIUS_SWITCH(p.entry[t].radius, VSS_BODY)
+#undef VSS_BODY
+}
+
+__global__ __launch_bounds__(256) void k_matte_mean_streams(MatteStreamsParams p) {
+  __shared__ int2 tile[matte_side(kMatteMaxRadius) * matte_ld(kMatteMaxRadius)];
+  const int t = stream_list_at(p.list, blockIdx.z), H = p.m.H, W = p.m.W;
+  const int2* qp = p.entry[t].q;
+  float2* abp = p.entry[t].ab;
+#define VSS_BODY(R) matte_mean_tile<R>(H, W, qp, abp, tile)
+  VSS_MATTE_RADIUS_SWITCH(p.entry[t].radius, VSS_BODY)
+#undef VSS_BODY
 }
 
 // k_composite's thread shape: 4 consecutive pixels of one row, one 4-B store.
@@ -223,6 +286,14 @@ void launch_matte_stage(const MatteParams& p, int n, hipStream_t s) {
     case 7: launch_matte_fit<7>(p, n, s); break;
     default: launch_matte_fit<8>(p, n, s); break;
   }
+}
+
+void launch_matte_streams(const MatteStreamsParams& p, int n, hipStream_t s) {
+  const MatteParams& m = p.m;
+  const dim3 grid((m.W + kMatteT - 1) / kMatteT, (m.H + kMatteT - 1) / kMatteT, n);
+  hipLaunchKernelGGL(k_matte_guide_streams, dim3(m.H, n), dim3(256), (size_t)m.W * 4, s, p);
+  hipLaunchKernelGGL(k_matte_coeff_streams, grid, dim3(256), 0, s, p);
+  hipLaunchKernelGGL(k_matte_mean_streams, grid, dim3(256), 0, s, p);
 }
 
 void launch_matte_alpha(const MatteAlphaParams& p, int n, hipStream_t s) {

@@ -82,6 +82,7 @@
 #include <map>
 #include <mutex>
 #include <deque>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -1862,6 +1863,250 @@ napi_value VideoProcess(napi_env env, napi_callback_info info) {
   return promise;
 }
 
+// ---- many streams to finished frames (include/vss_streams.h) ----------------------
+// One frame per stream, frame t of stream ids[t] over backgrounds[t]:
+//   segmentBackgroundStreams(handle, pool, ids, backgrounds, frames, n, height, width, channels, rowStride)
+//     -> Promise<Uint8Array> RGBA [n][height][width][4]
+//   videoProcessStreams(handle, video, pool, ids, backgrounds, y, uv, n, height, width)
+//     -> Promise<{y, uv}> tightly packed NV12
+struct StreamsWork {
+  napi_async_work work = nullptr;
+  napi_deferred deferred = nullptr;
+  napi_ref in_ref[2] = {nullptr, nullptr}, out_ref[2] = {nullptr, nullptr};
+  Handle* hd = nullptr;     // pending counted until StreamsComplete; main thread only
+  vss_handle* h = nullptr;  // what the worker thread uses
+  vss_video* v = nullptr;   // null: the RGB(A) call
+  vss_post_pool* pool = nullptr;
+  std::vector<int> ids;
+  std::vector<vss_background*> bgs;
+  const uint8_t* in[2] = {nullptr, nullptr};  // frames | y, uv
+  uint8_t* out[2] = {nullptr, nullptr};       // rgba   | y, uv
+  int n = 0, height = 0, width = 0, channels = 0;
+  size_t row_stride = 0;
+  int rc = 0;
+  std::string err;
+};
+
+void StreamsExecute(napi_env, void* data) {  // libuv worker thread: no JS calls here
+  StreamsWork* w = static_cast<StreamsWork*>(data);
+  if (w->v)
+    w->rc = vss_video_process_streams(w->v, w->pool, w->ids.data(), w->bgs.data(), w->in[0], w->in[1], w->n, w->height,
+                                      w->width, w->out[0], w->out[1]);
+  else
+    w->rc = vss_segment_background_streams(w->h, w->pool, w->ids.data(), w->bgs.data(), w->in[0], w->n, w->height,
+                                           w->width, w->channels, w->row_stride, w->out[0]);
+  if (w->rc != VSS_OK) w->err = vss_last_error(w->h);
+}
+
+void StreamsComplete(napi_env env, napi_status, void* data) {
+  StreamsWork* w = static_cast<StreamsWork*>(data);
+  const size_t px = (size_t)w->n * w->height * w->width;
+  if (w->rc == VSS_OK && w->v) {
+    napi_value aby = nullptr, abuv = nullptr, ay, auv, o;
+    napi_get_reference_value(env, w->out_ref[0], &aby);
+    napi_get_reference_value(env, w->out_ref[1], &abuv);
+    napi_create_typedarray(env, napi_uint8_array, px, aby, 0, &ay);
+    napi_create_typedarray(env, napi_uint8_array, px / 2, abuv, 0, &auv);
+    napi_create_object(env, &o);
+    napi_set_named_property(env, o, "y", ay);
+    napi_set_named_property(env, o, "uv", auv);
+    napi_resolve_deferred(env, w->deferred, o);
+  } else if (w->rc == VSS_OK) {
+    napi_value ab = nullptr, arr;
+    napi_get_reference_value(env, w->out_ref[0], &ab);
+    napi_create_typedarray(env, napi_uint8_array, px * 4, ab, 0, &arr);
+    napi_resolve_deferred(env, w->deferred, arr);
+  } else {
+    napi_value msg, code, e;
+    const std::string m = std::string(w->v ? "vss_video_process_streams" : "vss_segment_background_streams") +
+                          " failed (" + std::to_string(w->rc) + "): " + w->err;
+    napi_create_string_utf8(env, m.c_str(), m.size(), &msg);
+    napi_create_string_utf8(env, std::to_string(w->rc).c_str(), NAPI_AUTO_LENGTH, &code);
+    napi_create_error(env, code, msg, &e);
+    napi_reject_deferred(env, w->deferred, e);
+  }
+  for (int k = 0; k < 2; ++k) {
+    if (w->in_ref[k]) napi_delete_reference(env, w->in_ref[k]);
+    if (w->out_ref[k]) napi_delete_reference(env, w->out_ref[k]);
+  }
+  napi_delete_async_work(env, w->work);
+  Handle* hd = w->hd;
+  delete w;
+  work_done(hd);
+}
+
+// ids: an array of n stream ids; backgrounds: an array of n backgrounds of hd (false: a JS exception is pending)
+bool get_streams(napi_env env, napi_value ids_v, napi_value bgs_v, Handle* hd, StreamsWork* w) {
+  bool a = false, b = false;
+  uint32_t ni = 0, nb = 0;
+  if (napi_is_array(env, ids_v, &a) != napi_ok || !a || napi_get_array_length(env, ids_v, &ni) != napi_ok ||
+      napi_is_array(env, bgs_v, &b) != napi_ok || !b || napi_get_array_length(env, bgs_v, &nb) != napi_ok) {
+    napi_throw_type_error(env, nullptr, "ids and backgrounds must be arrays, one entry per frame");
+    return false;
+  }
+  w->ids.resize(ni);
+  for (uint32_t k = 0; k < ni; ++k) {
+    napi_value e;
+    napi_get_element(env, ids_v, k, &e);
+    if (napi_get_value_int32(env, e, &w->ids[k]) != napi_ok) {
+      napi_throw_type_error(env, nullptr, "ids must be an array of stream ids, one per frame");
+      return false;
+    }
+  }
+  w->bgs.resize(nb);
+  for (uint32_t k = 0; k < nb; ++k) {
+    napi_value e;
+    napi_get_element(env, bgs_v, k, &e);
+    Bg* bgp = get_bg(env, e);
+    if (!bgp) return false;
+    if (bgp->hd != hd) {
+      napi_throw_error(env, nullptr, "background belongs to another handle");
+      return false;
+    }
+    w->bgs[k] = bgp->bg;
+  }
+  return true;
+}
+
+// a Uint8Array / Uint8ClampedArray argument of at least `need` bytes (null: a JS exception is pending)
+const uint8_t* get_bytes(napi_env env, napi_value v, size_t need, const char* what) {
+  bool is_ta = false;
+  napi_is_typedarray(env, v, &is_ta);
+  napi_typedarray_type tt = napi_int8_array;
+  size_t len = 0, off = 0;
+  void* data = nullptr;
+  napi_value buf;
+  if (is_ta && napi_get_typedarray_info(env, v, &tt, &len, &data, &buf, &off) != napi_ok) is_ta = false;
+  if (!is_ta || (tt != napi_uint8_array && tt != napi_uint8_clamped_array)) {
+    napi_throw_type_error(env, nullptr, (std::string(what) + " must be a Uint8Array or Uint8ClampedArray").c_str());
+    return nullptr;
+  }
+  if (len < need || !data) {
+    napi_throw_range_error(env, nullptr, (std::string(what) + " holds fewer bytes than the frames need").c_str());
+    return nullptr;
+  }
+  return static_cast<const uint8_t*>(data);
+}
+
+// w is complete but for its handle: the worker thread may start at once, so hd and h are set before the work is queued
+napi_value queue_streams(napi_env env, Handle* hd, StreamsWork* w, const char* what) {
+  napi_value promise = nullptr, name;
+  w->hd = hd;
+  w->h = hd->h;
+  bool ok = napi_create_promise(env, &w->deferred, &promise) == napi_ok &&
+            napi_create_string_utf8(env, what, NAPI_AUTO_LENGTH, &name) == napi_ok &&
+            napi_create_async_work(env, nullptr, name, StreamsExecute, StreamsComplete, w, &w->work) == napi_ok;
+  if (ok) {
+    ++hd->pending;  // counted until StreamsComplete
+    ok = napi_queue_async_work(env, w->work) == napi_ok;
+    if (!ok) --hd->pending;
+  }
+  if (!ok) {  // nothing runs: the work item and what it holds are released here
+    if (w->work) napi_delete_async_work(env, w->work);
+    for (int k = 0; k < 2; ++k) {
+      if (w->in_ref[k]) napi_delete_reference(env, w->in_ref[k]);
+      if (w->out_ref[k]) napi_delete_reference(env, w->out_ref[k]);
+    }
+    delete w;
+    napi_throw_error(env, nullptr, (std::string(what) + ": the call could not be queued").c_str());
+    return nullptr;
+  }
+  return promise;
+}
+
+napi_value SegmentBackgroundStreams(napi_env env, napi_callback_info info) {
+  size_t argc = 10;
+  napi_value a[10];
+  NAPI_OK(env, napi_get_cb_info(env, info, &argc, a, nullptr, nullptr));
+  if (argc < 10) {
+    napi_throw_type_error(env, nullptr, "segmentBackgroundStreams(handle, pool, ids, backgrounds, frames, n, height, "
+                                        "width, channels, rowStride)");
+    return nullptr;
+  }
+  Handle* hd = get_handle(env, a[0]);
+  if (!hd) return nullptr;
+  Pool* pl = get_pool(env, a[1]);
+  if (!pl) return nullptr;
+  if (pl->hd != hd) {
+    napi_throw_error(env, nullptr, "post pool belongs to another handle");
+    return nullptr;
+  }
+  std::unique_ptr<StreamsWork> w(new StreamsWork());
+  if (!get_streams(env, a[2], a[3], hd, w.get())) return nullptr;
+  int rs = 0;
+  napi_get_value_int32(env, a[5], &w->n);
+  napi_get_value_int32(env, a[6], &w->height);
+  napi_get_value_int32(env, a[7], &w->width);
+  napi_get_value_int32(env, a[8], &w->channels);
+  napi_get_value_int32(env, a[9], &rs);
+  if (w->n < 1 || w->height < 1 || w->width < 1 || rs < 1 || w->ids.size() != (size_t)w->n ||
+      w->bgs.size() != (size_t)w->n) {
+    napi_throw_range_error(env, nullptr, "n >= 1 frames of at least 1 x 1, one stream id and one background per frame");
+    return nullptr;
+  }
+  w->row_stride = (size_t)rs;
+  w->pool = pl->p;
+  w->in[0] = get_bytes(env, a[4], (size_t)w->n * w->height * w->row_stride, "frames");
+  if (!w->in[0]) return nullptr;
+  napi_value ab;
+  void* out = nullptr;
+  NAPI_OK(env, napi_create_arraybuffer(env, (size_t)w->n * w->height * w->width * 4, &out, &ab));
+  w->out[0] = static_cast<uint8_t*>(out);
+  napi_create_reference(env, a[4], 1, &w->in_ref[0]);  // keep the frames alive until done
+  napi_create_reference(env, ab, 1, &w->out_ref[0]);
+  return queue_streams(env, hd, w.release(), "vss_segment_background_streams");
+}
+
+napi_value VideoProcessStreams(napi_env env, napi_callback_info info) {
+  size_t argc = 10;
+  napi_value a[10];
+  NAPI_OK(env, napi_get_cb_info(env, info, &argc, a, nullptr, nullptr));
+  if (argc < 10) {
+    napi_throw_type_error(env, nullptr,
+                          "videoProcessStreams(handle, video, pool, ids, backgrounds, y, uv, n, height, width)");
+    return nullptr;
+  }
+  Handle* hd = get_handle(env, a[0]);
+  if (!hd) return nullptr;
+  Vid* vd = get_vid(env, a[1]);
+  if (!vd) return nullptr;
+  Pool* pl = get_pool(env, a[2]);
+  if (!pl) return nullptr;
+  if (vd->hd != hd || pl->hd != hd) {
+    napi_throw_error(env, nullptr, "video or post pool belongs to another handle");
+    return nullptr;
+  }
+  std::unique_ptr<StreamsWork> w(new StreamsWork());
+  if (!get_streams(env, a[3], a[4], hd, w.get())) return nullptr;
+  napi_get_value_int32(env, a[7], &w->n);
+  napi_get_value_int32(env, a[8], &w->height);
+  napi_get_value_int32(env, a[9], &w->width);
+  if (w->n < 1 || w->height < 2 || w->width < 2 || w->ids.size() != (size_t)w->n || w->bgs.size() != (size_t)w->n) {
+    napi_throw_range_error(env, nullptr,
+                           "n >= 1 NV12 frames of at least 2 x 2, one stream id and one background per frame");
+    return nullptr;
+  }
+  const size_t yb = (size_t)w->n * w->height * w->width, ub = (size_t)w->n * (w->height / 2) * w->width;
+  w->v = vd->v;
+  w->pool = pl->p;
+  w->in[0] = get_bytes(env, a[5], yb, "y");
+  if (!w->in[0]) return nullptr;
+  w->in[1] = get_bytes(env, a[6], ub, "uv");
+  if (!w->in[1]) return nullptr;
+  napi_value aby, abuv;
+  void* oy = nullptr;
+  void* ouv = nullptr;
+  NAPI_OK(env, napi_create_arraybuffer(env, yb, &oy, &aby));
+  NAPI_OK(env, napi_create_arraybuffer(env, yb / 2, &ouv, &abuv));
+  w->out[0] = static_cast<uint8_t*>(oy);
+  w->out[1] = static_cast<uint8_t*>(ouv);
+  napi_create_reference(env, a[5], 1, &w->in_ref[0]);  // keep the planes alive until done
+  napi_create_reference(env, a[6], 1, &w->in_ref[1]);
+  napi_create_reference(env, aby, 1, &w->out_ref[0]);
+  napi_create_reference(env, abuv, 1, &w->out_ref[1]);
+  return queue_streams(env, hd, w.release(), "vss_video_process_streams");
+}
+
 // ---- ONNX sessions (include/vso.h) -------------------------------------------
 struct OrtSess {
   vso_session* s = nullptr;
@@ -2398,6 +2643,8 @@ napi_value Init(napi_env env, napi_value exports) {
       {"videoSetStandard", nullptr, VideoSetStandard, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"videoDestroy", nullptr, VideoDestroy, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"videoProcess", nullptr, VideoProcess, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"segmentBackgroundStreams", nullptr, SegmentBackgroundStreams, nullptr, nullptr, nullptr, napi_default, nullptr},
+      {"videoProcessStreams", nullptr, VideoProcessStreams, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ortCreate", nullptr, OrtCreate, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ortInfo", nullptr, OrtInfo, nullptr, nullptr, nullptr, napi_default, nullptr},
       {"ortRun", nullptr, OrtRun, nullptr, nullptr, nullptr, napi_default, nullptr},
