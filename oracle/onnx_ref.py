@@ -1,6 +1,6 @@
 """ONNX reference (TEST INFRASTRUCTURE ONLY — never imported by the product):
 a hand-written protobuf reader/writer for ONNX ModelProto and a numpy
-evaluator of the operator subset the GPU session (csrc/vso_model.hip)
+evaluator of the operator subset the GPU session (csrc/vso_plan.hip)
 implements.  It is the checker for the GPU ONNX sessions, the way
 oracle/vss_oracle.c is the checker for the segmentation path.
 
@@ -710,7 +710,7 @@ def run(model: Model, feeds: dict, want=None, conv_operands=None) -> dict:
                 sizes = ins[3] if len(ins) > 3 and ins[3] is not None else None
                 y = _resize(x, scales, sizes, a)
         elif op == "InstanceNormalization":
-            # (what the session refuses at creation: vso_model.hip, plan_node / plan_norm)
+            # (what the session refuses at creation: vso_plan.hip, the plan_<op> functions / plan_norm)
             if nd["inputs"][1] not in const or nd["inputs"][2] not in const:
                 raise ValueError("InstanceNormalization: constant scale/B only")
             if x.ndim < 3:

@@ -1,6 +1,6 @@
 """What the InstanceNorm kernels and the IBNorm fusion compute, restated in
 numpy float32 (test infrastructure; vso_kernels.hip: k_norm_plane,
-k_norm_stats, k_norm_apply, merge_stats, k_conv_thin; vso_model.hip:
+k_norm_stats, k_norm_apply, merge_stats, k_conv_thin; vso_plan.hip:
 plan_norm, find_ibnorm, plan_conv's BatchNorm fold), for the inorm / ibn
 families of the operator matrix (tests/op_cases.py):
 

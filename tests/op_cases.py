@@ -339,7 +339,7 @@ case("Softmax_opset11_axis-1", "softmax11", "Softmax", [x(2, 3, 5)], {"axis": -1
 
 # ---------------------------------------------------------------------------
 # Conv: every kernel form launch_conv / conv_kernel_name (vso_kernels.hip) and
-# plan_conv (vso_model.hip) choose but k_conv_tile in f32 (tests/test_gpu_conv_tile_matrix.py),
+# plan_conv (vso_plan.hip) choose but k_conv_tile in f32 (tests/test_gpu_conv_tile_matrix.py),
 # one Conv per case (or a depthwise -> 1x1 pair, or a Conv with its epilogue),
 # the name of its launch asserted.  Batch 2, planes 9x11 (99 outputs: a pixel
 # tile tail on every tile size) and channel counts off the 16 / 64 tiles unless
@@ -523,7 +523,7 @@ conv("attr_none", (2, 3, *P9), (5, 3, 3, 3), {}, [small(False, 8, False)])
 
 # ---------------------------------------------------------------------------
 # The MobileNetV2 inverted residual, one block per case: Conv 1x1 -> Clip -> Conv 3x3 depthwise -> Clip ->
-# Conv 1x1 [-> Add], fused by try_plan_ir (vso_model.hip) into one launch of k_ir (f32 sessions) or k_ir_b16
+# Conv 1x1 [-> Add], fused by try_plan_ir (vso_plan.hip) into one launch of k_ir (f32 sessions) or k_ir_b16
 # (bf16 / f16 sessions), plus k_ir_reduce where the hidden channels are split into slices (vso_ir.hip).
 # ir_entry() picks the instance by (ceil(CIN / 16) in f32 | ceil(CIN / 32) in 16 bits, ceil(COUT / 16), stride).
 #
@@ -702,7 +702,7 @@ ir("miss_pool_pad_residual", 16, 24, EVEN, GEN, GEN, s=2,
    tail=[POOL, then("Pad", ci(0, 0, 0, 0, 0, 8, 0, 0)), node("Add", [("node", 4), PREV])])
 
 # ---------------------------------------------------------------------------
-# InstanceNormalization alone (family inorm).  plan_norm (vso_model.hip) picks by the plane's element count:
+# InstanceNormalization alone (family inorm).  plan_norm (vso_plan.hip) picks by the plane's element count:
 # k_norm_plane<16, 256> up to 4096, <48, 256> up to 12288, <36, 1024> up to 36864 — one workgroup per plane, two
 # passes over registers — and above that k_norm_stats ((mean, M2, count) per piece of 4096 elements) +
 # k_norm_apply (the pieces merged in order, Chan et al.).  Each moves float4s where the plane is a multiple of
@@ -751,7 +751,7 @@ inorm("rows1", (1, 1, 3, 5))
 inorm("rows257", (1, 257, 3, 5))
 
 # ---------------------------------------------------------------------------
-# MODNet's IBNorm (family ibn), one pattern per case, fused by find_ibnorm (vso_model.hip):
+# MODNet's IBNorm (family ibn), one pattern per case, fused by find_ibnorm (vso_plan.hip):
 #   c = Conv(x); Concat(BatchNorm(Slice(c, 0:nb)), InstanceNorm(Slice(c, nb:M)), axis 1) [-> Relu] [-> consumer]
 # The conv writes the concatenation (the BatchNorm folded into its first nb channels, the Relu on them in its
 # epilogue), the norm runs in place on channels nb .. M - 1 (c0 = nb, ctot = M).  Before a thin 1x1 head

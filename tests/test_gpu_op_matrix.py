@@ -39,7 +39,7 @@ form, k_norm_stats + k_norm_apply up to 129 pieces, k_conv_thin behind a
 deferred norm — and here under VSO_NORM_PLANE=0 and VSO_THIN=0 in child
 processes and in bf16 and f16 sessions (the ibn16 cases against the oracle
 that rounds the conv's operands).  Figures and the value-only breaks of
-vso_kernels.hip / vso_model.hip that only these tests catch:
+vso_kernels.hip / vso_plan.hip that only these tests catch:
 profiles/NOTES.md, "Norm operator matrix".
 """
 import math

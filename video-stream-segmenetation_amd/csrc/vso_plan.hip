@@ -1,0 +1,1778 @@
+// vso_plan.hip — the ONNX sessions' planner: a parsed Graph (vso_onnx.h) and
+// the input shapes -> the session's launch list over preallocated HBM tensors
+// (vso_session.h), at create.  Host code; the kernels are vso_kernels.hip,
+// vso_conv.hip and vso_ir.hip.
+//
+// Planning rules:
+//  * every shape is static once input 0's shape is fixed; nodes whose inputs
+//    are all constants (the exporters' Shape/Gather/Concat/... arithmetic,
+//    weight reshapes) are evaluated on the host (vso_fold.cpp);
+//  * Reshape / Flatten / Squeeze / Unsqueeze / Identity alias their input;
+//  * Conv absorbs a following BatchNormalization (weights folded), residual
+//    Add and activation (Relu, Clip, PRelu, LeakyRelu, Sigmoid, Tanh) into
+//    one launch when each intermediate has exactly one consumer;
+//  * the fusions found before planning (find_*): IBNorm, strided residuals,
+//    Concat inputs written in place, 2x upsamples computed by their consumer;
+//  * every other runtime node is one launch, by the plan_<op> of its operator.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <map>
+#include <set>
+
+#include "vso_kernels.h"
+#include "vso_session.h"
+
+using namespace vso;
+using namespace vso_onnx;
+
+namespace {
+
+struct Planner {
+  using Ins = std::vector<Value*>;  // a node's inputs (null: an absent optional one)
+
+  vso_session* s;
+  Graph& g;
+  std::map<std::string, Value> vals;
+  std::map<std::string, int> consumers;
+  std::set<size_t> done;  // node indices absorbed by a fused launch
+  std::map<const void*, float*> dev_consts;
+  std::string err;
+
+  // ---- fusions found before planning (find_*; run) -------------------------
+  // Add operands computed inside the consuming convolution's epilogue instead
+  // of by their own launches: MaxPool(2x2, s2) -> [Pad of the channel axis] -> Add
+  struct ResFuse {
+    std::string src;  // the MaxPool's input, or the Pad's input
+    int mode;         // Epilogue::res_mode
+  };
+  std::map<std::string, ResFuse> res_fuse;  // by the Add operand's name (find_residual_fusions)
+  // MODNet's IBNorm (Conv2dIBNormRelu; the authors' src/models/modnet.py):
+  //   c = Conv(x); Concat(BN(Slice(c, 0:nb)), InstanceNorm(Slice(c, nb:M)), axis 1) [-> Relu]
+  // with every intermediate used once.  The conv writes the concatenation
+  // directly: the BatchNorm folded into its first nb output channels' weights,
+  // the Relu applied to those channels in its epilogue; the InstanceNorm then
+  // normalises channels nb .. M-1 in place (+ Relu).  Seven launches -> three.
+  struct IbnFuse {
+    int nb;
+    size_t bn, inorm, concat;
+    int relu;  // node index or -1
+    std::string out;
+  };
+  std::map<size_t, IbnFuse> ibn;  // conv node -> its IBNorm (find_ibnorm)
+  // Concat (axis 1) inputs whose producer — a convolution or a Resize — may
+  // write them straight into the concatenation (find_concat_direct).
+  // MODNet: 10 of its 13 Concat copies (the k_copy_rows launches).
+  std::set<std::string> cat_direct;
+  // 2x linear Resizes that may be computed inside their consumer convolution
+  // (k_conv_tile_up), by graph structure (find_up_fusions)
+  std::set<std::string> up_cand;
+
+  // ---- work left by one node to a later one, by value name -----------------
+  // Each entry is set by the producer's plan and cleared by the consumer that
+  // takes it, or by the flush_* that launches it after all; run() fails if one
+  // is left over.
+  // pending_dw: a depthwise conv's output computed in its 1x1 consumer (input,
+  //   producer).  Set: plan_conv (defer_depthwise).  Cleared: plan_conv of
+  //   that consumer (feeds_pointwise guarantees it takes it).
+  std::map<std::string, std::pair<const float*, DwPre>> pending_dw;
+  // norm_pending: an InstanceNorm's apply step left to a k_conv_thin consumer.
+  //   Set: plan_norm (defer).  Cleared: plan_conv's thin branch, or flush_norm.
+  std::map<std::string, std::shared_ptr<NormParams>> norm_pending;
+  // up_pending: a planned 2x Resize not yet launched.  Set: plan_resize.
+  //   Cleared: plan_conv_dense (computed while staging), or flush_up.
+  std::map<std::string, std::shared_ptr<ResizeParams>> up_pending;
+  // cat_up: per Concat output, the channel ranges of its inputs still in
+  //   up_pending.  Set: plan_concat.  Read by plan_conv_dense and flush_input
+  //   (stale ranges are harmless: flush_up of a launched Resize does nothing).
+  struct UpRange { std::string name; int c0, c1; };
+  std::map<std::string, std::vector<UpRange>> cat_up;
+  // cat_patch: per cat_direct value, patches re-pointing its producing
+  //   launches' output into the concatenation (base: the input's first channel
+  //   of image 0; ctot: the concatenation's channels).  Set: retarget_on_concat
+  //   and plan_norm.  Applied by plan_concat, which then copies only the other
+  //   inputs.
+  std::map<std::string, std::vector<std::function<void(float*, int)>>> cat_patch;
+  // cat_tail: a Concat's last input (whole 32-channel chunks on) left in its
+  //   own tensor instead of copied in: its sole consumer, a convolution on
+  //   k_conv_tile, reads those chunks from there (ConvTileParams::x2).  Set:
+  //   plan_concat.  Cleared: plan_conv_dense, or flush_tail, which runs the
+  //   copy.  MODNet: 3 copies of 8 x 3 / 32 x H x W planes (52 us of
+  //   k_copy_rows at batch 8).
+  struct CatTail {
+    const float* x;
+    int c0, C;
+    std::function<bool()> copy;
+  };
+  std::map<std::string, CatTail> cat_tail;
+
+  // launch a pending InstanceNorm apply step / fused Resize (by output name)
+  // after all: its consumer cannot take it
+  void flush_norm(const std::string& name) {
+    auto nt = norm_pending.find(name);
+    if (nt == norm_pending.end()) return;
+    add("vso::k_norm_apply(vso::NormParams)", nt->second, launch_norm_apply);
+    norm_pending.erase(nt);
+  }
+  void flush_up(const std::string& name) {
+    flush_norm(name);
+    auto it = up_pending.find(name);
+    if (it == up_pending.end()) return;
+    add(resize_kernel_name(*it->second), it->second, launch_resize);
+    up_pending.erase(it);
+  }
+  bool flush_tail(const std::string& name) {
+    auto t = cat_tail.find(name);
+    if (t == cat_tail.end()) return true;
+    std::function<bool()> copy = std::move(t->second.copy);
+    cat_tail.erase(t);
+    return copy();
+  }
+  // a consumer that computes no upsample itself: its input's pending Resize and,
+  // when the input is an in-place Concat, every pending upsampled input of it
+  void flush_input(const std::string& name) {
+    flush_tail(name);
+    flush_up(name);
+    auto cu = cat_up.find(name);
+    if (cu != cat_up.end())
+      for (const UpRange& u : cu->second) flush_up(u.name);
+  }
+
+  // ---- fusion discovery: what fills the sets and maps above ----------------
+  bool slice_range(const Node& nd, int64_t C, int64_t* b, int64_t* e) {
+    if (nd.op != "Slice" || nd.in.size() < 3) return false;
+    auto cint = [&](size_t k, std::vector<int64_t>* out) {
+      if (k >= nd.in.size() || nd.in[k].empty()) return false;
+      Value* v = val(nd.in[k]);
+      if (!v || !v->is_const || !v->c.is_int) return false;
+      *out = v->c.i;
+      return true;
+    };
+    std::vector<int64_t> st, en, ax{0}, sp{1};
+    if (!cint(1, &st) || !cint(2, &en) || st.size() != 1 || en.size() != 1) return false;
+    if (nd.in.size() > 3 && !nd.in[3].empty() && !cint(3, &ax)) return false;
+    if (nd.in.size() > 4 && !nd.in[4].empty() && !cint(4, &sp)) return false;
+    if (ax.size() != 1 || ax[0] != 1 || sp.size() != 1 || sp[0] != 1) return false;
+    *b = std::clamp<int64_t>(st[0] < 0 ? st[0] + C : st[0], 0, C);
+    *e = std::clamp<int64_t>(en[0] < 0 ? en[0] + C : en[0], 0, C);
+    return true;
+  }
+
+  void find_ibnorm() {
+    for (size_t k = 0; k < g.nodes.size(); ++k) {
+      const Node& cat = g.nodes[k];
+      if (cat.op != "Concat" || cat.in.size() != 2 || cat.ai("axis", 0) != 1) continue;
+      const int pbn = producer(cat.in[0]), pin = producer(cat.in[1]);
+      if (pbn < 0 || pin < 0 || g.nodes[pbn].op != "BatchNormalization" || g.nodes[pin].op != "InstanceNormalization")
+        continue;
+      if (sole_consumer(cat.in[0], (size_t)pbn) != (int)k || sole_consumer(cat.in[1], (size_t)pin) != (int)k) continue;
+      const Node &bn = g.nodes[pbn], &inn = g.nodes[pin];
+      bool consts = bn.in.size() == 5 && inn.in.size() == 3;
+      for (size_t q = 1; consts && q < bn.in.size(); ++q) consts = val(bn.in[q]) && val(bn.in[q])->is_const;
+      for (size_t q = 1; consts && q < inn.in.size(); ++q) consts = val(inn.in[q]) && val(inn.in[q])->is_const;
+      if (!consts) continue;
+      const int sa = producer(bn.in[0]), sb = producer(inn.in[0]);
+      if (sa < 0 || sb < 0 || sole_consumer(bn.in[0], (size_t)sa) != pbn || sole_consumer(inn.in[0], (size_t)sb) != pin)
+        continue;
+      const Node &la = g.nodes[sa], &lb = g.nodes[sb];
+      if (la.op != "Slice" || lb.op != "Slice" || la.in[0] != lb.in[0]) continue;
+      const std::string& c = la.in[0];
+      const int pc = producer(c);
+      if (pc < 0 || g.nodes[pc].op != "Conv" || consumers[c] != 2) continue;
+      bool is_out = false;
+      for (const IO& o : g.outputs) is_out = is_out || o.name == c;
+      Value* wv = val(g.nodes[pc].in[1]);
+      if (is_out || !wv || !wv->is_const || wv->c.dims.size() != 4) continue;
+      const int64_t M = wv->c.dims[0];
+      int64_t b0, e0, b1, e1;
+      if (!slice_range(la, M, &b0, &e0) || !slice_range(lb, M, &b1, &e1)) continue;
+      if (b0 != 0 || e0 != b1 || e1 != M || e0 <= 0 || e0 >= M) continue;
+      if (val(bn.in[1])->c.numel() != e0 || val(inn.in[1])->c.numel() != M - e0) continue;
+      IbnFuse f{(int)e0, (size_t)pbn, (size_t)pin, k, -1, cat.out[0]};
+      const int r = sole_consumer(cat.out[0], k);
+      if (r >= 0 && g.nodes[r].op == "Relu") {
+        f.relu = r;
+        f.out = g.nodes[r].out[0];
+      }
+      for (size_t q : {(size_t)sa, (size_t)sb, (size_t)pbn, (size_t)pin, k}) done.insert(q);
+      if (f.relu >= 0) done.insert((size_t)f.relu);
+      ibn[(size_t)pc] = f;
+    }
+  }
+
+  bool channel_pad_only(const Node& nd) {
+    if (nd.as("mode", "constant") != "constant" || nd.in.size() < 2) return false;
+    Value* pv = val(nd.in[1]);
+    if (!pv || !pv->is_const || !pv->c.is_int || pv->c.i.size() != 8) return false;
+    if (nd.in.size() > 2 && !nd.in[2].empty()) {
+      Value* cv = val(nd.in[2]);
+      if (!cv || !cv->is_const || (!cv->c.f.empty() && cv->c.f[0] != 0.f)) return false;
+    }
+    if (nd.in.size() > 3 && !nd.in[3].empty()) return false;  // axes
+    const std::vector<int64_t>& q = pv->c.i;
+    for (int d = 0; d < 8; ++d)
+      if (d != 5 && q[d] != 0) return false;
+    return q[5] >= 0;
+  }
+
+  static bool pool_2x2(const Node& nd) {
+    const std::vector<int64_t> k = nd.ais("kernel_shape"), st = nd.ais("strides"), pd = nd.ais("pads"),
+                               dl = nd.ais("dilations");
+    if (k != std::vector<int64_t>{2, 2} || st != std::vector<int64_t>{2, 2}) return false;
+    for (int64_t v : pd) if (v != 0) return false;
+    for (int64_t v : dl) if (v != 1) return false;
+    return nd.ai("ceil_mode", 0) == 0 && nd.as("auto_pad", "NOTSET") == "NOTSET";
+  }
+
+  // MaxPool(2x2, stride 2, unpadded, floor) -> [Pad: zeros appended on the
+  // channel axis only] -> Add(x, Conv(...)) where the Conv's output feeds only
+  // that Add (so plan_conv absorbs the Add): the Pad / MaxPool launches are
+  // dropped and the conv's epilogue reads the pool input (BlazeFace's and the
+  // landmark net's strided residual path: 5 + 8 launches).
+  void find_residual_fusions() {
+    for (size_t a = 0; a < g.nodes.size(); ++a) {
+      const Node& ad = g.nodes[a];
+      if (ad.op != "Add" || ad.in.size() != 2 || ad.in[0] == ad.in[1]) continue;
+      for (int side = 0; side < 2; ++side) {
+        const std::string& cv = ad.in[side];
+        const std::string& o = ad.in[1 - side];
+        const int pc = producer(cv);
+        if (pc < 0 || g.nodes[pc].op != "Conv" || sole_consumer(cv, (size_t)pc) != (int)a) continue;
+        int pn = producer(o);
+        if (pn < 0 || sole_consumer(o, (size_t)pn) != (int)a) continue;
+        int mode = 0, pad_node = -1;
+        std::string cur = o;
+        if (g.nodes[pn].op == "Pad" && channel_pad_only(g.nodes[pn])) {
+          pad_node = pn;
+          cur = g.nodes[pn].in[0];
+          mode = 1;
+          pn = producer(cur);
+          if (pn >= 0 && sole_consumer(cur, (size_t)pn) != pad_node) pn = -1;
+        }
+        int pool_node = -1;
+        if (pn >= 0 && g.nodes[pn].op == "MaxPool" && pool_2x2(g.nodes[pn])) {
+          pool_node = pn;
+          cur = g.nodes[pn].in[0];
+          mode = 2;
+        }
+        if (mode == 0) continue;
+        if (pad_node >= 0) done.insert((size_t)pad_node);
+        if (pool_node >= 0) done.insert((size_t)pool_node);
+        res_fuse[o] = ResFuse{cur, mode};
+        break;
+      }
+    }
+  }
+
+  // Inputs of the Concats that may be written in place: used by that Concat
+  // only, once, and neither a graph input / output nor a constant (whether the
+  // producer can, and the Concat is on axis 1 of 4-D tensors, is decided when
+  // they are planned: see cat_patch)
+  void find_concat_direct() {
+    std::set<std::string> fixed;
+    for (const IO& o : g.inputs) fixed.insert(o.name);
+    for (const IO& o : g.outputs) fixed.insert(o.name);
+    for (auto& kv : g.inits) fixed.insert(kv.first);
+    for (size_t k = 0; k < g.nodes.size(); ++k) {
+      const Node& cat = g.nodes[k];
+      if (cat.op != "Concat" || done.count(k)) continue;
+      for (const std::string& i : cat.in)
+        if (!i.empty() && !fixed.count(i) && consumers[i] == 1) cat_direct.insert(i);
+    }
+  }
+
+  // Resizes whose output feeds one convolution's input, directly or as an
+  // input of a Concat (written in place) that feeds one: planned as pending
+  // (plan_resize checks the kind: 2x linear half-pixel)
+  void find_up_fusions() {
+    for (size_t k = 0; k < g.nodes.size(); ++k) {
+      const Node& rs = g.nodes[k];
+      if (rs.op != "Resize" || done.count(k)) continue;
+      const std::string& o = rs.out[0];
+      const int c = sole_consumer(o, k);
+      if (c < 0) continue;
+      const Node& cn = g.nodes[c];
+      if (cn.op == "Conv" && cn.in[0] == o) {
+        up_cand.insert(o);
+      } else if (cn.op == "Concat" && cat_direct.count(o) && cn.ai("axis", 0) == 1) {
+        const int cc = sole_consumer(cn.out[0], (size_t)c);
+        if (cc >= 0 && g.nodes[cc].op == "Conv" && g.nodes[cc].in[0] == cn.out[0]) up_cand.insert(o);
+      }
+    }
+  }
+
+  // ---- the A/B knobs that change a plan ------------------------------------
+  // VSO_CAT_TAIL=0: every Concat input not written in place is copied
+  static bool cat_tail_enabled() { static const bool on = env_on("VSO_CAT_TAIL"); return on; }
+  // VSO_GEMM_ACT=0: a Gemm / MatMul's activation as its own launch
+  static bool gemm_act_enabled() { static const bool on = env_on("VSO_GEMM_ACT"); return on; }
+  // VSO_IR=0: the inverted residual blocks as three launches each
+  static bool ir_enabled() { static const bool on = env_on("VSO_IR"); return on; }
+  // the bf16x3 form in bf16 / f16 sessions (VSO_IR_B16=0: the f32 form there too)
+  static bool ir_b16_enabled() { static const bool on = env_on("VSO_IR_B16"); return on; }
+  // VSO_UP_FUSE=0 keeps every Resize a launch of its own
+  static bool up_fuse_enabled() { static const bool on = env_on("VSO_UP_FUSE"); return on; }
+  // VSO_NORM_PLANE=0: small InstanceNorm planes keep the stats + apply pair
+  static bool norm_plane_enabled() { static const bool on = env_on("VSO_NORM_PLANE"); return on; }
+  // VSO_THIN=0: 1x1 heads of <= kThinMaxM outputs stay on the MFMA kernels
+  static bool thin_enabled() { static const bool on = env_on("VSO_THIN"); return on; }
+
+  // ---- allocations, values, launches ---------------------------------------
+  bool fail(const std::string& m) {
+    err = m;
+    return false;
+  }
+
+  template <class T>
+  bool dalloc(T** p, size_t bytes) {
+    void* q = nullptr;
+    const size_t n = std::max<size_t>(bytes, 16);
+    if (hipMalloc(&q, n) != hipSuccess) return fail("hipMalloc failed");
+    s->allocs.push_back(q);
+    s->ranges.push_back(DevRange{(uintptr_t)q, (uintptr_t)q + n, false});
+    *p = static_cast<T*>(q);
+    return true;
+  }
+  // a constant's allocation (weights, biases, tables): kernels only read it
+  void mark_ro(const void* q) {
+    for (DevRange& r : s->ranges)
+      if ((uintptr_t)q >= r.lo && (uintptr_t)q < r.hi) r.ro = true;
+  }
+  // a read-only device copy of `bytes` host bytes
+  const void* upload_bytes(const void* src, size_t bytes, const char* what = "constant upload failed") {
+    unsigned char* d = nullptr;
+    if (!dalloc(&d, bytes)) return nullptr;
+    if (bytes && hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) != hipSuccess) {
+      fail(what);
+      return nullptr;
+    }
+    mark_ro(d);
+    return d;
+  }
+  const float* upload_vec(const std::vector<float>& v) {
+    return static_cast<const float*>(upload_bytes(v.data(), v.size() * 4));
+  }
+  // device copy of a constant's float data (cached per Const)
+  const float* upload(const Const& c) {
+    auto it = dev_consts.find(&c);
+    if (it != dev_consts.end()) return it->second;
+    const float* d = upload_vec(c.f);
+    if (d) dev_consts[&c] = const_cast<float*>(d);
+    return d;
+  }
+
+  int new_buf(int64_t elems) {
+    float* d = nullptr;
+    if (!dalloc(&d, (size_t)std::max<int64_t>(elems, 1) * 4)) return -1;
+    s->bufs.push_back(d);
+    s->buf_elems.push_back(elems);
+    return (int)s->bufs.size() - 1;
+  }
+
+  Value* val(const std::string& n) {
+    if (n.empty()) return nullptr;
+    auto it = vals.find(n);
+    return it == vals.end() ? nullptr : &it->second;
+  }
+  float* dptr(const Value& v) { return s->bufs[v.buf]; }
+  // a runtime pointer for an operand: its buffer, or its uploaded constant
+  const float* operand(Value& v) { return v.is_const ? upload(v.c) : s->bufs[v.buf]; }
+
+  bool set_runtime(const std::string& name, const std::vector<int64_t>& shape, int alias = -1) {
+    Value v;
+    v.shape = shape;
+    v.buf = alias >= 0 ? alias : new_buf(v.numel());
+    if (v.buf < 0) return false;
+    vals[name] = v;
+    return true;
+  }
+  // a new runtime tensor: its device pointer, or null (err set)
+  float* make_out(const std::string& name, const std::vector<int64_t>& shape) {
+    return set_runtime(name, shape) ? dptr(vals[name]) : nullptr;
+  }
+  void set_const(const std::string& name, const Const& c) {
+    Value v;
+    v.is_const = true;
+    v.c = c;
+    v.shape = c.dims;
+    vals[name] = v;
+  }
+
+  template <class T>
+  static Region reg(const std::shared_ptr<T>& sp) {
+    return Region{std::static_pointer_cast<const void>(sp), sp.get(), sizeof(T)};
+  }
+  // One launch, `launch(*pp, stream)`.  The parameter block is registered as
+  // the launch's region: schedule_lanes finds the launch's dependencies by
+  // scanning those bytes for device pointers.
+  template <class P, class F>
+  void add(const char* name, const std::shared_ptr<P>& pp, F launch) {
+    s->launches.push_back(Launch{name, [pp, launch](hipStream_t st) { launch(*pp, st); }, {reg(pp)}});
+  }
+  // ... of a parameter block the launch list keeps (returned for later patches)
+  template <class P, class F>
+  std::shared_ptr<P> emit(const char* name, const P& p, F launch) {
+    auto pp = std::make_shared<P>(p);
+    add(name, pp, launch);
+    return pp;
+  }
+  // `pp` (ConvParams, ResizeParams: `channels` of Ho x Wo) writes `out`; when
+  // `out` is a Concat input written in place, plan_concat re-points it there
+  template <class P>
+  void retarget_on_concat(const std::string& out, const std::shared_ptr<P>& pp, int channels) {
+    if (!cat_direct.count(out)) return;
+    cat_patch[out].push_back([pp, channels](float* base, int ctot) {
+      pp->y = base;
+      pp->y_nx = (long)(ctot - channels) * pp->Ho * pp->Wo;
+    });
+  }
+
+  // ---- graph queries -------------------------------------------------------
+  static bool is_act(const std::string& op) {
+    return op == "Relu" || op == "Clip" || op == "PRelu" || op == "LeakyRelu" || op == "Sigmoid" || op == "Tanh";
+  }
+
+  // the single node consuming `name`, if exactly one and `name` is no graph output
+  int sole_consumer(const std::string& name, size_t after) {
+    if (consumers[name] != 1) return -1;
+    for (const IO& o : g.outputs)
+      if (o.name == name) return -1;
+    for (size_t k = after + 1; k < g.nodes.size(); ++k)
+      for (const std::string& i : g.nodes[k].in)
+        if (i == name) return (int)k;
+    return -1;
+  }
+
+  int producer(const std::string& name) const {
+    for (size_t k = 0; k < g.nodes.size(); ++k)
+      for (const std::string& o : g.nodes[k].out)
+        if (o == name) return (int)k;
+    return -1;
+  }
+
+  // activation parameters of an activation node (constants only)
+  bool act_of(const Node& nd, Epilogue* ep, int channels) {
+    if (nd.op == "Relu") ep->act = ACT_RELU;
+    else if (nd.op == "Sigmoid") ep->act = ACT_SIGMOID;
+    else if (nd.op == "Tanh") ep->act = ACT_TANH;
+    else if (nd.op == "LeakyRelu") { ep->act = ACT_LEAKY; ep->a0 = nd.af("alpha", 0.01f); }
+    else if (nd.op == "Clip") {
+      float lo = nd.af("min", -INFINITY), hi = nd.af("max", INFINITY);
+      if (nd.in.size() > 1 && !nd.in[1].empty()) { Value* v = val(nd.in[1]); if (!v || !v->is_const) return false; lo = v->c.f[0]; }
+      if (nd.in.size() > 2 && !nd.in[2].empty()) { Value* v = val(nd.in[2]); if (!v || !v->is_const) return false; hi = v->c.f[0]; }
+      ep->act = ACT_CLIP; ep->a0 = lo; ep->a1 = hi;
+    } else if (nd.op == "PRelu") {
+      Value* sl = val(nd.in[1]);
+      if (!sl || !sl->is_const) return false;
+      const int64_t n = sl->c.numel();
+      if (n != 1 && n != channels) return false;
+      // the slope must be per channel under ONNX broadcasting against NCHW:
+      // [C,1,1], [1,C,1,1] or one value ([C] aligns with W: left to k_binary)
+      const std::vector<int64_t>& sd = sl->c.dims;
+      if (n != 1) {
+        const size_t r = sd.size();
+        if (r < 3 || r > 4 || sd[r - 3] != n) return false;
+      }
+      ep->act = ACT_PRELU;
+      ep->slope = upload(sl->c);
+      ep->slope_stride = n == 1 ? 0 : 1;
+    } else return false;
+    return true;
+  }
+
+  // auto_pad SAME_UPPER / SAME_LOWER of a convolution or pool (ConvParams,
+  // PoolParams: H, W, kernel, strides, dilations set): pads = {top, left,
+  // bottom, right}; false: `ap` is neither
+  template <class P>
+  static bool same_pads(const std::string& ap, const P& p, int pads[4]) {
+    if (ap != "SAME_UPPER" && ap != "SAME_LOWER") return false;
+    const int in[2] = {p.H, p.W}, k[2] = {p.kh, p.kw}, st[2] = {p.sh, p.sw}, dl[2] = {p.dh, p.dw};
+    for (int d = 0; d < 2; ++d) {
+      const int o = (in[d] + st[d] - 1) / st[d];
+      const int tot = std::max((o - 1) * st[d] + dl[d] * (k[d] - 1) + 1 - in[d], 0);
+      pads[d] = ap == "SAME_UPPER" ? tot / 2 : tot - tot / 2;
+      pads[d + 2] = tot - pads[d];
+    }
+    return true;
+  }
+
+  // BatchNormalization `bn` (constant parameters): y = (x - mean) * a + B per
+  // channel, a = scale / sqrt(var + epsilon)
+  struct BnConsts {
+    const Const &scale, &B, &mean, &var;
+    double eps;
+    double a(int c) const { return scale.f[c] / std::sqrt((double)var.f[c] + eps); }
+  };
+  BnConsts bn_consts(const Node& bn) {
+    return {val(bn.in[1])->c, val(bn.in[2])->c, val(bn.in[3])->c, val(bn.in[4])->c, bn.af("epsilon", 1e-5f)};
+  }
+  // ... folded into a convolution's output channels [m0, m1): `per` weights each
+  void fold_bn(std::vector<float>& wf, std::vector<float>& bias, int64_t per, int m0, int m1, const Node& bn) {
+    const BnConsts b = bn_consts(bn);
+    for (int m = m0; m < m1; ++m) {
+      const double a = b.a(m);
+      for (int64_t k = 0; k < per; ++k) wf[m * per + k] = (float)(wf[m * per + k] * a);
+      bias[m] = (float)((bias[m] - b.mean.f[m]) * a + b.B.f[m]);
+    }
+  }
+
+  // ---- the inverted residual block (vso_ir.hip) ----------------------------
+  // A constant conv's geometry: 1x1 / stride 1 / unpadded / undilated, or the
+  // 3x3 depthwise of a MobileNetV2 block (pads 1, stride 1 or 2)
+  bool conv_attrs(const Node& c, int k, int* stride, int* group) {
+    if (c.as("auto_pad", "NOTSET") != "NOTSET") return false;
+    const std::vector<int64_t> st = c.ais("strides"), dl = c.ais("dilations"), pd = c.ais("pads");
+    for (int64_t v : dl) if (v != 1) return false;
+    const int sh = st.size() > 0 ? (int)st[0] : 1, sw = st.size() > 1 ? (int)st[1] : 1;
+    if (sh != sw) return false;
+    for (int64_t v : pd) if (v != (k == 3 ? 1 : 0)) return false;
+    if (k == 3 && pd.size() != 4) return false;
+    *stride = sh;
+    *group = (int)c.ai("group", 1);
+    return true;
+  }
+
+  // The MobileNetV2 inverted residual starting at Conv ni: 1x1 expand -> Clip
+  // -> 3x3 depthwise (stride 1 / 2) -> Clip -> 1x1 project [-> Add of the
+  // block's input], each value consumed by the next node only
+  struct IrBlock {
+    int k1, k2, k3, k4, k5;  // the Clip, depthwise, Clip, project and Add nodes (k5: when res)
+    Value *x, *w1, *wd, *w2;
+    std::vector<float> b1, bd, b2;
+    Epilogue c1{}, c2{};
+    int sd;  // the depthwise stride
+    bool res;
+    std::string out;
+  };
+  bool match_ir(size_t ni, IrBlock* b) {
+    const Node& ex = g.nodes[ni];
+    if (ibn.count(ni) || ex.in.size() < 2) return false;
+    // an input that is a depthwise output left to its 1x1 consumer (pending_dw:
+    // no launch writes it) is computed by plan_conv's fused form, not here
+    if (pending_dw.count(ex.in[0])) return false;
+    Value *x = b->x = val(ex.in[0]), *w1 = b->w1 = val(ex.in[1]);
+    if (!x || x->is_const || x->shape.size() != 4 || !w1 || !w1->is_const || w1->c.dims.size() != 4) return false;
+    int s1, g1;
+    if (!conv_attrs(ex, 1, &s1, &g1) || s1 != 1 || g1 != 1 || w1->c.dims[2] != 1 || w1->c.dims[3] != 1) return false;
+    const int CIN = (int)x->shape[1], HID = (int)w1->c.dims[0];
+    if (w1->c.dims[1] != CIN) return false;
+    const int k1 = b->k1 = sole_consumer(ex.out[0], ni);
+    if (k1 < 0 || g.nodes[k1].op != "Clip") return false;
+    const int k2 = b->k2 = sole_consumer(g.nodes[k1].out[0], k1);
+    if (k2 < 0 || g.nodes[k2].op != "Conv" || g.nodes[k2].in[0] != g.nodes[k1].out[0]) return false;
+    const int k3 = b->k3 = sole_consumer(g.nodes[k2].out[0], k2);
+    if (k3 < 0 || g.nodes[k3].op != "Clip") return false;
+    const int k4 = b->k4 = sole_consumer(g.nodes[k3].out[0], k3);
+    if (k4 < 0 || g.nodes[k4].op != "Conv" || g.nodes[k4].in[0] != g.nodes[k3].out[0]) return false;
+    const Node &dw = g.nodes[k2], &pj = g.nodes[k4];
+    Value *wd = b->wd = val(dw.in[1]), *w2 = b->w2 = val(pj.in[1]);
+    int gd, s2, g2;
+    if (!wd || !wd->is_const || wd->c.dims.size() != 4 || !conv_attrs(dw, 3, &b->sd, &gd) ||
+        (b->sd != 1 && b->sd != 2) || gd != HID || wd->c.dims[0] != HID || wd->c.dims[1] != 1 ||
+        wd->c.dims[2] != 3 || wd->c.dims[3] != 3)
+      return false;
+    if (!w2 || !w2->is_const || w2->c.dims.size() != 4 || !conv_attrs(pj, 1, &s2, &g2) || s2 != 1 || g2 != 1 ||
+        w2->c.dims[1] != HID || w2->c.dims[2] != 1 || w2->c.dims[3] != 1)
+      return false;
+    const int COUT = (int)w2->c.dims[0];
+    auto bias_of = [&](const Node& c, int m, std::vector<float>* bv) {
+      bv->assign(m, 0.f);
+      if (c.in.size() < 3 || c.in[2].empty()) return true;
+      Value* v = val(c.in[2]);
+      if (!v || !v->is_const || v->c.numel() != m) return false;
+      *bv = v->c.f;
+      return true;
+    };
+    if (!bias_of(ex, HID, &b->b1) || !bias_of(dw, HID, &b->bd) || !bias_of(pj, COUT, &b->b2)) return false;
+    if (!act_of(g.nodes[k1], &b->c1, HID) || !act_of(g.nodes[k3], &b->c2, HID)) return false;
+    // the residual: an Add of the project's output and the block's input
+    b->out = pj.out[0];
+    b->k5 = sole_consumer(b->out, k4);
+    b->res = false;
+    if (b->k5 >= 0 && g.nodes[b->k5].op == "Add") {
+      const Node& ad = g.nodes[b->k5];
+      const std::string& other = ad.in[0] == b->out ? ad.in[1] : ad.in[0];
+      // a strided residual find_residual_fusions left to the project's epilogue (its MaxPool / Pad
+      // nodes are done, nothing writes `other`): the generic plan, whose plan_conv reads the pool's input
+      if (res_fuse.count(other)) return false;
+      if (other == ex.in[0] && ad.in[0] != ad.in[1] && b->sd == 1 && CIN == COUT) {
+        b->res = true;
+        b->out = ad.out[0];
+      }
+    }
+    return !cat_direct.count(b->out) && !cat_direct.count(pj.out[0]);  // (written into a Concat: the generic path)
+  }
+
+  // ... as one k_ir launch.  1: planned (the other nodes marked done), 0: not
+  // this pattern / no kernel for its shape, -1: an error.
+  int try_plan_ir(size_t ni) {
+    IrBlock b;
+    if (!ir_enabled() || !match_ir(ni, &b)) return 0;
+    const std::vector<int64_t>& xs = b.x->shape;
+    const int N = (int)xs[0], CIN = (int)xs[1], H = (int)xs[2], W = (int)xs[3];
+    const int HID = (int)b.w1->c.dims[0], COUT = (int)b.w2->c.dims[0], sd = b.sd;
+    const int Ho = (H + 2 - 3) / sd + 1, Wo = (W + 2 - 3) / sd + 1;
+    IrParams p{};
+    p.N = N; p.CIN = CIN; p.H = H; p.W = W; p.HID = HID; p.COUT = COUT; p.Ho = Ho; p.Wo = Wo;
+    p.stride = sd; p.res = b.res ? 1 : 0;
+    p.lo1 = b.c1.a0; p.hi1 = b.c1.a1; p.lo2 = b.c2.a0; p.hi2 = b.c2.a1;
+    p.b16 = s->conv_precision != PREC_F32 && ir_b16_enabled() ? 1 : 0;
+    ir_tiles(Ho, Wo, &p.tiles_x, &p.tiles);
+    // slices of the hidden channels: about two workgroups per CU (512; VSO_IR_WGS:
+    // 256 measured 1.445 against 1.424 ms on MODNet batch 8 bf16, profiles/r05f)
+    // over the tiles and slices, whole 16-channel chunks per slice (b16: whole
+    // chunk pairs, and the slice's weights within the LDS budget)
+    static const long wgs = std::max(1L, env_int("VSO_IR_WGS", 512));
+    static const int probe = (int)env_int("VSO_IR_PROBE", 0);
+    p.probe = probe;
+    static const bool wave_form = env_off("VSO_IR_WAVE");
+    p.wv = p.b16 && wave_form && CIN <= 64 ? 1 : 0;
+    const int nch = HID / 16;
+    // b16: about 6 chunks per slice, at least 256 workgroups (VSO_IR_CPS; 0:
+    // the VSO_IR_WGS target alone) — MODNet batch 8 bf16 1407.5 us of kernel
+    // time against 1411 (4), 1415 (8), 1421 (the 512-workgroup target),
+    // profiles/r05i
+    static const int cps_target = (int)env_int("VSO_IR_CPS", 6);
+    if (p.b16 && (HID % 16 != 0 || !ir_slab_plan(&p, wgs, cps_target))) return 0;
+    if (!ir_supported(p)) return 0;
+    if (!p.b16) {
+      const long wg0 = (long)N * p.tiles;
+      int ks = (int)std::min<long>(nch, std::max<long>(1, (wgs + wg0 / 2) / wg0));
+      p.cps = (nch + ks - 1) / ks;
+      p.ks = (nch + p.cps - 1) / p.cps;
+    }
+    p.pstr = ir_pstr(sd);
+    // weights: the expand / project as stored ([out][in]), the depthwise tap-major
+    const std::vector<float>&w1 = b.w1->c.f, &w2 = b.w2->c.f;
+    std::vector<float> wdt((size_t)9 * HID);
+    for (int h = 0; h < HID; ++h)
+      for (int k = 0; k < 9; ++k) wdt[(size_t)k * HID + h] = b.wd->c.f[(size_t)h * 9 + k];
+    const std::string& in0 = g.nodes[ni].in[0];
+    flush_input(in0);
+    flush_norm(in0);
+    p.x = dptr(*b.x);
+    p.w1 = upload_vec(w1);
+    p.b1 = upload_vec(b.b1);
+    p.wdw = upload_vec(wdt);
+    p.bdw = upload_vec(b.bd);
+    p.w2 = upload_vec(w2);
+    p.b2 = upload_vec(b.b2);
+    if (!p.w1 || !p.b1 || !p.wdw || !p.bdw || !p.w2 || !p.b2) return -1;
+    if (p.b16) {
+      std::vector<unsigned char> slab;
+      ir_slab_build(p, w1.data(), b.b1.data(), wdt.data(), b.bd.data(), w2.data(), &slab);
+      p.slab = static_cast<const unsigned char*>(upload_bytes(slab.data(), slab.size()));
+      if (!p.slab) return -1;
+    }
+    if (p.ks > 1 && !dalloc(&p.part, (size_t)p.ks * N * COUT * Ho * Wo * 4)) return -1;
+    if (!(p.y = make_out(b.out, {N, COUT, Ho, Wo}))) return -1;
+    auto pp = emit(ir_kernel_name(p), p, launch_ir);
+    if (p.ks > 1) add("void vso::k_ir_reduce(vso::IrParams)", pp, launch_ir_reduce);
+    for (int k : {b.k1, b.k2, b.k3, b.k4}) done.insert((size_t)k);
+    if (b.res) done.insert((size_t)b.k5);
+    s->ir_blocks++;
+    return 1;
+  }
+
+  // ---- Conv ----------------------------------------------------------------
+  // A Conv node with what its launch absorbs
+  struct ConvPlan {
+    ConvParams p{};
+    std::vector<float> wf, bias;  // weights and bias, BatchNormalization folded in
+    bool has_bias = false;
+    std::vector<int64_t> oshape;
+    std::string out;              // the value the launch writes: the last absorbed node's output
+    size_t last;                  // that node
+    const IbnFuse* ib = nullptr;  // the IBNorm this Conv heads
+  };
+
+  // geometry and attribute checks: c->p's sizes, c->wf, c->bias
+  bool conv_geometry(const Node& nd, ConvPlan* c) {
+    Value* x = val(nd.in[0]);
+    Value* w = val(nd.in[1]);
+    Value* b = nd.in.size() > 2 ? val(nd.in[2]) : nullptr;
+    if (!w || !w->is_const) return fail("Conv '" + nd.name + "': weights must be constant");
+    if (x->shape.size() != 4 || w->c.dims.size() != 4) return fail("Conv '" + nd.name + "': 2D only");
+    ConvParams& p = c->p;
+    p.N = (int)x->shape[0]; p.C = (int)x->shape[1]; p.H = (int)x->shape[2]; p.W = (int)x->shape[3];
+    p.M = (int)w->c.dims[0]; p.Cg = (int)w->c.dims[1]; p.kh = (int)w->c.dims[2]; p.kw = (int)w->c.dims[3];
+    p.G = (int)nd.ai("group", 1);
+    if (p.G < 1 || p.C != p.Cg * p.G || p.M % p.G) return fail("Conv '" + nd.name + "': channel/group mismatch");
+    p.Mg = p.M / p.G;
+    std::vector<int64_t> st = nd.ais("strides"), dl = nd.ais("dilations"), pd = nd.ais("pads");
+    // (absent, or one value per axis / per side: a shorter list would leave an axis at its default unnoticed)
+    if (!st.empty() && st.size() != 2) return fail("Conv '" + nd.name + "': strides must have 2 values");
+    if (!dl.empty() && dl.size() != 2) return fail("Conv '" + nd.name + "': dilations must have 2 values");
+    if (!pd.empty() && pd.size() != 4) return fail("Conv '" + nd.name + "': pads must have 4 values");
+    p.sh = st.empty() ? 1 : (int)st[0]; p.sw = st.empty() ? 1 : (int)st[1];
+    p.dh = dl.empty() ? 1 : (int)dl[0]; p.dw = dl.empty() ? 1 : (int)dl[1];
+    if (p.sh < 1 || p.sw < 1 || p.dh < 1 || p.dw < 1)
+      return fail("Conv '" + nd.name + "': strides and dilations must be positive");
+    int pads[4] = {0, 0, 0, 0};  // top, left, bottom, right
+    for (size_t k = 0; k < pd.size(); ++k) pads[k] = (int)pd[k];
+    const std::string ap = nd.as("auto_pad", "NOTSET");
+    if (!same_pads(ap, p, pads) && ap == "VALID") pads[0] = pads[1] = pads[2] = pads[3] = 0;
+    p.pt = pads[0]; p.pl = pads[1];
+    p.Ho = (p.H + pads[0] + pads[2] - p.dh * (p.kh - 1) - 1) / p.sh + 1;
+    p.Wo = (p.W + pads[1] + pads[3] - p.dw * (p.kw - 1) - 1) / p.sw + 1;
+    if (p.Ho < 1 || p.Wo < 1) return fail("Conv '" + nd.name + "': empty output");
+    c->oshape = {p.N, p.M, p.Ho, p.Wo};
+    c->wf = w->c.f;
+    c->bias.assign(p.M, 0.f);
+    if (b) {
+      if (!b->is_const || b->c.numel() != p.M) return fail("Conv '" + nd.name + "': bias must be constant [M]");
+      c->bias = b->c.f;
+      c->has_bias = true;
+    }
+    return true;
+  }
+
+  // `node` (absorbed) now ends the launch
+  void absorb(ConvPlan* c, int node, int* next) {
+    done.insert((size_t)node);
+    c->out = g.nodes[node].out[0];
+    c->last = (size_t)node;
+    *next = sole_consumer(c->out, c->last);
+  }
+
+  // epilogue absorption: BatchNormalization -> residual Add -> activation (an
+  // IBNorm: its BatchNorm half and Relu), while each value has one consumer
+  bool conv_absorb(size_t ni, ConvPlan* c) {
+    ConvParams& p = c->p;
+    Epilogue& ep = p.ep;
+    c->out = g.nodes[ni].out[0];
+    c->last = ni;
+    int c1 = sole_consumer(c->out, c->last);
+    const int64_t per = (int64_t)p.Cg * p.kh * p.kw;
+    const auto ib = ibn.find(ni);
+    if (ib != ibn.end()) {  // BN folded into channels < nb, Relu there; the InstanceNorm after the launch
+      const IbnFuse& f = ib->second;
+      c->ib = &f;
+      fold_bn(c->wf, c->bias, per, 0, f.nb, g.nodes[f.bn]);
+      c->has_bias = true;
+      if (f.relu >= 0) {
+        ep.act = ACT_RELU;
+        ep.act_c_end = f.nb;
+      }
+      c->out = f.out;
+      c1 = -1;
+    }
+    if (c1 >= 0 && g.nodes[c1].op == "BatchNormalization") {
+      const Node& bn = g.nodes[c1];
+      Value *sc = val(bn.in[1]), *bb = val(bn.in[2]), *mu = val(bn.in[3]), *vr = val(bn.in[4]);
+      if (sc && bb && mu && vr && sc->is_const && bb->is_const && mu->is_const && vr->is_const &&
+          sc->c.numel() == p.M) {
+        fold_bn(c->wf, c->bias, per, 0, p.M, bn);
+        c->has_bias = true;
+        absorb(c, c1, &c1);
+      }
+    }
+    if (c1 >= 0 && g.nodes[c1].op == "Add") {
+      const Node& ad = g.nodes[c1];
+      const std::string& other = ad.in[0] == c->out ? ad.in[1] : ad.in[0];
+      auto rf = res_fuse.find(other);
+      Value* o = val(rf != res_fuse.end() ? rf->second.src : other);
+      if (rf != res_fuse.end()) {  // the strided residual: the MaxPool / Pad computed here
+        const int mode = rf->second.mode;
+        if (!o || o->is_const || o->shape.size() != 4 || o->shape[0] != p.N || o->shape[1] > p.M ||
+            (mode == 1 && (o->shape[2] != p.Ho || o->shape[3] != p.Wo)) ||
+            (mode == 2 && (o->shape[2] / 2 != p.Ho || o->shape[3] / 2 != p.Wo)))
+          return fail("Conv '" + g.nodes[ni].name + "': internal: fused residual shape");
+        ep.res = dptr(*o);
+        ep.res_mode = mode;
+        ep.res_c = (int)o->shape[1];
+        ep.res_h = (int)o->shape[2];
+        ep.res_w = (int)o->shape[3];
+        ep.out_c = p.M;
+        ep.out_hw = p.Ho * p.Wo;
+        ep.out_w = p.Wo;
+        absorb(c, c1, &c1);
+      } else if (o && !o->is_const && o->shape == c->oshape && ad.in[0] != ad.in[1]) {
+        ep.res = dptr(*o);
+        absorb(c, c1, &c1);
+      }
+    }
+    if (c1 >= 0 && is_act(g.nodes[c1].op) && act_of(g.nodes[c1], &ep, p.M)) absorb(c, c1, &c1);
+    return err.empty();
+  }
+
+  // `out`'s sole consumer is a Conv k_conv_thin runs (thin_conv_fits, C <= kThinMaxC)
+  static constexpr int kThinMaxC = 256;
+  bool feeds_thin(const std::string& out, size_t last) {
+    const int c = sole_consumer(out, last);
+    if (c < 0) return false;
+    const Node& cv = g.nodes[c];
+    if (cv.op != "Conv" || cv.in.empty() || cv.in[0] != out || cv.in.size() < 2) return false;
+    Value* w = val(cv.in[1]);
+    if (!w || !w->is_const || w->c.dims.size() != 4) return false;
+    const std::vector<int64_t>& d = w->c.dims;
+    if (d[0] > kThinMaxM || d[1] > kThinMaxC || d[2] != 1 || d[3] != 1 || cv.ai("group", 1) != 1) return false;
+    for (int64_t v : cv.ais("strides")) if (v != 1) return false;
+    for (int64_t v : cv.ais("pads")) if (v != 0) return false;
+    const std::string ap = cv.as("auto_pad", "NOTSET");
+    return ap == "NOTSET" || ap == "VALID";
+  }
+
+  // output channels of the sole Conv consuming `out` (its weights' dims[0]), or 0
+  int consumer_out_channels(const std::string& out, size_t last) {
+    const int c = sole_consumer(out, last);
+    if (c < 0 || g.nodes[c].op != "Conv" || g.nodes[c].in.size() < 2) return 0;
+    Value* w = val(g.nodes[c].in[1]);
+    return (w && w->is_const && !w->c.dims.empty()) ? (int)w->c.dims[0] : 0;
+  }
+
+  // The output of a depthwise conv feeds exactly one Conv, 1x1 / stride 1 /
+  // unpadded / ungrouped, on all its channels: the pair runs as k_conv_dwpw.
+  bool feeds_pointwise(const std::string& out, size_t last, int channels) {
+    const int c = sole_consumer(out, last);
+    if (c < 0 || g.nodes[c].op != "Conv" || g.nodes[c].in.empty() || g.nodes[c].in[0] != out) return false;
+    const Node& pw = g.nodes[c];
+    Value* w = val(pw.in[1]);
+    if (!w || !w->is_const || w->c.dims.size() != 4 || w->c.dims[1] != channels || w->c.dims[2] != 1 ||
+        w->c.dims[3] != 1 || pw.ai("group", 1) != 1 || pw.as("auto_pad", "NOTSET") != "NOTSET")
+      return false;
+    for (int64_t v : pw.ais("strides")) if (v != 1) return false;
+    for (int64_t v : pw.ais("pads")) if (v != 0) return false;
+    for (int64_t v : pw.ais("dilations")) if (v != 1) return false;
+    return true;
+  }
+
+  // a depthwise conv whose 1x1 consumer computes it (k_conv_pw / k_conv_dwpw): no launch
+  bool defer_depthwise(const ConvPlan& c) {
+    const ConvParams& p = c.p;
+    // (k_conv_pw stages the pair's channels in chunks: any count for a 3x3 / 5x5
+    // depthwise on enough pixels; k_conv_dwpw, the rest, holds all of them in LDS)
+    const int pw_m = consumer_out_channels(c.out, c.last);
+    // (pw_pair_fits: pw_kernel's own test, its 32-bit offset limits included —
+    // a pair it declined would fall to k_conv_dwpw, whose LDS holds kDwPwMaxC)
+    const bool pw_dw = p.kh == p.kw && (p.kh == 3 || p.kh == 5) && pw_m > 0 &&
+                       pw_pair_fits(p.N, p.C, (long)p.H * p.W, (long)p.Ho * p.Wo, pw_m);
+    return p.G == p.C && p.G == p.M && !p.ep.res && !c.ib && (pw_dw || p.C <= kDwPwMaxC) &&
+           feeds_pointwise(c.out, c.last, p.M);
+  }
+
+  bool plan_conv(size_t ni, const Node& nd, Ins&) {
+    const std::string& in0 = nd.in[0];
+    // a deferred Concat copy into this Conv's input: only a dense 3x3 / 5x5
+    // convolution (plan_conv_dense, which takes it or flushes) may take it;
+    // every other plan reads the whole concatenation
+    if (cat_tail.count(in0)) {
+      Value* w = nd.in.size() > 1 ? val(nd.in[1]) : nullptr;
+      const bool dense = w && w->shape.size() == 4 && nd.ai("group", 1) == 1 && w->shape[2] == w->shape[3] &&
+                         (w->shape[2] == 3 || w->shape[2] == 5);
+      if (!dense && !flush_tail(in0)) return false;
+    }
+    if (const int rc = try_plan_ir(ni)) return rc > 0;
+    ConvPlan c;
+    if (!conv_geometry(nd, &c) || !conv_absorb(ni, &c)) return false;
+    ConvParams& p = c.p;
+    p.w = upload_vec(c.wf);
+    p.ep.bias = c.has_bias ? upload_vec(c.bias) : nullptr;
+    if (!p.w || (c.has_bias && !p.ep.bias)) return false;
+    p.x = dptr(*val(in0));
+    if (!(p.y = make_out(c.out, c.oshape))) return false;
+    if (defer_depthwise(c)) {
+      flush_input(in0);
+      pending_dw[c.out] = {p.x, DwPre{p.w, p.H, p.W, p.kh, p.kw, p.sh, p.sw, p.dh, p.dw, p.pt, p.pl, p.ep}};
+      return true;
+    }
+    auto pre = pending_dw.find(in0);
+    if (pre != pending_dw.end()) {
+      if (p.G != 1 || p.kh != 1 || p.kw != 1 || p.sh != 1 || p.sw != 1 || p.pt || p.pl || p.Ho != p.H || p.Wo != p.W)
+        return fail("Conv '" + nd.name + "': internal: fused depthwise producer");
+      p.x = pre->second.first;
+      p.pre = pre->second.second;
+      pending_dw.erase(pre);  // (its sole consumer: taken)
+    }
+    if (!c.ib && thin_conv_fits(p) && p.C <= kThinMaxC && thin_enabled()) return plan_conv_thin(in0, c);
+    flush_norm(in0);  // (a pending InstanceNorm apply step: not taken here)
+    if (!plan_conv_dense(in0, c)) return false;
+    if (!c.ib) return true;
+    const Node& inn = g.nodes[c.ib->inorm];
+    const std::string* direct = cat_direct.count(c.out) ? &c.out : nullptr;
+    // a thin 1x1 consumer normalises its input itself: statistics only here
+    const bool defer = !direct && thin_enabled() && feeds_thin(c.out, c.last);
+    return plan_norm(p.y, p.y, p.N, p.M - c.ib->nb, c.ib->nb, p.M, (int64_t)p.Ho * p.Wo, inn, val(inn.in[1]),
+                     val(inn.in[2]), c.ib->relu >= 0 ? ACT_RELU : ACT_NONE, direct, defer ? &c.out : nullptr);
+  }
+
+  // k_conv_thin (a matte / logit head: memory bound, on the VALU); its input's
+  // InstanceNorm apply step, when left pending, folded into the loads
+  bool plan_conv_thin(const std::string& in0, const ConvPlan& c) {
+    std::shared_ptr<NormParams> norm;
+    auto nt = norm_pending.find(in0);
+    if (nt != norm_pending.end()) {
+      norm = nt->second;
+      norm_pending.erase(nt);
+    }
+    flush_input(in0);  // (a pending Resize, or a Concat's pending upsampled inputs)
+    auto pp = std::make_shared<ConvParams>(c.p);
+    std::vector<Region> io{reg(pp)};
+    if (norm) io.push_back(reg(norm));
+    s->launches.push_back(
+        Launch{conv_thin_name(c.p.M), [pp, norm](hipStream_t st) { launch_conv_thin(*pp, norm.get(), st); }, io});
+    retarget_on_concat(c.out, pp, c.p.M);
+    return true;
+  }
+
+  // k_conv_tile where it has a shape for the convolution (with a 2x upsample
+  // of its input, or of one Concat input, computed while staging, and a
+  // Concat's tail read in place), else the generic kernels (launch_conv)
+  static constexpr double kTileMinMacs = 8e6;  // f32: smaller convs keep k_conv_small / k_conv_gemm
+  bool plan_conv_dense(const std::string& in0, const ConvPlan& c) {
+    const ConvParams& p = c.p;
+    ConvTileShape ts{};
+    const double macs = (double)p.N * p.M * p.Ho * p.Wo * p.Cg * p.kh * p.kw;
+    const bool tile = !p.pre.w && conv_tile_shape(p, s->conv_precision, &ts) &&
+                      (s->conv_precision != PREC_F32 || macs >= kTileMinMacs);
+    std::vector<UpRange> ups;
+    if (up_pending.count(in0)) ups.push_back({in0, 0, p.C});
+    else if (cat_up.count(in0)) ups = cat_up[in0];
+    const ResizeParams* up = nullptr;
+    // (one output-channel tile of at most 32 only: each tile would interpolate
+    // the whole input again, and at 64 output channels the interpolation
+    // measured slower than the Resize's own launch, MODNet 288x512 b8 bf16)
+    static const bool up_bm64 = env_off("VSO_UP_BM64");  // (A/B knob: 64-channel upsample tiles)
+    if (tile && ups.size() == 1 && ts.s == 1 && (ts.ks == 3 || ts.ks == 5) && ts.Mp == ts.bm &&
+        (ts.bm <= 32 || up_bm64) &&
+        ts.prec != PREC_F32 && ups[0].c0 % 32 == 0 && ups[0].c1 % 32 == 0 && up_fuse_enabled()) {
+      ConvTileShape tu{};
+      tu.up = 1;
+      if (conv_tile_shape(p, s->conv_precision, &tu)) {
+        up = up_pending[ups[0].name].get();
+        ts = tu;
+      }
+    }
+    for (const UpRange& u : ups)
+      if (!up || u.name != ups[0].name) flush_up(u.name);
+    if (!tile) {
+      if (!flush_tail(in0)) return false;
+      auto pp = emit(conv_kernel_name(p), p, [](const ConvParams& q, hipStream_t st) { launch_conv(q, st, nullptr); });
+      retarget_on_concat(c.out, pp, p.M);
+      return true;
+    }
+    const CatTail* tail = nullptr;
+    auto ct = cat_tail.find(in0);
+    if (ct != cat_tail.end() && ct->second.c0 + ct->second.C == p.C && ct->second.c0 % 32 == 0 &&
+        (!up || ct->second.c0 >= ups[0].c1))
+      tail = &ct->second;
+    else if (!flush_tail(in0))
+      return false;
+    if (!plan_conv_tile(c, ts, up, up ? ups[0].c0 : 0, up ? ups[0].c1 : 0, tail)) return false;
+    if (tail) cat_tail.erase(in0);
+    if (up) up_pending.erase(ups[0].name);
+    return true;
+  }
+
+  // A dense convolution on k_conv_tile (vso_conv.hip): weights (BatchNorm
+  // folded) packed [tap][Mp][Cp] in the operand type, zero padded; a
+  // partial-sum buffer when the channel chunks are split over workgroups.
+  bool plan_conv_tile(const ConvPlan& c, const ConvTileShape& ts, const ResizeParams* up, int up_c0, int up_c1,
+                      const CatTail* tail) {
+    const ConvParams& p = c.p;
+    const int taps = p.kh * p.kw;
+    const size_t n = (size_t)taps * ts.Mp * ts.Cp;
+    ConvTileParams tp{};
+    tp.c = p;
+    tp.Mp = ts.Mp; tp.Cp = ts.Cp; tp.tiles_x = ts.tiles_x; tp.ksplit = ts.ksplit; tp.cps = ts.cps;
+    static const int qskip = (int)env_int("VSO_CONV_QSKIP", 1);
+    tp.qskip = qskip;
+    static const int xcd = (int)env_int("VSO_CONV_XCD", 1);
+    tp.xcd = xcd;
+    if (tail) {
+      tp.x2 = tail->x;
+      tp.x2_c0 = tail->c0;
+      tp.x2_C = tail->C;
+    }
+    tp.tiles = ts.tiles; tp.mtiles = ts.Mp / ts.bm;
+    if (up) {
+      tp.up = up->x;
+      tp.up_H = up->H; tp.up_W = up->W;
+      tp.up_c0 = up_c0; tp.up_c1 = up_c1;
+    }
+    // w[tap][m][c] of the packed layout <- the node's [m][c][tap]
+    auto pack = [&](auto* w, auto conv) {
+      for (int tap = 0; tap < taps; ++tap)
+        for (int m = 0; m < p.M; ++m)
+          for (int ch = 0; ch < p.C; ++ch)
+            w[((size_t)tap * ts.Mp + m) * ts.Cp + ch] = conv(c.wf[((size_t)m * p.C + ch) * taps + tap]);
+    };
+    if (ts.prec == PREC_F32) {
+      std::vector<float> w(n, 0.f);
+      pack(w.data(), [](float v) { return v; });
+      tp.wp = upload_bytes(w.data(), n * 4, "conv weight upload failed");
+    } else {
+      std::vector<uint16_t> w(n, 0);
+      if (ts.prec == PREC_BF16) pack(w.data(), [](float v) { return float_to_bf16(v); });
+      else pack(w.data(), [](float v) { return float_to_half_bits(v); });
+      tp.wp = upload_bytes(w.data(), n * 2, "conv weight upload failed");
+    }
+    if (!tp.wp) return false;
+    if (ts.ksplit > 1) {
+      const size_t blocks = (size_t)p.N * (ts.Mp / ts.bm) * ts.tiles;
+      // partial tiles in accumulator order: per output block and split, 256 threads x bm/16 x th*tw/64 f4
+      const size_t per = (size_t)256 * (ts.bm / 16) * (ts.th * ts.tw / 64) * 16;
+      if (!dalloc(&tp.part, blocks * ts.ksplit * per) || !dalloc(&tp.counters, blocks * 4))
+        return false;
+      if (hipMemset(tp.counters, 0, blocks * 4) != hipSuccess) return fail("hipMemset failed");
+    }
+    auto tpp = emit(conv_tile_name(ts), tp,
+                    [ts](const ConvTileParams& q, hipStream_t st) { launch_conv_tile(q, ts, st); });
+    retarget_on_concat(c.out, std::shared_ptr<ConvParams>(tpp, &tpp->c), p.M);
+    s->tile_convs++;
+    return true;
+  }
+
+  // ---- the other operators: one plan_<op> each -----------------------------
+  static void fill_strides(const std::vector<int64_t>& shape, std::vector<int64_t>* st) {
+    st->assign(shape.size(), 1);
+    for (int k = (int)shape.size() - 2; k >= 0; --k) (*st)[k] = (*st)[k + 1] * shape[k + 1];
+  }
+  static int64_t inner_from(const std::vector<int64_t>& shape, size_t d0) {  // the product of dims d0 on
+    int64_t n = 1;
+    for (size_t d = d0; d < shape.size(); ++d) n *= shape[d];
+    return n;
+  }
+  static std::vector<int64_t> ints(const Value& v) {
+    return v.c.is_int ? v.c.i : std::vector<int64_t>(v.c.f.begin(), v.c.f.end());
+  }
+
+  bool plan_view(size_t, const Node& nd, Ins& in) {  // Reshape, Flatten, Squeeze, Unsqueeze: an alias
+    std::vector<int64_t> shp;
+    if (!infer_view(nd, operands(in), &shp, &err)) return false;
+    return set_runtime(nd.out[0], shp, in[0]->buf);
+  }
+
+  bool plan_alias(size_t, const Node& nd, Ins& in) {  // Identity, Dropout
+    return set_runtime(nd.out[0], in[0]->shape, in[0]->buf);
+  }
+
+  bool plan_unary(const Node& nd, Value& x, int act, float a0, float a1) {
+    UnaryParams p{};
+    p.x = dptr(x);
+    p.act = act; p.a0 = a0; p.a1 = a1;
+    if (!(p.y = make_out(nd.out[0], x.shape))) return false;
+    p.n = vals[nd.out[0]].numel();
+    emit("vso::k_unary(vso::UnaryParams)", p, launch_unary);
+    return true;
+  }
+
+  bool plan_cast(size_t ni, const Node& nd, Ins& in) {
+    const int64_t to = nd.ai("to", DT_FLOAT);
+    // float16 storage semantics: round to the nearest half (the values stay
+    // f32 in HBM; later ops compute in f32, a superset of the f16 precision)
+    if (to == DT_FLOAT16) return plan_unary(nd, *in[0], ACT_F16, 0.f, 0.f);
+    if (to != DT_FLOAT) return fail("Cast of a runtime tensor to a non-float type");
+    return plan_alias(ni, nd, in);
+  }
+
+  bool plan_activation(size_t, const Node& nd, Ins& in) {
+    const std::vector<int64_t>& xs = in[0]->shape;
+    if (nd.op == "PRelu") {
+      // unidirectional: the slope broadcasts to x, never x to the slope
+      const std::vector<int64_t>& ss = in[1]->shape;
+      bool uni = ss.size() <= xs.size();
+      for (size_t d = 0; uni && d < ss.size(); ++d)
+        uni = ss[d] == 1 || ss[d] == xs[d + xs.size() - ss.size()];
+      if (!uni) return fail("PRelu '" + nd.name + "': slope does not broadcast to the input");
+      return plan_binary(nd, in[0], in[1], BIN_PRELU);
+    }
+    Epilogue ep{};
+    if (!act_of(nd, &ep, 0)) return fail(nd.op + " '" + nd.name + "': non-constant parameters");
+    return plan_unary(nd, *in[0], ep.act, ep.a0, ep.a1);
+  }
+
+  bool plan_arith(size_t, const Node& nd, Ins& in) {
+    const std::string& op = nd.op;
+    return plan_binary(nd, in[0], in[1], op == "Add" ? BIN_ADD : op == "Sub" ? BIN_SUB : op == "Mul" ? BIN_MUL : BIN_DIV);
+  }
+
+  bool plan_binary(const Node& nd, Value* a, Value* b, int op) {
+    const size_t ra = a->shape.size(), rb = b->shape.size(), rk = std::max(ra, rb);
+    if (rk > (size_t)kMaxDims) return fail(nd.op + ": rank > 6");
+    std::vector<int64_t> os(rk);
+    for (size_t d = 0; d < rk; ++d) {
+      const int64_t da = d + ra >= rk ? a->shape[d + ra - rk] : 1, db = d + rb >= rk ? b->shape[d + rb - rk] : 1;
+      if (da != db && da != 1 && db != 1) return fail(nd.op + " '" + nd.name + "': shapes do not broadcast");
+      os[d] = std::max(da, db);
+    }
+    std::vector<int64_t> sta, stb;
+    fill_strides(a->shape, &sta);
+    fill_strides(b->shape, &stb);
+    BinParams p{};
+    p.nd = (int)rk;
+    for (size_t d = 0; d < rk; ++d) {
+      p.dims[d] = (int)os[d];
+      const int64_t da = d + ra >= rk ? a->shape[d + ra - rk] : 1, db = d + rb >= rk ? b->shape[d + rb - rk] : 1;
+      p.sa[d] = da == 1 ? 0 : sta[d + ra - rk];
+      p.sb[d] = db == 1 ? 0 : stb[d + rb - rk];
+    }
+    p.op = op;
+    p.a = operand(*a);
+    p.b = operand(*b);
+    if (!p.a || !p.b) return false;
+    if (!(p.y = make_out(nd.out[0], os))) return false;
+    p.n = vals[nd.out[0]].numel();
+    emit(binary_kernel_name(p), p, launch_binary);
+    return true;
+  }
+
+  // One strided copy (k_copy; k_copy_rows where it is rows of one contiguous
+  // run): iteration space `iter`, written at dst_off, read from src_start by
+  // src_step through src_perm, `fill` outside the source
+  bool plan_copy_into(const float* src, const std::vector<int64_t>& src_shape, float* dst,
+                      const std::vector<int64_t>& dst_shape, const std::vector<int64_t>& iter, const std::vector<int64_t>& dst_off,
+                      const std::vector<int64_t>& src_start, const std::vector<int64_t>& src_step,
+                      const std::vector<int64_t>& src_perm, float fill) {
+    const size_t rk = iter.size();
+    if (rk > (size_t)kMaxDims) return fail("copy: rank > 6");
+    std::vector<int64_t> sst, dst_st;
+    fill_strides(src_shape, &sst);
+    fill_strides(dst_shape, &dst_st);
+    CopyParams p{};
+    p.nd = (int)rk;
+    p.n = 1;
+    long base = 0;
+    for (size_t d = 0; d < rk; ++d) {
+      p.size[d] = (int)iter[d];
+      p.n *= iter[d];
+      p.dst_stride[d] = dst_st[d];
+      base += dst_off[d] * dst_st[d];
+      const int64_t sd = src_perm.empty() ? (int64_t)d : src_perm[d];
+      p.src_stride[d] = sst[sd];
+      p.start[d] = (int)src_start[d];
+      p.step[d] = (int)src_step[d];
+      p.lim[d] = (int)src_shape[sd];
+    }
+    p.dst_base = base;
+    p.src_base = 0;
+    p.src = src;
+    p.dst = dst;
+    p.fill = fill;
+    if (p.n == 0) return true;
+    // a block copy (Concat / Split / Slice of whole trailing dims, no fill):
+    // rows of one contiguous run in both tensors -> k_copy_rows (16-byte moves)
+    bool block = src_perm.empty();
+    for (size_t d = 0; block && d < rk; ++d)
+      block = src_step[d] == 1 && src_start[d] >= 0 && src_start[d] + iter[d] <= src_shape[d];
+    if (block) {
+      int d = (int)rk - 1;
+      int64_t inner = 1;
+      while (d >= 0 && iter[d] == src_shape[d] && iter[d] == dst_shape[d]) inner *= iter[d--];
+      if (d >= 0) inner *= iter[d--];
+      bool one_outer = true;  // at most one outer dimension left (dim 0)
+      for (int k = 0; k <= d && k < (int)rk; ++k)
+        if (k > 0 && iter[k] != 1) one_outer = false;
+      if (one_outer && d <= 0) {
+        RowCopyParams q{};
+        q.src = src;
+        q.dst = dst;
+        q.inner = inner;
+        q.rows = d == 0 ? iter[0] : 1;
+        q.src_row = d == 0 ? sst[0] : 0;
+        q.dst_row = d == 0 ? dst_st[0] : 0;
+        int64_t sb = 0;
+        for (size_t k = 0; k < rk; ++k) sb += src_start[k] * sst[k];
+        q.src_base = sb;
+        q.dst_base = base;
+        emit(row_copy_name(q), q, launch_copy_rows);
+        return true;
+      }
+    }
+    emit("vso::k_copy(vso::CopyParams)", p, launch_copy);
+    return true;
+  }
+  // ... a whole tensor `x` (shape xs) into `name` (shape os), from `start` by `step`
+  bool plan_copy_out(const std::string& name, const std::vector<int64_t>& os, const float* x,
+                     const std::vector<int64_t>& xs, const std::vector<int64_t>& start,
+                     const std::vector<int64_t>& step, const std::vector<int64_t>& perm, float fill) {
+    float* y = make_out(name, os);
+    return y && plan_copy_into(x, xs, y, os, os, std::vector<int64_t>(os.size(), 0), start, step, perm, fill);
+  }
+
+  bool plan_pool(size_t, const Node& nd, Ins& in) {  // MaxPool, AveragePool
+    const std::string& op = nd.op;
+    const std::vector<int64_t>& xs = in[0]->shape;
+    if (xs.size() != 4) return fail(op + ": 2D only");
+    std::vector<int64_t> k = nd.ais("kernel_shape"), st = nd.ais("strides"), dl = nd.ais("dilations"), pd = nd.ais("pads");
+    if (k.size() != 2) return fail(op + ": kernel_shape must be 2D");
+    if (!pd.empty() && pd.size() != 4) return fail(op + ": pads must have 4 values");
+    if (nd.ai("storage_order", 0) != 0) return fail(op + ": storage_order 1 is not supported");
+    if (nd.out.size() > 1 && !nd.out[1].empty()) return fail(op + ": the Indices output is not supported");
+    PoolParams p{};
+    p.N = (int)xs[0]; p.C = (int)xs[1]; p.H = (int)xs[2]; p.W = (int)xs[3];
+    p.kh = (int)k[0]; p.kw = (int)k[1];
+    p.sh = st.size() > 0 ? (int)st[0] : 1; p.sw = st.size() > 1 ? (int)st[1] : 1;
+    p.dh = dl.size() > 0 ? (int)dl[0] : 1; p.dw = dl.size() > 1 ? (int)dl[1] : 1;
+    int pads[4] = {0, 0, 0, 0};  // top, left, bottom, right
+    for (size_t q = 0; q < pd.size(); ++q) pads[q] = (int)pd[q];
+    same_pads(nd.as("auto_pad", "NOTSET"), p, pads);
+    p.pt = pads[0]; p.pl = pads[1];
+    p.He = p.H + pads[2]; p.We = p.W + pads[3];
+    const bool ceil_mode = nd.ai("ceil_mode", 0) != 0;
+    auto osz = [&](int i, int p0, int p1, int kk, int ss, int dd) {
+      const int num = i + p0 + p1 - dd * (kk - 1) - 1;
+      int o = (ceil_mode ? (num + ss - 1) / ss : num / ss) + 1;
+      if (ceil_mode && (o - 1) * ss >= i + p0) --o;
+      return o;
+    };
+    p.Ho = osz(p.H, pads[0], pads[2], p.kh, p.sh, p.dh);
+    p.Wo = osz(p.W, pads[1], pads[3], p.kw, p.sw, p.dw);
+    p.max_mode = op == "MaxPool";
+    p.count_include_pad = (int)nd.ai("count_include_pad", 0);
+    p.x = dptr(*in[0]);
+    if (!(p.y = make_out(nd.out[0], {xs[0], xs[1], p.Ho, p.Wo}))) return false;
+    emit("vso::k_pool(vso::PoolParams)", p, launch_pool);
+    return true;
+  }
+
+  bool plan_global_pool(size_t, const Node& nd, Ins& in) {  // GlobalAveragePool
+    const std::vector<int64_t>& xs = in[0]->shape;
+    RowParams p{};
+    p.x = dptr(*in[0]);
+    p.rows = xs[0] * xs[1];
+    p.inner = inner_from(xs, 2);
+    std::vector<int64_t> os = {xs[0], xs[1]};
+    for (size_t d = 2; d < xs.size(); ++d) os.push_back(1);
+    if (!(p.y = make_out(nd.out[0], os))) return false;
+    emit(gap_kernel_name(p), p, launch_gap);
+    return true;
+  }
+
+  bool plan_instance_norm(size_t, const Node& nd, Ins& in) {
+    const std::vector<int64_t>& xs = in[0]->shape;
+    if (!in[1]->is_const || !in[2]->is_const) return fail("InstanceNormalization: constant scale/B only");
+    if (xs.size() < 3) return fail("InstanceNormalization: rank >= 3 only");
+    float* y = make_out(nd.out[0], xs);
+    return y && plan_norm(dptr(*in[0]), y, (int)xs[0], (int)xs[1], 0, (int)xs[1], inner_from(xs, 2), nd, in[1], in[2],
+                          ACT_NONE);
+  }
+
+  // InstanceNormalization (node `nd`, constant scale / B) of planes c0 .. c0+C-1
+  // of an [N][ctot][inner] tensor: k_norm_plane, or k_norm_stats + k_norm_apply
+  bool plan_norm(const float* x, float* y, int N, int C, int c0, int ctot, int64_t inner, const Node& nd, Value* sc,
+                 Value* sh, int act, const std::string* direct = nullptr, const std::string* defer = nullptr) {
+    if (sc->c.numel() != C || sh->c.numel() != C) return fail("InstanceNormalization '" + nd.name + "': scale/B size");
+    NormParams p{};
+    p.x = x; p.y = y;
+    p.N = N; p.C = C; p.c0 = c0; p.ctot = ctot;
+    p.inner = inner;
+    p.scale = upload(sc->c);
+    p.shift = upload(sh->c);
+    p.eps = nd.af("epsilon", 1e-5f);
+    p.act = act;
+    p.chunk = kNormChunk;
+    p.chunks = (int)((inner + kNormChunk - 1) / kNormChunk);
+    if (!p.scale || !p.shift || !dalloc(&p.stats, (size_t)N * C * std::max(p.chunks, 1) * 3 * 4)) return false;
+    if (inner == 0 || N * C == 0) return true;
+    std::shared_ptr<NormParams> pp;
+    if (!defer && norm_plane_fits(inner) && norm_plane_enabled()) {
+      pp = emit(norm_plane_name(inner), p, launch_norm_plane);
+    } else {
+      pp = emit("vso::k_norm_stats(vso::NormParams)", p, launch_norm_stats);
+      if (defer) {  // the apply step runs in the consumer (k_conv_thin) or, failing that, flush_norm
+        norm_pending[*defer] = pp;
+        return true;
+      }
+      add("vso::k_norm_apply(vso::NormParams)", pp, launch_norm_apply);
+    }
+    if (direct)  // in place on the conv's output, wherever that now lies
+      cat_patch[*direct].push_back([pp](float* base, int ctot) { pp->x = pp->y = base; pp->ctot = ctot; });
+    return true;
+  }
+
+  bool plan_batch_norm(size_t, const Node& nd, Ins& in) {
+    const std::vector<int64_t>& xs = in[0]->shape;
+    for (int k = 1; k <= 4; ++k)
+      if (!in[k]->is_const) return fail("BatchNormalization: constant parameters only");
+    const int C = (int)xs[1];
+    std::vector<float> sc(C), sh(C);
+    const BnConsts b = bn_consts(nd);
+    for (int c = 0; c < C; ++c) {
+      const double a = b.a(c);
+      sc[c] = (float)a;
+      sh[c] = (float)(b.B.f[c] - b.mean.f[c] * a);
+    }
+    AffineParams p{};
+    p.x = dptr(*in[0]);
+    p.C = C;
+    p.inner = inner_from(xs, 2);
+    p.scale = upload_vec(sc);
+    p.shift = upload_vec(sh);
+    if (!(p.y = make_out(nd.out[0], xs))) return false;
+    p.n = vals[nd.out[0]].numel();
+    emit("vso::k_affine(vso::AffineParams)", p, launch_affine);
+    return true;
+  }
+
+  bool plan_softmax(size_t, const Node& nd, Ins& in) {
+    const std::vector<int64_t>& xs = in[0]->shape;
+    // opset 13 on: along `axis` (default -1), here the last axis only.  Before:
+    // the input flattened to 2-D at `axis` (default 1), each row normalised.
+    const bool flat = g.opset > 0 && g.opset < 13;
+    const int64_t rk = (int64_t)xs.size();
+    int64_t ax = nd.ai("axis", flat ? 1 : -1);
+    if (ax < 0) ax += rk;
+    if (ax < 0 || ax >= rk) return fail("Softmax: axis out of range");
+    if (!flat && ax != rk - 1) return fail("Softmax: last axis only");
+    RowParams p{};
+    p.x = dptr(*in[0]);
+    p.inner = inner_from(xs, (size_t)ax);
+    p.rows = in[0]->numel() / std::max<int64_t>(p.inner, 1);
+    if (!(p.y = make_out(nd.out[0], xs))) return false;
+    emit("vso::k_softmax(vso::RowParams)", p, launch_softmax);
+    return true;
+  }
+
+  bool plan_transpose(size_t, const Node& nd, Ins& in) {
+    const std::vector<int64_t>& xs = in[0]->shape;
+    std::vector<int64_t> perm = nd.ais("perm");
+    const size_t rk = xs.size();
+    if (perm.empty()) for (size_t k = 0; k < rk; ++k) perm.push_back((int64_t)(rk - 1 - k));
+    std::vector<int64_t> os(rk);
+    for (size_t k = 0; k < rk; ++k) os[k] = xs[perm[k]];
+    return plan_copy_out(nd.out[0], os, dptr(*in[0]), xs, std::vector<int64_t>(rk, 0), std::vector<int64_t>(rk, 1),
+                         perm, 0.f);
+  }
+
+  bool plan_pad(size_t, const Node& nd, Ins& in) {
+    const std::vector<int64_t>& xs = in[0]->shape;
+    const std::string mode = nd.as("mode", "constant");
+    if (mode != "constant") return fail("Pad: constant mode only");
+    std::vector<int64_t> pads = nd.ais("pads");
+    if (in.size() > 1 && in[1]) {
+      if (!in[1]->is_const) return fail("Pad: constant pads only");
+      pads = ints(*in[1]);
+    }
+    float value = nd.af("value", 0.f);
+    if (in.size() > 2 && in[2]) {
+      if (!in[2]->is_const) return fail("Pad: constant value only");
+      if (!in[2]->c.f.empty()) value = in[2]->c.f[0];
+    }
+    const size_t rk = xs.size();
+    std::vector<int64_t> axes;
+    if (in.size() > 3 && in[3]) {
+      if (!in[3]->is_const) return fail("Pad: constant axes only");
+      axes = in[3]->c.i;
+    }
+    std::vector<int64_t> pb(rk, 0), pe(rk, 0);
+    if (axes.empty()) {
+      if (pads.size() != 2 * rk) return fail("Pad: pads length");
+      for (size_t d = 0; d < rk; ++d) { pb[d] = pads[d]; pe[d] = pads[d + rk]; }
+    } else {
+      if (pads.size() != 2 * axes.size()) return fail("Pad: pads length");
+      for (size_t k = 0; k < axes.size(); ++k) {
+        const int64_t a = axes[k] < 0 ? axes[k] + (int64_t)rk : axes[k];
+        if (a < 0 || a >= (int64_t)rk) return fail("Pad: axis out of range");
+        pb[a] = pads[k];
+        pe[a] = pads[k + axes.size()];
+      }
+    }
+    std::vector<int64_t> os(rk), start(rk);
+    for (size_t d = 0; d < rk; ++d) {
+      os[d] = xs[d] + pb[d] + pe[d];
+      start[d] = -pb[d];
+      if (os[d] < 0) return fail("Pad: negative pads remove more than the axis holds");
+    }
+    return plan_copy_out(nd.out[0], os, dptr(*in[0]), xs, start, std::vector<int64_t>(rk, 1), {}, value);
+  }
+
+  bool plan_concat(size_t ni, const Node& nd, Ins& in) {
+    const std::vector<int64_t>& xs = in[0]->shape;
+    int64_t ax = nd.ai("axis", 0);
+    const size_t rk = xs.size();
+    if (ax < 0) ax += (int64_t)rk;
+    std::vector<int64_t> os = xs;
+    os[ax] = 0;
+    for (Value* v : in) os[ax] += v->shape[ax];
+    float* dst = make_out(nd.out[0], os);
+    if (!dst) return false;
+    const std::vector<int64_t> zero(rk, 0), one(rk, 1);
+    int64_t off = 0;
+    for (size_t q = 0; q < in.size(); ++q) {
+      Value* v = in[q];
+      std::vector<int64_t> doff(rk, 0);
+      doff[ax] = off;
+      off += v->shape[ax];
+      auto direct = cat_patch.find(nd.in[q]);
+      if (direct != cat_patch.end() && rk == 4 && ax == 1) {  // its producer writes it here
+        for (auto& f : direct->second) f(dst + doff[1] * os[2] * os[3], (int)os[1]);
+        if (up_pending.count(nd.in[q]))
+          cat_up[nd.out[0]].push_back({nd.in[q], (int)doff[1], (int)(doff[1] + v->shape[1])});
+        continue;
+      }
+      flush_up(nd.in[q]);
+      if (q + 1 == in.size() && rk == 4 && ax == 1 && doff[1] % 32 == 0 && doff[1] > 0 && cat_tail_enabled()) {
+        const int c = sole_consumer(nd.out[0], ni);
+        if (c >= 0 && g.nodes[c].op == "Conv" && g.nodes[c].in[0] == nd.out[0]) {  // left to that Conv (cat_tail)
+          const float* src = operand(*v);
+          if (!src) return false;
+          const std::vector<int64_t> vs = v->shape;
+          cat_tail[nd.out[0]] = {src, (int)doff[1], (int)v->shape[1], [this, src, vs, dst, os, doff, zero, one]() {
+                                   return plan_copy_into(src, vs, dst, os, vs, doff, zero, one, {}, 0.f);
+                                 }};
+          continue;
+        }
+      }
+      if (!plan_copy_into(operand(*v), v->shape, dst, os, v->shape, doff, zero, one, {}, 0.f)) return false;
+    }
+    return true;
+  }
+
+  bool plan_split(size_t, const Node& nd, Ins& in) {
+    const std::vector<int64_t>& xs = in[0]->shape;
+    int64_t ax = nd.ai("axis", 0);
+    const size_t rk = xs.size();
+    if (ax < 0) ax += (int64_t)rk;
+    std::vector<int64_t> sp = nd.ais("split");
+    if (in.size() > 1 && in[1]) sp = in[1]->c.i;
+    const int64_t k = (int64_t)nd.out.size();
+    if (sp.empty()) {
+      // opset 18: ceil-sized parts, the last one smaller; before, even parts only
+      if (xs[ax] % k != 0 && g.opset > 0 && g.opset < 18)
+        return fail("Split '" + nd.name + "': uneven default split needs opset 18");
+      const int64_t part = (xs[ax] + k - 1) / k;
+      for (int64_t q = 0; q < k; ++q) sp.push_back(std::max<int64_t>(0, std::min(part, xs[ax] - q * part)));
+    }
+    int64_t sum = 0;
+    for (int64_t v : sp) sum += v;
+    if ((int64_t)sp.size() != k || sum != xs[ax]) return fail("Split '" + nd.name + "': sizes do not add up to the axis");
+    int64_t off = 0;
+    for (int64_t q = 0; q < k; ++q) {
+      std::vector<int64_t> os = xs;
+      os[ax] = sp[q];
+      std::vector<int64_t> start(rk, 0);
+      start[ax] = off;
+      off += sp[q];
+      if (!plan_copy_out(nd.out[q], os, dptr(*in[0]), xs, start, std::vector<int64_t>(rk, 1), {}, 0.f)) return false;
+    }
+    return true;
+  }
+
+  bool plan_slice(size_t, const Node& nd, Ins& in) {
+    const std::vector<int64_t>& xs = in[0]->shape;
+    const size_t rk = xs.size();
+    std::vector<int64_t> st, en, axes, steps;
+    if (in.size() >= 3) {
+      for (size_t k = 1; k < in.size(); ++k)
+        if (in[k] && !in[k]->is_const) return fail("Slice: constant starts/ends/axes/steps only");
+      st = ints(*in[1]); en = ints(*in[2]);
+      if (in.size() > 3 && in[3]) axes = ints(*in[3]);
+      if (in.size() > 4 && in[4]) steps = ints(*in[4]);
+    } else {
+      st = nd.ais("starts"); en = nd.ais("ends"); axes = nd.ais("axes");
+    }
+    if (axes.empty()) for (size_t k = 0; k < st.size(); ++k) axes.push_back((int64_t)k);
+    if (steps.empty()) steps.assign(st.size(), 1);
+    std::vector<int64_t> os = xs, start(rk, 0), step(rk, 1);
+    for (size_t k = 0; k < st.size(); ++k) {
+      const int64_t a = axes[k] < 0 ? axes[k] + (int64_t)rk : axes[k];
+      const int64_t L = xs[a], sk = steps[k];
+      if (sk == 0) return fail("Slice: zero step");
+      int64_t b = st[k] < 0 ? st[k] + L : st[k], e = en[k] < 0 ? en[k] + L : en[k];
+      if (sk > 0) { b = std::clamp<int64_t>(b, 0, L); e = std::clamp<int64_t>(e, 0, L); os[a] = std::max<int64_t>(0, (e - b + sk - 1) / sk); }
+      else { b = std::clamp<int64_t>(b, 0, L - 1); e = std::clamp<int64_t>(e, -1, L - 1); os[a] = std::max<int64_t>(0, (b - e - sk - 1) / (-sk)); }
+      start[a] = b;
+      step[a] = sk;
+    }
+    return plan_copy_out(nd.out[0], os, dptr(*in[0]), xs, start, step, {}, 0.f);
+  }
+
+  bool plan_resize(size_t, const Node& nd, Ins& in) {  // Resize, Upsample
+    const std::string& op = nd.op;
+    const std::vector<int64_t>& xs = in[0]->shape;
+    if (xs.size() != 4) return fail(op + ": 4D only");
+    std::vector<float> scales;
+    std::vector<int64_t> sizes;
+    if (op == "Upsample") {
+      if (in.size() > 1 && in[1] && in[1]->is_const) scales = in[1]->c.f;
+      else scales = nd.attrs.count("scales") ? nd.attrs.at("scales").fs : std::vector<float>{};
+    } else {
+      if (in.size() > 2 && in[2]) { if (!in[2]->is_const) return fail("Resize: constant scales only"); scales = in[2]->c.f; }
+      if (in.size() > 3 && in[3]) { if (!in[3]->is_const) return fail("Resize: constant sizes only"); sizes = in[3]->c.i; }
+    }
+    ResizeParams p{};
+    p.N = (int)xs[0]; p.C = (int)xs[1]; p.H = (int)xs[2]; p.W = (int)xs[3];
+    if (!sizes.empty()) {
+      if (sizes.size() != 4 || sizes[0] != xs[0] || sizes[1] != xs[1]) return fail("Resize: N, C must not change");
+      p.Ho = (int)sizes[2]; p.Wo = (int)sizes[3];
+      p.sy = (float)p.Ho / p.H; p.sx = (float)p.Wo / p.W;
+    } else {
+      if (scales.size() != 4 || scales[0] != 1.f || scales[1] != 1.f) return fail("Resize: scales on H, W only");
+      p.sy = scales[2]; p.sx = scales[3];
+      p.Ho = (int)std::floor(p.H * (double)p.sy);
+      p.Wo = (int)std::floor(p.W * (double)p.sx);
+    }
+    const std::string mode = nd.as("mode", "nearest");
+    if (mode != "nearest" && mode != "linear" && mode != "bilinear") return fail("Resize: mode " + mode);
+    p.linear = mode != "nearest";
+    // the position of `v` in `names`, or -1
+    auto index_of = [](const std::string& v, std::initializer_list<const char*> names) {
+      int k = 0;
+      for (const char* n : names) { if (v == n) return k; ++k; }
+      return -1;
+    };
+    const std::string ctm = nd.as("coordinate_transformation_mode", op == "Upsample" ? "asymmetric" : "half_pixel");
+    p.ctm = index_of(ctm, {"half_pixel", "pytorch_half_pixel", "align_corners", "asymmetric"});
+    if (p.ctm < 0) return fail("Resize: coordinate_transformation_mode " + ctm);
+    // Upsample (opset 7-9) has neither attribute: y[o] = x[floor(o / scale)]
+    const std::string nm = nd.as("nearest_mode", op == "Upsample" ? "floor" : "round_prefer_floor");
+    p.nearest = index_of(nm, {"round_prefer_floor", "round_prefer_ceil", "floor", "ceil"});
+    if (p.nearest < 0) return fail("Resize: nearest_mode " + nm);
+    if (nd.ai("antialias", 0) != 0) return fail("Resize: antialias is not supported");
+    if (nd.has("axes")) return fail("Resize: axes is not supported");
+    if (nd.as("keep_aspect_ratio_policy", "stretch") != "stretch")
+      return fail("Resize: keep_aspect_ratio_policy " + nd.as("keep_aspect_ratio_policy", "") + " is not supported");
+    p.x = dptr(*in[0]);
+    if (!(p.y = make_out(nd.out[0], {xs[0], xs[1], p.Ho, p.Wo}))) return false;
+    if ((long)p.N * p.C * p.Ho * p.Wo >= (1L << 31)) return fail("Resize: output of 2^31 elements or more");
+    std::shared_ptr<ResizeParams> pp;
+    if (up_cand.count(nd.out[0]) && p.linear && (p.ctm == 0 || p.ctm == 1) && p.sy == 2.f && p.sx == 2.f &&
+        p.Ho == 2 * p.H && p.Wo == 2 * p.W && p.C % 32 == 0 && s->conv_precision != PREC_F32)
+      up_pending[nd.out[0]] = pp = std::make_shared<ResizeParams>(p);  // its consumer convolution computes it (or flush_up launches it)
+    else
+      pp = emit(resize_kernel_name(p), p, launch_resize);
+    retarget_on_concat(nd.out[0], pp, p.C);
+    return true;
+  }
+
+  // a following elementwise activation (the SE blocks' Relu / Sigmoid) in a
+  // Gemm / MatMul's epilogue (PRelu not: its slope's axis is ambiguous on [M, N]);
+  // then the launch
+  bool emit_gemm(size_t ni, const Node& nd, GemmParams& p, const std::vector<int64_t>& os, bool absorb_act) {
+    std::string out = nd.out[0];
+    const int c1 = absorb_act && gemm_act_enabled() ? sole_consumer(out, ni) : -1;
+    if (c1 >= 0 && is_act(g.nodes[c1].op) && g.nodes[c1].op != "PRelu" && act_of(g.nodes[c1], &p.ep, p.N)) {
+      done.insert((size_t)c1);
+      out = g.nodes[c1].out[0];
+    }
+    if (!(p.y = make_out(out, os))) return false;
+    emit(gemm_kernel_name(p), p, launch_gemm);
+    return true;
+  }
+
+  bool plan_gemm(size_t ni, const Node& nd, Ins& in) {
+    Value *a = in[0], *b = in[1];
+    if (a->shape.size() != 2 || b->shape.size() != 2) return fail("Gemm: 2D operands");
+    GemmParams p{};
+    const bool ta = nd.ai("transA", 0) != 0, tb = nd.ai("transB", 0) != 0;
+    p.alpha = nd.af("alpha", 1.f);
+    p.beta = nd.af("beta", 1.f);
+    p.batch = 1;
+    p.M = (int)(ta ? a->shape[1] : a->shape[0]);
+    p.K = (int)(ta ? a->shape[0] : a->shape[1]);
+    p.N = (int)(tb ? b->shape[0] : b->shape[1]);
+    if ((tb ? b->shape[1] : b->shape[0]) != p.K) return fail("Gemm: inner dimensions differ");
+    p.sam = ta ? 1 : p.K; p.sak = ta ? p.M : 1;
+    p.sbk = tb ? 1 : p.N; p.sbn = tb ? p.K : 1;
+    if (in.size() > 2 && in[2]) {
+      const std::vector<int64_t>& cs = in[2]->shape;
+      if (cs.size() == 2) { p.scm = cs[0] == 1 ? 0 : cs[1]; p.scn = cs[1] == 1 ? 0 : 1; }
+      else if (cs.size() == 1) { p.scm = 0; p.scn = cs[0] == 1 ? 0 : 1; }
+      else { p.scm = 0; p.scn = 0; }
+      p.c = operand(*in[2]);
+    }
+    p.a = operand(*a);
+    p.b = operand(*b);
+    if (!p.a || !p.b) return false;
+    return emit_gemm(ni, nd, p, {p.M, p.N}, true);
+  }
+
+  bool plan_matmul(size_t ni, const Node& nd, Ins& in) {
+    Value *a = in[0], *b = in[1];
+    const std::vector<int64_t>& as_ = a->shape;
+    const std::vector<int64_t>& bs = b->shape;
+    if (as_.size() < 2 || bs.size() < 2) return fail("MatMul: operands of rank >= 2 only");
+    GemmParams p{};
+    p.alpha = 1.f;
+    p.beta = 1.f;
+    p.M = (int)as_[as_.size() - 2]; p.K = (int)as_.back(); p.N = (int)bs.back();
+    if (bs[bs.size() - 2] != p.K) return fail("MatMul: inner dimensions differ");
+    int64_t ba = 1, bb = 1;
+    for (size_t d = 0; d + 2 < as_.size(); ++d) ba *= as_[d];
+    for (size_t d = 0; d + 2 < bs.size(); ++d) bb *= bs[d];
+    if (bb != 1 && bb != ba) return fail("MatMul: batch broadcast beyond [B] x [1] not supported");
+    p.batch = (int)ba;
+    p.sab = (int64_t)p.M * p.K; p.sam = p.K; p.sak = 1;
+    p.sbb = bb == 1 ? 0 : (int64_t)p.K * p.N; p.sbk = p.N; p.sbn = 1;
+    std::vector<int64_t> os(as_.begin(), as_.end() - 2);
+    os.push_back(p.M);
+    os.push_back(p.N);
+    p.a = operand(*a);
+    if (b->is_const && p.sbb == 0) {
+      // a constant B stored transposed ([N][K]): k contiguous for k_gemm<true>
+      std::vector<float> bt((size_t)p.K * p.N);
+      for (int k = 0; k < p.K; ++k)
+        for (int n2 = 0; n2 < p.N; ++n2) bt[(size_t)n2 * p.K + k] = b->c.f[(size_t)k * p.N + n2];
+      p.b = upload_vec(bt);
+      p.sbk = 1; p.sbn = p.K;
+    } else {
+      p.b = operand(*b);
+    }
+    if (!p.a || !p.b) return false;
+    return emit_gemm(ni, nd, p, os, true);
+  }
+
+  // com.microsoft MatMulNBits (the q4 layers of a q4f16 export): Y = A @ W^T
+  // (+ bias), W [N][K] dequantised once at create from 4-bit blocks:
+  // W[n][k] = (q - zp) * scale[n][k / block_size], q the k-th nibble of row
+  // n (low nibble first), zp the packed per-block zero point (default 8).
+  bool plan_matmul_nbits(size_t ni, const Node& nd, Ins& in) {
+    auto opt = [&](size_t k) { return in.size() > k ? in[k] : nullptr; };
+    Value *a = in[0], *bq = opt(1), *sc = opt(2), *zp = opt(3), *gidx = opt(4), *bias = opt(5);
+    if (!bq || !bq->is_const || !sc || !sc->is_const || (zp && !zp->is_const) || (bias && !bias->is_const))
+      return fail("MatMulNBits '" + nd.name + "': B, scales, zero_points and bias must be initializers");
+    if (gidx) return fail("MatMulNBits '" + nd.name + "': g_idx is not supported");
+    const int64_t K = nd.ai("K", 0), N = nd.ai("N", 0), bits = nd.ai("bits", 4), bs = nd.ai("block_size", 0);
+    if (bits != 4 || bs < 16 || K <= 0 || N <= 0) return fail("MatMulNBits '" + nd.name + "': 4-bit blocks only");
+    const int64_t kb = (K + bs - 1) / bs, blob = bs * bits / 8, zpb = (kb * bits + 7) / 8;
+    if (bq->c.numel() != N * kb * blob || sc->c.numel() != N * kb)
+      return fail("MatMulNBits '" + nd.name + "': B / scales sizes do not match K, N, block_size");
+    if (zp && (!zp->c.is_int || zp->c.numel() != N * zpb))
+      return fail("MatMulNBits '" + nd.name + "': only packed uint8 zero points are supported");
+    if (a->shape.empty() || a->shape.back() != K) return fail("MatMulNBits '" + nd.name + "': A's last dim is not K");
+    std::vector<float> w((size_t)(N * K));
+    for (int64_t n = 0; n < N; ++n)
+      for (int64_t b = 0; b < kb; ++b) {
+        const double sv = sc->c.f[n * kb + b];
+        const int z = zp ? (int)((zp->c.i[n * zpb + b / 2] >> ((b & 1) * 4)) & 15) : 8;
+        for (int64_t j = 0; j < bs && b * bs + j < K; ++j) {
+          const int q = (int)((bq->c.i[(n * kb + b) * blob + j / 2] >> ((j & 1) * 4)) & 15);
+          float v = (float)((double)(q - z) * sv);
+          if (sc->c.f16) v = round_half(v);
+          w[n * K + b * bs + j] = v;
+        }
+      }
+    GemmParams p{};
+    p.alpha = 1.f;
+    p.beta = 1.f;
+    p.batch = 1;
+    p.K = (int)K;
+    p.N = (int)N;
+    p.M = (int)(a->numel() / K);
+    p.sam = K; p.sak = 1;
+    p.sbn = K; p.sbk = 1;  // W stored [N][K]
+    p.a = operand(*a);
+    p.b = upload_vec(w);
+    if (bias) {
+      if (bias->c.numel() != N) return fail("MatMulNBits '" + nd.name + "': bias must have N elements");
+      p.c = operand(*bias);
+      p.scm = 0; p.scn = 1;
+    }
+    if (!p.a || !p.b || (bias && !p.c)) return false;
+    std::vector<int64_t> os(a->shape.begin(), a->shape.end() - 1);
+    os.push_back(N);
+    return emit_gemm(ni, nd, p, os, false);
+  }
+
+  // ---- the walk ------------------------------------------------------------
+  static std::vector<Operand> operands(const Ins& in) {
+    std::vector<Operand> o;
+    for (const Value* v : in) o.push_back(v ? Operand{&v->shape, v->is_const ? &v->c : nullptr} : Operand{});
+    return o;
+  }
+
+  using PlanOp = bool (Planner::*)(size_t, const Node&, Ins&);
+  static PlanOp plan_of(const std::string& op) {
+    static const std::map<std::string, PlanOp> ops = {
+        {"Conv", &Planner::plan_conv},
+        {"Reshape", &Planner::plan_view}, {"Flatten", &Planner::plan_view},
+        {"Squeeze", &Planner::plan_view}, {"Unsqueeze", &Planner::plan_view},
+        {"Identity", &Planner::plan_alias}, {"Dropout", &Planner::plan_alias}, {"Cast", &Planner::plan_cast},
+        {"Relu", &Planner::plan_activation}, {"Clip", &Planner::plan_activation},
+        {"PRelu", &Planner::plan_activation}, {"LeakyRelu", &Planner::plan_activation},
+        {"Sigmoid", &Planner::plan_activation}, {"Tanh", &Planner::plan_activation},
+        {"Add", &Planner::plan_arith}, {"Sub", &Planner::plan_arith},
+        {"Mul", &Planner::plan_arith}, {"Div", &Planner::plan_arith},
+        {"MaxPool", &Planner::plan_pool}, {"AveragePool", &Planner::plan_pool},
+        {"GlobalAveragePool", &Planner::plan_global_pool},
+        {"InstanceNormalization", &Planner::plan_instance_norm},
+        {"BatchNormalization", &Planner::plan_batch_norm},
+        {"Softmax", &Planner::plan_softmax}, {"Transpose", &Planner::plan_transpose}, {"Pad", &Planner::plan_pad},
+        {"Concat", &Planner::plan_concat}, {"Split", &Planner::plan_split}, {"Slice", &Planner::plan_slice},
+        {"Resize", &Planner::plan_resize}, {"Upsample", &Planner::plan_resize},
+        {"Gemm", &Planner::plan_gemm}, {"MatMul", &Planner::plan_matmul},
+        {"MatMulNBits", &Planner::plan_matmul_nbits}};
+    auto it = ops.find(op);
+    return it == ops.end() ? nullptr : it->second;
+  }
+
+  // input resolution, then: a constant node is folded on the host, a runtime
+  // node goes to its operator's plan
+  bool plan_node(size_t ni) {
+    const Node& nd = g.nodes[ni];
+    const std::string& op = nd.op;
+    Ins in;
+    bool all_const = true;
+    for (const std::string& n : nd.in) {
+      if (n.empty()) { in.push_back(nullptr); continue; }
+      Value* v = val(n);
+      if (!v) return fail("node '" + nd.name + "' (" + op + "): input '" + n + "' is not defined");
+      in.push_back(v);
+      all_const = all_const && v->is_const;
+    }
+    if (op != "Conv" && op != "Concat")
+      for (const std::string& n : nd.in) flush_up(n);
+    if (op == "Shape" || (all_const && !in.empty() && op != "Conv") || op == "Constant") {
+      Const r;
+      if (!fold(nd, operands(in), &r, &err)) return false;
+      set_const(nd.out[0], r);
+      return true;
+    }
+    const PlanOp plan = plan_of(op);
+    if (!plan) return fail("unsupported operator " + op + " (node '" + nd.name + "')");
+    return (this->*plan)(ni, nd, in);
+  }
+
+  bool run(const std::vector<std::vector<int64_t>>& in_shapes) {
+    for (const Node& nd : g.nodes)
+      for (const std::string& i : nd.in)
+        if (!i.empty()) consumers[i]++;
+    for (auto& kv : g.inits) set_const(kv.first, kv.second);
+    for (size_t k = 0; k < g.inputs.size(); ++k) {
+      if (!set_runtime(g.inputs[k].name, in_shapes[k])) return false;
+      s->in_names.push_back(g.inputs[k].name);
+      s->in_shapes.push_back(in_shapes[k]);
+      s->in_bufs.push_back(vals[g.inputs[k].name].buf);
+    }
+    find_residual_fusions();
+    find_ibnorm();
+    find_concat_direct();
+    if (s->conv_precision != PREC_F32) find_up_fusions();
+    for (size_t k = 0; k < g.nodes.size(); ++k) {
+      if (done.count(k)) continue;
+      if (!plan_node(k)) return false;
+    }
+    if (!up_pending.empty()) return fail("internal: Resize '" + up_pending.begin()->first + "' never launched");
+    if (!cat_tail.empty()) return fail("internal: Concat input copy into '" + cat_tail.begin()->first + "' never launched");
+    if (!norm_pending.empty()) return fail("internal: InstanceNorm of '" + norm_pending.begin()->first + "' never applied");
+    if (!pending_dw.empty()) return fail("internal: depthwise Conv into '" + pending_dw.begin()->first + "' never computed");
+    for (const IO& o : g.outputs) {
+      Value* v = val(o.name);
+      if (!v) return fail("graph output '" + o.name + "' is never produced");
+      if (v->is_const) {  // a constant output: materialise it once
+        const float* d = upload(v->c);
+        if (!d) return false;
+        const int b = new_buf(v->c.numel());
+        if (b < 0) return false;
+        if (hipMemcpy(s->bufs[b], d, v->c.numel() * 4, hipMemcpyDeviceToDevice) != hipSuccess)
+          return fail("constant output copy failed");
+        v->buf = b;
+      }
+      s->out_names.push_back(o.name);
+      s->out_shapes.push_back(v->shape);
+      s->out_bufs.push_back(v->buf);
+    }
+    return true;
+  }
+};
+
+}  // namespace
+
+bool plan_session(vso_session* s, Graph& g, const std::vector<std::vector<int64_t>>& in_shapes, std::string* err) {
+  Planner pl{s, g};
+  const bool ok = pl.run(in_shapes);
+  *err = pl.err;
+  return ok;
+}
