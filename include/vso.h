@@ -16,9 +16,10 @@
  * residual adds fused into the convolution epilogues), replayed from a
  * hipGraph.  Tensors are float32 NCHW.
  *
- * Supported operators: Conv, Relu, PRelu, LeakyRelu, Clip, Sigmoid, Tanh,
- * Add, Sub, Mul, Div (numpy broadcasting), MaxPool, AveragePool,
- * GlobalAveragePool, Pad (constant), Concat, Split, Slice, Transpose,
+ * Supported operators: Conv, ConvTranspose, Relu, PRelu, LeakyRelu, Clip,
+ * Sigmoid, Tanh, HardSigmoid, HardSwish, Add, Sub, Mul, Div (numpy
+ * broadcasting), MaxPool, AveragePool, GlobalAveragePool, ReduceMean (over H
+ * and W), Pad (constant), Concat, Split, Slice, Transpose,
  * Reshape, Flatten, Squeeze, Unsqueeze, Identity, Dropout, Cast (float),
  * Resize/Upsample (nearest, linear; half_pixel, pytorch_half_pixel,
  * align_corners, asymmetric), InstanceNormalization, BatchNormalization,
@@ -31,7 +32,8 @@
  * points, bias; dequantised once at create).  Anything else fails vso_create
  * with VSO_E_UNSUPPORTED naming the node.
  *
- * Attributes (tests/op_cases.py is the table the sessions are held to):
+ * Attributes (tests/op_cases.py and tests/op_cases_deconv.py are the tables
+ * the sessions are held to):
  *   opset_import          read; it selects Softmax's form and Split's default.
  *   Conv                  2-D, constant weights and bias; group, strides,
  *                         dilations (0 or 2 values each), pads (0 or 4 values),
@@ -39,6 +41,48 @@
  *                         from the weights.  Refused: any other list length,
  *                         channels that do not match the weights and group, an
  *                         empty output.
+ *   ConvTranspose         2-D: X [N,C,H,W], constant W [C, M/group, kh, kw] and
+ *                         optional constant B [M]; group, strides, dilations,
+ *                         output_padding (0 or 2 values each), pads (0 or 4
+ *                         values), auto_pad, output_shape (2 values);
+ *                         kernel_shape is taken from the weights.  Per axis
+ *                         Ho = s (H - 1) + output_padding + (k - 1) d + 1 -
+ *                         pad_begin - pad_end, and Y[n, g Mg + m, oy, ox] = B +
+ *                         the sum over the group's c and ky, kx of X[n, c, iy,
+ *                         ix] W[c, m, ky, kx] with oy = iy s + ky d - pad_begin.
+ *                         With output_shape (it wins over pads) or auto_pad
+ *                         SAME_UPPER / SAME_LOWER (the output is H s) the total
+ *                         padding is derived from the size and split as the
+ *                         ONNX operator text says — SAME_UPPER: total / 2 at the
+ *                         beginning, otherwise total - total / 2 — which matters
+ *                         for an odd total only; PyTorch has no such attribute
+ *                         to compare with: the operator text is the authority.
+ *                         VALID: zero pads.  Refused: runtime weights, channels
+ *                         that do not match the weights and group, an
+ *                         output_padding not below max(stride, dilation) on its
+ *                         axis, negative pads (given or derived), any other
+ *                         list length, an empty output, tensors of 2^31
+ *                         elements or more, a stride, dilation or kernel side
+ *                         above 1024.  Computed on f32 operands in every
+ *                         session: conv_precision does not round it (as the
+ *                         1x1, grouped and inverted-residual convolutions).
+ *                         It absorbs a following BatchNormalization, residual
+ *                         Add and activation as Conv does.  Stride 1 runs as
+ *                         the Conv it equals (flipped weights, pads d (k - 1) -
+ *                         pads); other strides as one stride-1 correlation per
+ *                         output phase (vso_deconv.hip), see below.
+ *   HardSigmoid           alpha (0.2), beta (0.5): max(0, min(1, alpha x + beta)).
+ *   HardSwish             x max(0, min(1, x / 6 + 0.5)).  Both run in the
+ *                         epilogue of a producing Conv, ConvTranspose, Gemm or
+ *                         MatMul; so does Mul(x, HardSigmoid(x)), the
+ *                         hard-swish of exports before opset 14, for any alpha
+ *                         and beta, when that Mul is the HardSigmoid's only
+ *                         consumer (one activation, x clamp(alpha x + beta)).
+ *   ReduceMean            rank-4 input; axes (attribute, or constant input from
+ *                         opset 18) exactly the two spatial axes, negative
+ *                         forms accepted; keepdims 0 or 1;
+ *                         noop_with_empty_axes.  Runs on GlobalAveragePool's
+ *                         kernels.  Refused: every other axis set or rank.
  *   MaxPool, AveragePool  kernel_shape, strides, dilations, pads (0 or 4
  *                         values), auto_pad, ceil_mode, count_include_pad: the
  *                         divisor is the window's taps inside the padded input
@@ -180,6 +224,18 @@ int vso_tile_conv_count(const vso_session* s);
  * launches; VSO_IR_B16=0 keeps the f32 form in 16-bit sessions; VSO_IR_CPS
  * (default 6) hidden 16-channel chunks per slice of a 16-bit block. */
 int vso_ir_block_count(const vso_session* s);
+/* ConvTranspose at a stride above 1 (vso_deconv.hip): per output phase
+ * ((oy + pad) mod stride, per axis) one stride-1 correlation over the taps
+ * ky = phase + j stride, 1 / (sh sw) of the zero-stuffed form's multiply-adds.
+ * k_deconv_tile — group 1, dilation 1, at least 16 input and 16 output
+ * channels, at most 4 taps per phase and axis: an implicit GEMM per phase on
+ * v_mfma_f32_16x16x4_f32 (exact f32 products); at stride 2 in x with 1024
+ * workgroups or more both x phases come from one workgroup and rows are stored
+ * contiguous (k_deconv_tile<2>, else <1>).  k_deconv_direct — groups
+ * (depthwise), dilations, thin channel counts (a one-channel matte head), and
+ * stride 1 with pads beyond d (k - 1): a gather on the VALU.  Planning knobs,
+ * read once per process: VSO_DECONV_TILE=0 plans every one on k_deconv_direct;
+ * VSO_DECONV_PAIR=0 / 1 forces k_deconv_tile<1> / <2> at stride 2 in x. */
 /* Lanes of the captured graph (0 before the first run): launches that share no
  * activation buffer run on two capture streams, so independent branches of
  * the model (MODNet's HR branch beside its backbone) execute concurrently —

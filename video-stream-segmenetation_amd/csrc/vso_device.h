@@ -45,6 +45,8 @@ __device__ __forceinline__ float act_apply(float v, int act, float a0, float a1,
     case ACT_SIGMOID: return 1.f / (1.f + expf(-v));
     case ACT_TANH: return tanhf(v);
     case ACT_F16: return __half2float(__float2half_rn(v));
+    case ACT_HSIGMOID: return fminf(fmaxf(__builtin_fmaf(a0, v, a1), 0.f), 1.f);
+    case ACT_HSWISH: return v * fminf(fmaxf(__builtin_fmaf(a0, v, a1), 0.f), 1.f);
     default: return v;
   }
 }

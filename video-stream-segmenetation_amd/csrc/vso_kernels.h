@@ -13,13 +13,15 @@ constexpr int kMaxDims = 6;
 
 // Activations fused into the producing kernel's epilogue (and the unary kernel).
 enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_CLIP = 2, ACT_PRELU = 3, ACT_LEAKY = 4, ACT_SIGMOID = 5, ACT_TANH = 6,
-                 ACT_F16 = 7 /* Cast to float16: round to the nearest half (ties to even), kept as f32 */ };
+                 ACT_F16 = 7 /* Cast to float16: round to the nearest half (ties to even), kept as f32 */,
+                 ACT_HSIGMOID = 8 /* HardSigmoid: clamp(a0 * x + a1, 0, 1) */,
+                 ACT_HSWISH = 9 /* x * clamp(a0 * x + a1, 0, 1): HardSwish (a0 1/6, a1 0.5), Mul(x, HardSigmoid(x)) */ };
 
 struct Epilogue {
   const float* bias;   // [M] or null
   const float* res;    // residual added before the activation (same layout as y) or null
   int act;             // Act
-  float a0, a1;        // CLIP lo/hi, LEAKY alpha
+  float a0, a1;        // CLIP lo/hi, LEAKY alpha, HSIGMOID / HSWISH alpha/beta
   const float* slope;  // PRELU: per output channel ([M]) or one value (slope_stride 0)
   int slope_stride;
   // res_mode 1: res is [N][res_c][Ho][Wo], channels >= res_c add 0 (an ONNX Pad
@@ -254,6 +256,52 @@ void ir_tiles(int Ho, int Wo, int* tiles_x, int* tiles);
 const char* ir_kernel_name(const IrParams& p);
 void launch_ir(const IrParams& p, hipStream_t s);
 void launch_ir_reduce(const IrParams& p, hipStream_t s);  // ks > 1: the launch after launch_ir
+
+// ConvTranspose at stride > 1 (vso_deconv.hip).  A transposed convolution of
+// stride s is sh * sw stride-1 correlations, one per output phase: with
+// t = oy + pt, py = t mod sh and q = t div sh, the taps of phase py are the ky
+// with (ky * dh) mod sh == py, and tap ky reads input row q - (ky * dh) div sh;
+// likewise in x.  Every phase runs over the same grid of q: rows qy0 ..
+// qy0 + Qh - 1, columns qx0 .. qx0 + Qw - 1 (outputs outside [0, Ho) x [0, Wo)
+// are not written).  Two kernels:
+//  * k_deconv_tile — group 1, dilation 1, at most kDeconvMaxTaps taps per
+//    phase and axis: an implicit GEMM per phase on v_mfma_f32_16x16x4_f32
+//    (exact f32 products).  A workgroup owns one image, one phase, a
+//    kDeconvTH x 16 tile of the phase's pixels (a wave per row) and
+//    kDeconvBM output channels; the input channels go in chunks of 16, each
+//    chunk's region (tile + taps - 1 rows and columns, zero outside the image)
+//    staged in LDS.  At sw == 2 the workgroup computes both x phases from one
+//    region (k_deconv_tile<2>: a lane holds two neighbouring outputs, rows go
+//    out contiguous); otherwise one phase (k_deconv_tile<1>).  w: packed [phase][tap jy * tmx + jx][Mp][Cp], tap (jy, jx)
+//    of phase (py, px) being W[c][m][py + jy * sh][px + jx * sw], zero padded.
+//  * k_deconv_direct — any group, dilation and channel count: a VALU gather,
+//    kDeconvPx consecutive pixels of one phase row per thread, over the
+//    phase's taps (`taps`, enumerated by the planner) x the group's channels.
+//    w: the node's [C][Mg][kh][kw].
+constexpr int kDeconvTH = 4, kDeconvBM = 64, kDeconvMaxTaps = 4, kDeconvPx = 4;
+struct DeconvParams {
+  const float* x;  // [N][C][H][W]
+  const float* w;
+  float* y;        // [N][M][Ho][Wo], image n at y + n * (M * Ho * Wo + y_nx)
+  long y_nx;
+  int N, C, H, W, M, Ho, Wo;
+  int G, Cg, Mg;
+  int kh, kw, sh, sw, dh, dw, pt, pl;
+  int qy0, qx0, Qh, Qw;
+  Epilogue ep;
+  // direct: ints [sh + 1] first tap of each y phase, [kh][2] (ky, rows back) by
+  // phase, [sw + 1], [kw][2] likewise in x; o_*: where each part starts
+  const int* taps;
+  int o_yt, o_xs, o_xt;
+  // tile: padded channels, the most taps of a phase per axis, pixel tiles per
+  // row of tiles / per image, floats between the staged region's rows / channels
+  int Mp, Cp, tmy, tmx, tiles_x, tiles, pitch, plane;
+  int sx;  // x phases per workgroup: 2 (sw == 2: both, rows stored contiguous) or 1
+};
+const char* deconv_tile_name(const DeconvParams& p);
+void launch_deconv_tile(const DeconvParams& p, hipStream_t s);
+void launch_deconv_direct(const DeconvParams& p, hipStream_t s);
+size_t deconv_tile_lds(const DeconvParams& p);
 
 const char* conv_kernel_name(const ConvParams& p);
 // a depthwise -> 1x1 pair of N images of P pixels into M channels runs fused

@@ -9,8 +9,10 @@
 //    weight reshapes) are evaluated on the host (vso_fold.cpp);
 //  * Reshape / Flatten / Squeeze / Unsqueeze / Identity alias their input;
 //  * Conv absorbs a following BatchNormalization (weights folded), residual
-//    Add and activation (Relu, Clip, PRelu, LeakyRelu, Sigmoid, Tanh) into
-//    one launch when each intermediate has exactly one consumer;
+//    Add and activation (Relu, Clip, PRelu, LeakyRelu, Sigmoid, Tanh,
+//    HardSigmoid, HardSwish, and Mul(x, HardSigmoid(x)) as one) into one
+//    launch when each intermediate has exactly one consumer; a ConvTranspose
+//    absorbs them the same way (plan_conv_transpose);
 //  * the fusions found before planning (find_*): IBNorm, strided residuals,
 //    Concat inputs written in place, 2x upsamples computed by their consumer;
 //  * every other runtime node is one launch, by the plan_<op> of its operator.
@@ -68,6 +70,13 @@ struct Planner {
   // 2x linear Resizes that may be computed inside their consumer convolution
   // (k_conv_tile_up), by graph structure (find_up_fusions)
   std::set<std::string> up_cand;
+
+  // The hard-swish of exports before opset 14, Mul(x, HardSigmoid(x)) with the
+  // HardSigmoid used by that Mul only: HardSigmoid node -> Mul node
+  // (find_hswish).  The pair is one activation, x * clamp(alpha x + beta, 0, 1):
+  // in the epilogue of x's producer when the two are all that reads x
+  // (hswish_pair), else one k_unary launch (plan_activation).
+  std::map<size_t, size_t> hswish;
 
   // ---- work left by one node to a later one, by value name -----------------
   // Each entry is set by the producer's plan and cleared by the consumer that
@@ -302,7 +311,42 @@ struct Planner {
     }
   }
 
+  void find_hswish() {
+    for (size_t k = 0; k < g.nodes.size(); ++k) {
+      const Node& hs = g.nodes[k];
+      if (hs.op != "HardSigmoid" || hs.in.size() != 1 || hs.out.empty() || g.inits.count(hs.in[0])) continue;
+      const int m = sole_consumer(hs.out[0], k);
+      if (m < 0 || g.nodes[m].op != "Mul" || g.nodes[m].in.size() != 2) continue;
+      const Node& mul = g.nodes[m];
+      const std::string& other = mul.in[0] == hs.out[0] ? mul.in[1] : mul.in[0];
+      if (other == hs.in[0]) hswish[k] = (size_t)m;
+    }
+  }
+
+  // `out` (a launch's output so far, written by node `last`) is read by a
+  // decomposed hard-swish and by nothing else: the activation into *ep, the
+  // HardSigmoid marked done; returns the Mul for the caller to absorb, or -1
+  int hswish_pair(const std::string& out, size_t last, Epilogue* ep) {
+    if (hswish.empty() || consumers[out] != 2) return -1;
+    for (const IO& o : g.outputs)
+      if (o.name == out) return -1;
+    for (auto& kv : hswish) {
+      const Node& hs = g.nodes[kv.first];
+      if (kv.first <= last || hs.in[0] != out || done.count(kv.first) || done.count(kv.second)) continue;
+      if (!act_of(hs, ep, 0)) return -1;
+      ep->act = ACT_HSWISH;
+      done.insert(kv.first);
+      return (int)kv.second;
+    }
+    return -1;
+  }
+
   // ---- the A/B knobs that change a plan ------------------------------------
+  // VSO_DECONV_TILE=0: every strided ConvTranspose on k_deconv_direct
+  static bool deconv_tile_enabled() { static const bool on = env_on("VSO_DECONV_TILE"); return on; }
+  // VSO_DECONV_PAIR=0 / 1: k_deconv_tile<1> (one x phase per workgroup, strided stores) / <2> (both, rows
+  // stored contiguous) for every sw == 2 layer; unset: <2> from kDeconvPairMinWgs of its workgroups on
+  static long deconv_pair() { static const long v = env_int("VSO_DECONV_PAIR", -1); return v; }
   // VSO_CAT_TAIL=0: every Concat input not written in place is copied
   static bool cat_tail_enabled() { static const bool on = env_on("VSO_CAT_TAIL"); return on; }
   // VSO_GEMM_ACT=0: a Gemm / MatMul's activation as its own launch
@@ -430,7 +474,8 @@ struct Planner {
 
   // ---- graph queries -------------------------------------------------------
   static bool is_act(const std::string& op) {
-    return op == "Relu" || op == "Clip" || op == "PRelu" || op == "LeakyRelu" || op == "Sigmoid" || op == "Tanh";
+    return op == "Relu" || op == "Clip" || op == "PRelu" || op == "LeakyRelu" || op == "Sigmoid" || op == "Tanh" ||
+           op == "HardSigmoid" || op == "HardSwish";
   }
 
   // the single node consuming `name`, if exactly one and `name` is no graph output
@@ -457,6 +502,8 @@ struct Planner {
     else if (nd.op == "Sigmoid") ep->act = ACT_SIGMOID;
     else if (nd.op == "Tanh") ep->act = ACT_TANH;
     else if (nd.op == "LeakyRelu") { ep->act = ACT_LEAKY; ep->a0 = nd.af("alpha", 0.01f); }
+    else if (nd.op == "HardSigmoid") { ep->act = ACT_HSIGMOID; ep->a0 = nd.af("alpha", 0.2f); ep->a1 = nd.af("beta", 0.5f); }
+    else if (nd.op == "HardSwish") { ep->act = ACT_HSWISH; ep->a0 = 1.f / 6.f; ep->a1 = 0.5f; }
     else if (nd.op == "Clip") {
       float lo = nd.af("min", -INFINITY), hi = nd.af("max", INFINITY);
       if (nd.in.size() > 1 && !nd.in[1].empty()) { Value* v = val(nd.in[1]); if (!v || !v->is_const) return false; lo = v->c.f[0]; }
@@ -794,6 +841,10 @@ struct Planner {
       }
     }
     if (c1 >= 0 && is_act(g.nodes[c1].op) && act_of(g.nodes[c1], &ep, p.M)) absorb(c, c1, &c1);
+    else if (c1 < 0 && !c->ib && ep.act == ACT_NONE) {
+      const int mul = hswish_pair(c->out, c->last, &ep);
+      if (mul >= 0) absorb(c, mul, &c1);
+    }
     return err.empty();
   }
 
@@ -887,7 +938,7 @@ struct Planner {
     }
     if (!c.ib && thin_conv_fits(p) && p.C <= kThinMaxC && thin_enabled()) return plan_conv_thin(in0, c);
     flush_norm(in0);  // (a pending InstanceNorm apply step: not taken here)
-    if (!plan_conv_dense(in0, c)) return false;
+    if (!plan_conv_dense(in0, c, s->conv_precision)) return false;
     if (!c.ib) return true;
     const Node& inn = g.nodes[c.ib->inorm];
     const std::string* direct = cat_direct.count(c.out) ? &c.out : nullptr;
@@ -920,12 +971,12 @@ struct Planner {
   // of its input, or of one Concat input, computed while staging, and a
   // Concat's tail read in place), else the generic kernels (launch_conv)
   static constexpr double kTileMinMacs = 8e6;  // f32: smaller convs keep k_conv_small / k_conv_gemm
-  bool plan_conv_dense(const std::string& in0, const ConvPlan& c) {
+  // (prec: the session's conv_precision; PREC_F32 for a lowered ConvTranspose)
+  bool plan_conv_dense(const std::string& in0, const ConvPlan& c, int prec) {
     const ConvParams& p = c.p;
     ConvTileShape ts{};
     const double macs = (double)p.N * p.M * p.Ho * p.Wo * p.Cg * p.kh * p.kw;
-    const bool tile = !p.pre.w && conv_tile_shape(p, s->conv_precision, &ts) &&
-                      (s->conv_precision != PREC_F32 || macs >= kTileMinMacs);
+    const bool tile = !p.pre.w && conv_tile_shape(p, prec, &ts) && (prec != PREC_F32 || macs >= kTileMinMacs);
     std::vector<UpRange> ups;
     if (up_pending.count(in0)) ups.push_back({in0, 0, p.C});
     else if (cat_up.count(in0)) ups = cat_up[in0];
@@ -939,7 +990,7 @@ struct Planner {
         ts.prec != PREC_F32 && ups[0].c0 % 32 == 0 && ups[0].c1 % 32 == 0 && up_fuse_enabled()) {
       ConvTileShape tu{};
       tu.up = 1;
-      if (conv_tile_shape(p, s->conv_precision, &tu)) {
+      if (conv_tile_shape(p, prec, &tu)) {
         up = up_pending[ups[0].name].get();
         ts = tu;
       }
@@ -1024,6 +1075,203 @@ struct Planner {
     return true;
   }
 
+  // ---- ConvTranspose -------------------------------------------------------
+  // Geometry of a ConvTranspose node (include/vso.h: the attribute table) into
+  // the ConvPlan of the stride-1 Conv it would equal at stride 1 — weights
+  // [M][Cg][kh][kw], flipped in both spatial axes, C and M exchanged within
+  // each group, pads d (k - 1) - pads — with the node's strides in *sh / *sw
+  // (c->p.sh / sw stay 1: conv_absorb and a lowered Conv read the plan).
+  bool deconv_geometry(const Node& nd, Ins& in, ConvPlan* c, int* sh, int* sw) {
+    const std::string who = "ConvTranspose '" + nd.name + "'";
+    Value *x = in[0], *w = in.size() > 1 ? in[1] : nullptr, *b = in.size() > 2 ? in[2] : nullptr;
+    if (!w || !w->is_const) return fail(who + ": weights must be constant");
+    if (x->shape.size() != 4 || w->c.dims.size() != 4) return fail(who + ": 2D only");
+    ConvParams& p = c->p;
+    p.N = (int)x->shape[0]; p.C = (int)x->shape[1]; p.H = (int)x->shape[2]; p.W = (int)x->shape[3];
+    p.G = (int)nd.ai("group", 1);
+    p.Mg = (int)w->c.dims[1]; p.kh = (int)w->c.dims[2]; p.kw = (int)w->c.dims[3];
+    if (p.G < 1 || w->c.dims[0] != p.C || p.C % p.G) return fail(who + ": channel/group mismatch");
+    p.Cg = p.C / p.G;
+    p.M = p.Mg * p.G;
+    const std::vector<int64_t> st = nd.ais("strides"), dl = nd.ais("dilations"), pd = nd.ais("pads"),
+                               op = nd.ais("output_padding"), osz = nd.ais("output_shape");
+    if (!st.empty() && st.size() != 2) return fail(who + ": strides must have 2 values");
+    if (!dl.empty() && dl.size() != 2) return fail(who + ": dilations must have 2 values");
+    if (!op.empty() && op.size() != 2) return fail(who + ": output_padding must have 2 values");
+    if (!pd.empty() && pd.size() != 4) return fail(who + ": pads must have 4 values");
+    if (!osz.empty() && osz.size() != 2) return fail(who + ": output_shape must have 2 values");
+    const int64_t in_[2] = {p.H, p.W}, k[2] = {p.kh, p.kw};
+    int64_t s[2], d[2], opad[2], pb[2], pe[2], out[2];
+    const std::string ap = nd.as("auto_pad", "NOTSET");
+    if (ap != "NOTSET" && ap != "VALID" && ap != "SAME_UPPER" && ap != "SAME_LOWER")
+      return fail(who + ": auto_pad " + ap);
+    for (int a = 0; a < 2; ++a) {
+      s[a] = st.empty() ? 1 : st[a];
+      d[a] = dl.empty() ? 1 : dl[a];
+      opad[a] = op.empty() ? 0 : op[a];
+      if (s[a] < 1 || d[a] < 1) return fail(who + ": strides and dilations must be positive");
+      if (s[a] > 1024 || d[a] > 1024 || k[a] > 1024) return fail(who + ": strides, dilations and kernels up to 1024 only");
+      if (opad[a] < 0 || opad[a] >= std::max(s[a], d[a]))
+        return fail(who + ": output_padding must be below max(stride, dilation)");
+      const int64_t full = s[a] * (in_[a] - 1) + opad[a] + (k[a] - 1) * d[a] + 1;  // the unpadded output
+      const bool same = ap == "SAME_UPPER" || ap == "SAME_LOWER";
+      if (!osz.empty() || same) {
+        // ONNX's ConvTranspose text: the total padding from the wanted size, then
+        // split — SAME_UPPER: total / 2 at the beginning; otherwise at the end
+        const int64_t total = full - (osz.empty() ? in_[a] * s[a] : osz[a]);
+        if (total < 0) return fail(who + ": the output size asks for negative pads");
+        pb[a] = ap == "SAME_UPPER" ? total / 2 : total - total / 2;
+        pe[a] = total - pb[a];
+      } else {
+        pb[a] = pd.empty() || ap == "VALID" ? 0 : pd[a];
+        pe[a] = pd.empty() || ap == "VALID" ? 0 : pd[a + 2];
+        if (pb[a] < 0 || pe[a] < 0) return fail(who + ": pads must not be negative");
+      }
+      out[a] = full - pb[a] - pe[a];
+      if (out[a] < 1) return fail(who + ": empty output");
+    }
+    // (the kernels' plane and tensor offsets are int where the neighbouring convolution kernels' are)
+    if ((int64_t)p.N * p.M * out[0] * out[1] >= (1LL << 31) || x->numel() >= (1LL << 31))
+      return fail(who + ": tensors below 2^31 elements only");
+    *sh = (int)s[0]; *sw = (int)s[1];
+    p.sh = p.sw = 1;
+    p.dh = (int)d[0]; p.dw = (int)d[1];
+    p.pt = (int)(d[0] * (k[0] - 1) - pb[0]);
+    p.pl = (int)(d[1] * (k[1] - 1) - pb[1]);
+    p.Ho = (int)out[0]; p.Wo = (int)out[1];
+    c->oshape = {p.N, p.M, p.Ho, p.Wo};
+    const int taps = p.kh * p.kw;
+    c->wf.assign((size_t)p.M * p.Cg * taps, 0.f);
+    for (int gi = 0; gi < p.G; ++gi)
+      for (int ch = 0; ch < p.Cg; ++ch)
+        for (int m = 0; m < p.Mg; ++m)
+          for (int t = 0; t < taps; ++t)
+            c->wf[((size_t)(gi * p.Mg + m) * p.Cg + ch) * taps + (taps - 1 - t)] =
+                w->c.f[((size_t)(gi * p.Cg + ch) * p.Mg + m) * taps + t];
+    c->bias.assign(p.M, 0.f);
+    if (b) {
+      if (!b->is_const || b->c.numel() != p.M) return fail(who + ": bias must be constant [M]");
+      c->bias = b->c.f;
+      c->has_bias = true;
+    }
+    return true;
+  }
+
+  // ConvTranspose.  Stride 1: the Conv above on the convolution planner, f32
+  // operands in every session.  Otherwise the phase decomposition
+  // (vso_kernels.h, DeconvParams): k_deconv_tile for group 1, dilation 1, at
+  // least kDeconvMinC channels on both sides and at most kDeconvMaxTaps taps
+  // per phase and axis; k_deconv_direct for the rest, and for a stride-1 node
+  // whose pads exceed d (k - 1) (the Conv's would be negative).
+  static constexpr int kDeconvMinC = 16;
+  static constexpr long kDeconvPairMinWgs = 1024;
+  bool plan_conv_transpose(size_t ni, const Node& nd, Ins& in) {
+    const std::string& in0 = nd.in[0];
+    ConvPlan c;
+    int sh = 1, sw = 1;
+    if (!deconv_geometry(nd, in, &c, &sh, &sw) || !conv_absorb(ni, &c)) return false;
+    flush_input(in0);
+    flush_norm(in0);
+    ConvParams& cp = c.p;
+    cp.ep.bias = c.has_bias ? upload_vec(c.bias) : nullptr;
+    if (c.has_bias && !cp.ep.bias) return false;
+    cp.x = dptr(*in[0]);
+    if (sh == 1 && sw == 1 && cp.pt >= 0 && cp.pl >= 0) {
+      cp.w = upload_vec(c.wf);
+      if (!cp.w || !(cp.y = make_out(c.out, c.oshape))) return false;
+      return plan_conv_dense(in0, c, PREC_F32);
+    }
+    DeconvParams p{};
+    p.x = cp.x;
+    p.N = cp.N; p.C = cp.C; p.H = cp.H; p.W = cp.W; p.M = cp.M; p.Ho = cp.Ho; p.Wo = cp.Wo;
+    p.G = cp.G; p.Cg = cp.Cg; p.Mg = cp.Mg;
+    p.kh = cp.kh; p.kw = cp.kw; p.sh = sh; p.sw = sw; p.dh = cp.dh; p.dw = cp.dw;
+    p.pt = cp.dh * (cp.kh - 1) - cp.pt;  // the node's own pads again
+    p.pl = cp.dw * (cp.kw - 1) - cp.pl;
+    p.ep = cp.ep;
+    // the phase grid: q = (o + pad) div stride over the outputs of every phase
+    p.qy0 = p.pt / sh; p.Qh = (p.Ho - 1 + p.pt) / sh - p.qy0 + 1;
+    p.qx0 = p.pl / sw; p.Qw = (p.Wo - 1 + p.pl) / sw - p.qx0 + 1;
+    const int taps = p.kh * p.kw;
+    // c.wf (flipped, [M][Cg]) -> the node's W[c][mg][ky][kx], whatever conv_absorb folded in
+    auto w_at = [&](int ch, int m, int ky, int kx) {
+      const int gi = ch / p.Cg;
+      return c.wf[((size_t)(gi * p.Mg + m) * p.Cg + (ch - gi * p.Cg)) * taps + (taps - 1 - (ky * p.kw + kx))];
+    };
+    p.tmy = (p.kh + sh - 1) / sh;
+    p.tmx = (p.kw + sw - 1) / sw;
+    const long mblocks = (p.M + kDeconvBM - 1) / kDeconvBM;
+    const bool tile = deconv_tile_enabled() && p.G == 1 && p.dh == 1 && p.dw == 1 && p.C >= kDeconvMinC &&
+                      p.M >= kDeconvMinC && p.tmy <= kDeconvMaxTaps && p.tmx <= kDeconvMaxTaps &&
+                      (long)sh * sw * mblocks < 65536 && p.N < 65536;
+    const char* name;
+    void (*launch)(const DeconvParams&, hipStream_t);
+    if (tile) {
+      p.Mp = (int)mblocks * kDeconvBM;
+      p.Cp = (p.C + 15) / 16 * 16;
+      p.tiles_x = (p.Qw + 15) / 16;
+      p.tiles = p.tiles_x * ((p.Qh + kDeconvTH - 1) / kDeconvTH);
+      p.pitch = 16 + p.tmx - 1;
+      // channels 4 apart in banks 16 apart: the MFMA B reads of lanes (r, g) are conflict free
+      const int rows = (kDeconvTH + p.tmy - 1) * p.pitch;
+      p.plane = rows + ((4 - rows) % 8 + 8) % 8;
+      std::vector<float> wp((size_t)sh * sw * p.tmy * p.tmx * p.Mp * p.Cp, 0.f);
+      for (int py = 0; py < sh; ++py)
+        for (int px = 0; px < sw; ++px)
+          for (int jy = 0; py + jy * sh < p.kh; ++jy)
+            for (int jx = 0; px + jx * sw < p.kw; ++jx) {
+              float* dst = wp.data() + (size_t)(((py * sw + px) * p.tmy + jy) * p.tmx + jx) * p.Mp * p.Cp;
+              for (int m = 0; m < p.M; ++m)
+                for (int ch = 0; ch < p.C; ++ch) dst[(size_t)m * p.Cp + ch] = w_at(ch, m, py + jy * sh, px + jx * sw);
+            }
+      p.w = static_cast<const float*>(upload_bytes(wp.data(), wp.size() * 4, "conv weight upload failed"));
+      // both x phases per workgroup halve the workgroups: 10 % faster with 10064 of them (32 -> 16 k2 s2 at
+      // 144x256, batch 8), the same at 1258 and 2736, 14 % slower at 342 (64 -> 32 k4 s2 at 72x128, batch 1:
+      // 1.3 per CU) — profiles/NOTES.md, "ConvTranspose"
+      const long pair_wgs = (long)p.N * p.tiles * sh * mblocks;
+      p.sx = sw == 2 && (deconv_pair() < 0 ? pair_wgs >= kDeconvPairMinWgs : deconv_pair() != 0) ? 2 : 1;
+      name = deconv_tile_name(p);
+      launch = launch_deconv_tile;
+    } else {
+      std::vector<float> wd((size_t)p.C * p.Mg * taps);
+      for (int ch = 0; ch < p.C; ++ch)
+        for (int m = 0; m < p.Mg; ++m)
+          for (int ky = 0; ky < p.kh; ++ky)
+            for (int kx = 0; kx < p.kw; ++kx) wd[((size_t)ch * p.Mg + m) * taps + ky * p.kw + kx] = w_at(ch, m, ky, kx);
+      p.w = upload_vec(wd);
+      // per phase, its taps: k with (k d) mod s == phase, reading q - (k d) div s
+      std::vector<int> tab;
+      auto axis = [&](int kk, int ss, int dd) {
+        const size_t start = tab.size();
+        tab.resize(start + ss + 1 + 2 * (size_t)kk);
+        size_t at = start + ss + 1, n = 0;
+        for (int ph = 0; ph < ss; ++ph) {
+          tab[start + ph] = (int)n;
+          for (int q = 0; q < kk; ++q)
+            if ((q * dd) % ss == ph) {
+              tab[at + 2 * n] = q;
+              tab[at + 2 * n + 1] = (q * dd) / ss;
+              ++n;
+            }
+        }
+        tab[start + ss] = (int)n;
+      };
+      axis(p.kh, sh, p.dh);
+      p.o_yt = sh + 1;
+      p.o_xs = (int)tab.size();
+      axis(p.kw, sw, p.dw);
+      p.o_xt = p.o_xs + sw + 1;
+      p.taps = static_cast<const int*>(upload_bytes(tab.data(), tab.size() * sizeof(int)));
+      if (!p.taps) return false;
+      name = "vso::k_deconv_direct(vso::DeconvParams)";
+      launch = launch_deconv_direct;
+    }
+    if (!p.w || !(p.y = make_out(c.out, c.oshape))) return false;
+    auto pp = emit(name, p, launch);
+    retarget_on_concat(c.out, pp, p.M);
+    return true;
+  }
+
   // ---- the other operators: one plan_<op> each -----------------------------
   static void fill_strides(const std::vector<int64_t>& shape, std::vector<int64_t>* st) {
     st->assign(shape.size(), 1);
@@ -1048,12 +1296,13 @@ struct Planner {
     return set_runtime(nd.out[0], in[0]->shape, in[0]->buf);
   }
 
-  bool plan_unary(const Node& nd, Value& x, int act, float a0, float a1) {
+  bool plan_unary(const Node& nd, Value& x, int act, float a0, float a1, const std::string* out = nullptr) {
+    const std::string& o = out ? *out : nd.out[0];
     UnaryParams p{};
     p.x = dptr(x);
     p.act = act; p.a0 = a0; p.a1 = a1;
-    if (!(p.y = make_out(nd.out[0], x.shape))) return false;
-    p.n = vals[nd.out[0]].numel();
+    if (!(p.y = make_out(o, x.shape))) return false;
+    p.n = vals[o].numel();
     emit("vso::k_unary(vso::UnaryParams)", p, launch_unary);
     return true;
   }
@@ -1067,7 +1316,7 @@ struct Planner {
     return plan_alias(ni, nd, in);
   }
 
-  bool plan_activation(size_t, const Node& nd, Ins& in) {
+  bool plan_activation(size_t ni, const Node& nd, Ins& in) {
     const std::vector<int64_t>& xs = in[0]->shape;
     if (nd.op == "PRelu") {
       // unidirectional: the slope broadcasts to x, never x to the slope
@@ -1080,6 +1329,11 @@ struct Planner {
     }
     Epilogue ep{};
     if (!act_of(nd, &ep, 0)) return fail(nd.op + " '" + nd.name + "': non-constant parameters");
+    const auto hw = hswish.find(ni);
+    if (hw != hswish.end() && !done.count(hw->second)) {  // with its Mul: x * HardSigmoid(x), written as the Mul's output
+      done.insert(hw->second);
+      return plan_unary(nd, *in[0], ACT_HSWISH, ep.a0, ep.a1, &g.nodes[hw->second].out[0]);
+    }
     return plan_unary(nd, *in[0], ep.act, ep.a0, ep.a1);
   }
 
@@ -1236,6 +1490,32 @@ struct Planner {
     std::vector<int64_t> os = {xs[0], xs[1]};
     for (size_t d = 2; d < xs.size(); ++d) os.push_back(1);
     if (!(p.y = make_out(nd.out[0], os))) return false;
+    emit(gap_kernel_name(p), p, launch_gap);
+    return true;
+  }
+
+  // ReduceMean over exactly H and W of a rank-4 tensor: GlobalAveragePool's
+  // kernels; keepdims 0 is the same buffer seen as [N, C]
+  bool plan_reduce_mean(size_t ni, const Node& nd, Ins& in) {
+    const std::string who = "ReduceMean '" + nd.name + "'";
+    const std::vector<int64_t>& xs = in[0]->shape;
+    if (xs.size() != 4) return fail(who + ": rank-4 input only");
+    std::vector<int64_t> axes = nd.ais("axes");
+    if (in.size() > 1 && in[1]) {  // opset 18 on: an input
+      if (!in[1]->is_const) return fail(who + ": constant axes only");
+      axes = ints(*in[1]);
+    }
+    if (axes.empty() && nd.ai("noop_with_empty_axes", 0) != 0) return plan_alias(ni, nd, in);
+    for (int64_t& a : axes) a = a < 0 ? a + 4 : a;
+    std::sort(axes.begin(), axes.end());
+    if (axes != std::vector<int64_t>{2, 3}) return fail(who + ": the two spatial axes of an NCHW tensor only");
+    RowParams p{};
+    p.x = dptr(*in[0]);
+    p.rows = xs[0] * xs[1];
+    p.inner = xs[2] * xs[3];
+    const bool keep = nd.ai("keepdims", 1) != 0;
+    if (!(p.y = make_out(nd.out[0], keep ? std::vector<int64_t>{xs[0], xs[1], 1, 1} : std::vector<int64_t>{xs[0], xs[1]})))
+      return false;
     emit(gap_kernel_name(p), p, launch_gap);
     return true;
   }
@@ -1546,6 +1826,12 @@ struct Planner {
     if (c1 >= 0 && is_act(g.nodes[c1].op) && g.nodes[c1].op != "PRelu" && act_of(g.nodes[c1], &p.ep, p.N)) {
       done.insert((size_t)c1);
       out = g.nodes[c1].out[0];
+    } else if (c1 < 0 && absorb_act && gemm_act_enabled()) {
+      const int mul = hswish_pair(out, ni, &p.ep);
+      if (mul >= 0) {
+        done.insert((size_t)mul);
+        out = g.nodes[mul].out[0];
+      }
     }
     if (!(p.y = make_out(out, os))) return false;
     emit(gemm_kernel_name(p), p, launch_gemm);
@@ -1683,6 +1969,8 @@ struct Planner {
         {"Relu", &Planner::plan_activation}, {"Clip", &Planner::plan_activation},
         {"PRelu", &Planner::plan_activation}, {"LeakyRelu", &Planner::plan_activation},
         {"Sigmoid", &Planner::plan_activation}, {"Tanh", &Planner::plan_activation},
+        {"HardSigmoid", &Planner::plan_activation}, {"HardSwish", &Planner::plan_activation},
+        {"ConvTranspose", &Planner::plan_conv_transpose}, {"ReduceMean", &Planner::plan_reduce_mean},
         {"Add", &Planner::plan_arith}, {"Sub", &Planner::plan_arith},
         {"Mul", &Planner::plan_arith}, {"Div", &Planner::plan_arith},
         {"MaxPool", &Planner::plan_pool}, {"AveragePool", &Planner::plan_pool},
@@ -1736,6 +2024,7 @@ struct Planner {
       s->in_shapes.push_back(in_shapes[k]);
       s->in_bufs.push_back(vals[g.inputs[k].name].buf);
     }
+    find_hswish();
     find_residual_fusions();
     find_ibnorm();
     find_concat_direct();
