@@ -404,6 +404,18 @@ void vss_expand_frag_layout(int cin, int cout, int* out4);
 int vss_expand_frag_image(int cin, int chid, int cout, int h0, int cs, const float* w1, const float* b1,
                           const float* wdw, const float* bdw, const float* w2, void* out);
 
+/* Workgroup -> tile of a layer launch with grid (gx, gy, gz) (TileMap / tile_of
+ * in csrc/vss_kernels.h); no GPU needed.  The kernels divide by gx and gy with
+ * reciprocals the host computes once per launch list.  vss_tile_map: out6 =
+ * {gx, gy, rx, ry, per, full}, r = min(floor(2^32 / g), 2^32 - 1); for every
+ * 32-bit T, q = (T * r) >> 32 is T / g or T / g - 1 (one step on the remainder
+ * makes it exact).  vss_tile_index: the tile (x, y, z) that workgroup L = bx +
+ * gx * (by + gy * bz) computes, by the kernels' own function, as three planes
+ * of gx * gy * gz ints: out[L] = x, out[n + L] = y, out[2 n + L] = z — a
+ * bijection on the grid. */
+int vss_tile_map(int gx, int gy, int gz, unsigned* out6);
+int vss_tile_index(int gx, int gy, int gz, int* out);
+
 /* ---- §8(f) row 1: the reference's mask post-processing, on the GPU ----------
  * processFrame's steps after the seam (frameProcessorTest.ts:115-169):
  * temporalEMA (:218) -> morphologicalOpening (:644) -> jointBilateral3x3 with the

@@ -1148,6 +1148,27 @@ def block_lds_bytes(mode, stride, th, tw, cin, cskip, chid, cout, stem_in=0) -> 
     return lib().vss_block_lds_bytes(mode, stride, th, tw, cin, cskip, chid, cout, stem_in)
 
 
+def tile_map(gx: int, gy: int, gz: int) -> dict:
+    """tile_map() of csrc/vss_kernels.h for a launch grid (no GPU needed): the grid's x and y
+    sizes, their reciprocals rx, ry = min(floor(2^32 / g), 2^32 - 1), per = (gx gy gz) >> 3
+    and full = per << 3, as the layer kernels receive them."""
+    out = (ctypes.c_uint * 6)()
+    fn = lib().vss_tile_map  # (bound here: a VSS_LIBRARY build from before it still loads)
+    fn.argtypes, fn.restype = [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_uint)], ctypes.c_int
+    _check(fn(gx, gy, gz, out))
+    return dict(zip(("gx", "gy", "rx", "ry", "per", "full"), out))
+
+
+def tile_index(gx: int, gy: int, gz: int) -> np.ndarray:
+    """int32 [3][gz * gy * gx]: the tile (x, y, z) that workgroup bx + gx (by + gy bz) of a
+    layer launch computes, by the kernels' own function run on the host."""
+    out = np.empty((3, gz * gy * gx), np.int32)
+    fn = lib().vss_tile_index
+    fn.argtypes, fn.restype = [ctypes.c_int] * 3 + [ctypes.c_void_p], ctypes.c_int
+    _check(fn(gx, gy, gz, out.ctypes.data))
+    return out
+
+
 def expand_frag_layout(cin: int, cout: int) -> dict:
     """expand_frag() of csrc/vss_kernels.h: byte size of one 16-channel chunk's fragment
     record of an expand layer and the offsets of its sections."""

@@ -722,6 +722,7 @@ BlockParams block_params(const vss_handle* h, const Slot& s, int li, int n, cons
   const Rec& r = l.rec;
   const LayerPlan& src = h->L[r.src];
   BlockParams p{};
+  p.tm = tile_map((unsigned)l.tiles_x, (unsigned)l.tiles_y, (unsigned)(n * l.ks));  // the launch's grid
   p.wimg = l.wimg;
   p.wimg_stride = l.wimg_stride;
   p.wfrag = l.wfrag;
@@ -827,6 +828,7 @@ void forward_launches(vss_handle* h, Slot& s, const uint8_t* frames, int n, int 
       L.fn = (const void*)head_kernel16();
       L.grid = dim3((Wm + kHeadTW - 1) / kHeadTW, (Hm + kHeadTH - 1) / kHeadTH, n);
       L.lds = kHeadLds * 4;
+      p.tm = tile_map(L.grid.x, L.grid.y, L.grid.z);
       L.prm.head = p;
     } else {
       continue;
@@ -886,16 +888,27 @@ bool has_fused_stem(const vss_handle* h) {
   return false;
 }
 
-void destroy_graph(GraphEntry& g) {
-  if (g.last && g.launched) (void)hipEventSynchronize(g.last);  // never destroy an executable in flight
+// Is a launch of one of slot s's executables possibly still running?  Every
+// launch (forward) is followed on its stream by the record of the slot's done
+// event (release_slot), and the slot's next user is ordered after that record
+// (claim_slot), so the slot's latest done record completes after every launch
+// of every executable of the slot: one event record per call serves both the
+// slot's claim protocol and the executables.
+int wait_slot_graphs(vss_handle* h, const Slot& s) {
+  if (s.used) HIP_TRY(h, hipEventSynchronize(s.done));
+  return VSS_OK;
+}
+
+// s = the slot a launched executable belongs to (null: never launched)
+void destroy_graph(GraphEntry& g, const Slot* s = nullptr) {
+  if (g.launched && s && s->used) (void)hipEventSynchronize(s->done);  // never destroy an executable in flight
   if (g.exec) (void)hipGraphExecDestroy(g.exec);
   if (g.graph) (void)hipGraphDestroy(g.graph);
-  if (g.last) (void)hipEventDestroy(g.last);
   g = GraphEntry();
 }
 
-void destroy_graph_set(std::vector<GraphEntry>& v) {
-  for (GraphEntry& g : v) destroy_graph(g);
+void destroy_graph_set(std::vector<GraphEntry>& v, const Slot& s) {
+  for (GraphEntry& g : v) destroy_graph(g, &s);
   v.clear();
 }
 
@@ -917,8 +930,7 @@ int build_graph(vss_handle* h, const std::vector<Launch>& ls, GraphEntry* out) {
     }
     g.nodes.push_back(node);
   }
-  hipError_t e = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&g.last, hipEventDisableTiming);
+  const hipError_t e = hipGraphInstantiate(&g.exec, g.graph, nullptr, nullptr, 0);
   if (e != hipSuccess) {
     destroy_graph(g);
     return fail(h, VSS_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(e));
@@ -937,12 +949,14 @@ int graph_diff(const GraphEntry& g, const std::vector<Launch>& ls) {
 
 // Point executable g at this call's launches: the kernel nodes whose parameter
 // blocks differ are updated.  An update must not race a launch of the same
-// executable still in flight, so it first waits for g's own latest launch.
-int patch_graph(vss_handle* h, GraphEntry& g, const std::vector<Launch>& ls) {
+// executable still in flight, so it first waits for the slot's latest work
+// (wait_slot_graphs: that covers g's own latest launch).
+int patch_graph(vss_handle* h, const Slot& s, GraphEntry& g, const std::vector<Launch>& ls) {
   bool waited = false;
   for (size_t i = 0; i < ls.size(); ++i) {
     if (std::memcmp(&ls[i].prm, &g.launches[i].prm, sizeof(Launch::Prm)) == 0) continue;
-    if (!waited && g.launched) HIP_TRY(h, hipEventSynchronize(g.last));
+    if (!waited && g.launched)
+      if (int rc = wait_slot_graphs(h, s)) return rc;
     waited = true;
     void* args[1];
     const hipKernelNodeParams kp = node_params(ls[i], args);
@@ -972,7 +986,7 @@ void make_room_for_shape(Slot& s) {
       victim = it;
     }
   }
-  destroy_graph_set(victim->second);
+  destroy_graph_set(victim->second, s);
   s.shape_tick.erase(victim->first);
   s.graphs.erase(victim);
 }
@@ -1002,7 +1016,7 @@ int pick_graph(vss_handle* h, Slot& s, const GraphKey& key, const std::vector<La
     *out = &v.back();
     return VSS_OK;
   }
-  if (int rc = patch_graph(h, *lru, ls)) return rc;
+  if (int rc = patch_graph(h, s, *lru, ls)) return rc;
   *out = lru;
   return VSS_OK;
 }
@@ -1071,8 +1085,7 @@ int forward(vss_handle* h, int si, const uint8_t* frames, int n, int fh, int fw,
   g_device_clock.mark(4);
   HIP_TRY(h, hipGraphLaunch(g->exec, st));
   g_device_clock.mark(5);
-  HIP_TRY(h, hipEventRecord(g->last, st));
-  g_device_clock.mark(6);
+  g_device_clock.mark(6);  // (no event of the executable's own: the caller's release_slot records the slot's)
   g->launched = true;
   g->tick = ++s.graph_tick;
   return VSS_OK;
@@ -1080,7 +1093,7 @@ int forward(vss_handle* h, int si, const uint8_t* frames, int n, int fh, int fw,
 
 void drop_graphs(vss_handle* h) {
   for (Slot& s : h->slots) {
-    for (auto& kv : s.graphs) destroy_graph_set(kv.second);
+    for (auto& kv : s.graphs) destroy_graph_set(kv.second, s);
     s.graphs.clear();
     s.shape_tick.clear();
   }
@@ -1829,7 +1842,7 @@ void destroy_engine(vss_handle* h) {
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
   for (Slot& s : h->slots) {
-    for (auto& kv : s.graphs) destroy_graph_set(kv.second);
+    for (auto& kv : s.graphs) destroy_graph_set(kv.second, s);
     if (s.comm) (void)ncclCommDestroy(s.comm);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     if (s.done) (void)hipEventDestroy(s.done);
@@ -2428,6 +2441,29 @@ int vss_slot_stream(vss_handle* h, int k, void** stream) {
 int vss_shard_plan(int n, int nranks, int rank, int* first, int* count, int* per_rank) {
   if (n < 0 || nranks < 1 || rank < 0 || rank >= nranks || !first || !count || !per_rank) return VSS_E_INVALID_ARG;
   shard_plan(n, nranks, rank, first, count, per_rank);
+  return VSS_OK;
+}
+
+int vss_tile_map(int gx, int gy, int gz, unsigned* out6) {
+  if (gx < 1 || gy < 1 || gz < 1 || !out6 || (long long)gx * gy * gz > 0x7FFFFFFFll) return VSS_E_INVALID_ARG;
+  const TileMap m = tile_map((unsigned)gx, (unsigned)gy, (unsigned)gz);
+  const unsigned v[6] = {m.gx, m.gy, m.rx, m.ry, m.per, m.full};
+  std::memcpy(out6, v, sizeof v);
+  return VSS_OK;
+}
+
+int vss_tile_index(int gx, int gy, int gz, int* out) {
+  if (gx < 1 || gy < 1 || gz < 1 || !out || (long long)gx * gy * gz > 0x7FFFFFFFll) return VSS_E_INVALID_ARG;
+  const TileMap m = tile_map((unsigned)gx, (unsigned)gy, (unsigned)gz);
+  const size_t n = (size_t)gx * gy * gz;
+  for (int bz = 0; bz < gz; ++bz)
+    for (int by = 0; by < gy; ++by)
+      for (int bx = 0; bx < gx; ++bx, ++out) {
+        const TileIdx t = tile_of(m, (unsigned)bx, (unsigned)by, (unsigned)bz);
+        out[0] = t.x;
+        out[n] = t.y;
+        out[2 * n] = t.z;
+      }
   return VSS_OK;
 }
 

@@ -82,19 +82,21 @@ struct Launch {
 // executable is built while the set has room, and after that the least
 // recently used one is patched (hipGraphExecKernelNodeSetParams on the kernel
 // nodes whose parameters differ — the first layer reads the frames, the head
-// writes the masks) once ITS last launch is done (its own event: the wait is
-// normally over already, since three newer launches were issued after it).
-// So callers rotating up to kExecPerShape buffer pairs through a slot never
-// patch in steady state, and no caller ever waits for the slot's latest work
-// here (the round-3 single executable waited on every call of a
-// caller rotating 3 buffers over 4 slots, holding the handle's lock).
+// writes the masks) once the slot's latest work is done: the slot's done event,
+// which every call records after its launch anyway (release_slot), completes
+// after every launch of every executable of the slot, so the executables keep
+// no event of their own — one event record, one barrier packet, per call
+// instead of two.  Callers rotating up to kExecPerShape buffer pairs through a
+// slot never patch in steady state, so they never wait here (the
+// round-3 single executable waited on every call of a caller rotating 3
+// buffers over 4 slots, holding the handle's lock); a caller rotating more
+// pairs than that patches on every call and waits for the slot's previous call.
 using GraphKey = std::tuple<int, int, int, int, size_t, size_t>;  // n, fh, fw, fc, row / frame stride
 constexpr int kExecPerShape = 4;
 struct GraphEntry {
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
-  hipEvent_t last = nullptr;          // recorded after this executable's latest launch
-  bool launched = false;
+  bool launched = false;              // ever launched: the slot's done event then covers it
   unsigned long long tick = 0;        // LRU clock of its latest launch
   std::vector<hipGraphNode_t> nodes;  // one kernel node per launch, in order
   std::vector<Launch> launches;       // the parameters the executable graph holds now

@@ -320,6 +320,15 @@ __host__ __device__ constexpr int frag_off(int n, int i, int l) {
   } while (0)
 #endif
 
+// Workgroup -> tile of the layer launches and the head, computed by the host
+// for the launch's grid (tile_map() / xcd_tile() at the end of this file)
+struct TileMap {
+  unsigned gx, gy;   // the launch's grid x, y (tiles per row, rows of tiles)
+  unsigned rx, ry;   // min(floor(2^32 / gx), 2^32 - 1), the same of gy
+  unsigned per;      // workgroups per XCD's eighth: (gx * gy * gz) >> 3
+  unsigned full;     // per << 3: indices from here on keep their place
+};
+
 struct StemParams {
   const uint8_t* frames; // [N] frames, row_stride / frame_stride bytes
   long row_stride, frame_stride;
@@ -336,6 +345,7 @@ struct StemParams {
 };
 
 struct BlockParams {
+  TileMap tm;            // workgroup -> tile of this launch's grid (tiles_x, tiles_y, N * KS)
   const float* wimg;     // the layer's LDS weight image (block_lds regions w1..b2), built by the host;
                          // with KS > 1 one image per hidden slice, wimg_stride floats apart
   long wimg_stride;
@@ -421,6 +431,7 @@ const BlockEntry* block_registry(int* count);
 
 
 struct HeadParams {
+  TileMap tm;            // workgroup -> tile of the launch's grid
   const float* x;        // pre-norm dec output [N][h][w][cin]
   const unsigned long long* in_acc;  // its norm accumulator (see BlockParams), frame stride acc_stride
   int acc_stride;
@@ -867,20 +878,48 @@ void launch_post_filter(const PostFilterParams& p, int n, hipStream_t s);
 #ifndef VSS_XCD_REMAP
 #define VSS_XCD_REMAP 1
 #endif
+// The remap runs at the head of every workgroup, before its first load, and
+// its two divisions by the grid's sizes cost ~25 instructions each as run-time
+// integer divisions (v_rcp_iflag_f32 sequences).  The host knows the grid: it
+// passes the sizes, their reciprocals and `per` in the kernel's parameter block
+// (TileMap, tile_map() below), and a division becomes a multiply-high plus one
+// correction step.  With m = min(floor(2^32 / d), 2^32 - 1) the estimate
+// q' = (T * m) >> 32 is q or q - 1 for EVERY 32-bit T and every d >= 1
+// (T / d - T * m / 2^32 < T / 2^32 < 1; d = 1: q' = T - 1), so one compare of
+// the remainder makes it exact: no bound on the grid's size.
 struct TileIdx {
   int x, y, z;
 };
-__device__ __forceinline__ TileIdx xcd_tile() {
-  if constexpr (VSS_XCD_REMAP) {
-    const int gx = (int)gridDim.x, gy = (int)gridDim.y;
-    const int L = (int)blockIdx.x + gx * ((int)blockIdx.y + gy * (int)blockIdx.z);
-    const int per = (gx * gy * (int)gridDim.z) >> 3;
-    const int T = L < (per << 3) ? (L & 7) * per + (L >> 3) : L;
-    const int zy = T / gx;
-    return {T - zy * gx, zy % gy, zy / gy};
-  } else {
-    return {(int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z};
+__host__ __device__ inline unsigned tile_recip(unsigned d) {
+  const unsigned long long m = 0x100000000ull / d;
+  return m > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned)m;
+}
+__host__ __device__ inline TileMap tile_map(unsigned gx, unsigned gy, unsigned gz) {
+  const unsigned per = (gx * gy * gz) >> 3;
+  return {gx, gy, tile_recip(gx), tile_recip(gy), per, per << 3};
+}
+// T / d and T % d from d's reciprocal m = tile_recip(d)
+__host__ __device__ __forceinline__ void tile_divmod(unsigned T, unsigned d, unsigned m, unsigned& q, unsigned& r) {
+  q = (unsigned)(((unsigned long long)T * m) >> 32);
+  r = T - q * d;
+  if (r >= d) {
+    ++q;
+    r -= d;
   }
 }
+// the tile (x, y, z) of workgroup (bx, by, bz)
+__host__ __device__ __forceinline__ TileIdx tile_of(const TileMap& m, unsigned bx, unsigned by, unsigned bz) {
+  if constexpr (VSS_XCD_REMAP) {
+    const unsigned L = bx + m.gx * (by + m.gy * bz);
+    const unsigned T = L < m.full ? (L & 7) * m.per + (L >> 3) : L;
+    unsigned zy, x, z, y;
+    tile_divmod(T, m.gx, m.rx, zy, x);
+    tile_divmod(zy, m.gy, m.ry, z, y);
+    return {(int)x, (int)y, (int)z};
+  } else {
+    return {(int)bx, (int)by, (int)bz};
+  }
+}
+__device__ __forceinline__ TileIdx xcd_tile(const TileMap& m) { return tile_of(m, blockIdx.x, blockIdx.y, blockIdx.z); }
 
 }  // namespace vss

@@ -632,6 +632,25 @@ __device__ __forceinline__ void dma_wait() {
   if constexpr (ON) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
+// Output stores of a layer launch: plain, or write-through (`sc1`, Gm<true>::st)
+// so that the layer leaves no dirty lines in L2 for the kernel boundary behind
+// it to flush.  A compile-time choice by the layer's shape (A/B knobs:
+// VSS_WT_COUT_MAX = the widest output that stores through, 0 = none;
+// VSS_WT_MODES = bit m set: layers of BlockMode m).
+#ifndef VSS_WT_COUT_MAX
+#define VSS_WT_COUT_MAX 32
+#endif
+#ifndef VSS_WT_MODES
+#define VSS_WT_MODES 7
+#endif
+#ifndef VSS_WT_RES
+#define VSS_WT_RES 0  // (A/B knob: the stride-1 expand blocks too)
+#endif
+constexpr bool block_wt_stores(int mode, int stride, int cout) {
+  return cout <= VSS_WT_COUT_MAX && ((VSS_WT_MODES >> mode) & 1) &&
+         (VSS_WT_RES || !(mode == MODE_IR_EXPAND && stride == 1));
+}
+
 template <bool B>
 struct ChunkTag {
   static constexpr bool value = B;
@@ -1352,7 +1371,7 @@ __device__ __forceinline__ void block_body(const BlockParams& p, int bx, int by,
     // the accumulators — the same additions in the same order as the slab
     // path, without its LDS round trip and two barriers (b1)
     VSS_STAMP(2);
-    const Gm<COH> gy(p.y + (long)n * Ho * Wo * COUT);
+    const Gm<COH || block_wt_stores(MODE, STRIDE, COUT)> gy(p.y + (long)n * Ho * Wo * COUT);
 #pragma unroll
     for (int q = 0; q < NPBW / XR; ++q)
 #pragma unroll
@@ -1380,7 +1399,7 @@ __device__ __forceinline__ void block_body(const BlockParams& p, int bx, int by,
   }
   __syncthreads();
   constexpr int C4O = COUT / 4, NOUT = (P_OUT * C4O + 255) / 256;
-  const Gm<COH> gy(p.y + ks * p.y_part_stride + (long)n * Ho * Wo * COUT);
+  const Gm<COH || block_wt_stores(MODE, STRIDE, COUT)> gy(p.y + ks * p.y_part_stride + (long)n * Ho * Wo * COUT);
   // the decoder keeps its outputs in registers until its stats are done: a
   // workgroup barrier waits for every store issued before it (vmcnt(0))
   f4 outv[MODE == MODE_DEC ? NOUT : 1];
@@ -1523,7 +1542,7 @@ template <int MODE, int STRIDE, int TH, int TW, int CIN, int CSKIP, int CH, int 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(block_min_waves(MODE, STRIDE, TH, TW, CIN, COUT, PREC))))
 void k_block(BlockParams p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const TileIdx t = xcd_tile();
+  const TileIdx t = xcd_tile(p.tm);
   block_body<MODE, STRIDE, TH, TW, CIN, CSKIP, CH, COUT, FLAGS, PREC, false>(p, t.x, t.y, t.z, smem);
 }
 
@@ -1556,7 +1575,7 @@ __global__ __launch_bounds__(kWideThreads) void k_stem_b1(BlockParams p) {
   float* sbs = smem + S.sb;
   float* xt = smem + S.xt;
   float* wim = smem + S.wim;
-  const TileIdx tl = xcd_tile();
+  const TileIdx tl = xcd_tile(p.tm);
   const int bx = tl.x, by = tl.y, n = tl.z;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, g = lane >> 4;
   const int oy0 = by * TH, ox0 = bx * TW, iy0 = oy0 - 1, ix0 = ox0 - 1;
@@ -1772,7 +1791,7 @@ __device__ __forceinline__ void head_body(const HeadParams& p, int bx, int by, i
 template <int C>
 __global__ __launch_bounds__(256) void k_head(HeadParams p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  const TileIdx t = xcd_tile();
+  const TileIdx t = xcd_tile(p.tm);
   head_body<C, false>(p, t.x, t.y, t.z, smem);
 }
 
