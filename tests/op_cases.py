@@ -52,7 +52,7 @@ class Case:
     # node j (0: its operator, j: chain[j - 1]).  A chain node may carry a fourth element, {"whole": its
     # inputs are all listed, ("prev",) standing for the node before; "out": its output is one more graph
     # output of the case, ahead of the last node's; "n": it has that many outputs, ("node", j, q) its q-th}.
-    # Further input kinds (the norm families): "ramp", "off100", "small", "half" — see _generate.
+    # Further input kinds (the norm families): "ramp", "off100", "small", "half"; "q8" (the fusion matrix) — see _generate.
     kernels16: tuple = ()   # `kernels` of a bf16 / f16 session (the ir family, whose fused forms differ by precision)
     echo: bool = False      # the case's input 0 is a graph output too (the first of the case's)
     op_out: bool = False    # the operator's own output (node 0 of a chain) is a graph output too (behind echo's)
@@ -1029,6 +1029,8 @@ def _generate(name, kind, shape):
         k = np.arange(int(np.prod(shape[:2])), dtype=np.int64)
         a = np.broadcast_to((0.5 * (1 + k % 7) * (1 - 2 * (k % 2))).reshape(tuple(shape[:2]) + (1,) * (len(shape) - 2)),
                             shape)
+    elif kind == "q8":  # multiples of 1/8: a 2x linear Resize of them is exact in float32 and float64 alike
+        a = np.round(rng.standard_normal(shape) * 8.0) / 8.0
     else:  # "x", "x3", "x4": standard normal, times 3 / 4 (wider activations)
         a = rng.standard_normal(shape) * (float(kind[1:]) if len(kind) > 1 else 1.0)
     return a.astype(np.float32)

@@ -1319,7 +1319,8 @@ __global__ __launch_bounds__(256) void k_conv_thin(ConvParams p, NormParams q, i
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const long pix = pix0 + j;
-      o[j] = epilogue(p.ep, acc[m][j], m, ((long)n * p.M + m) * P + pix, n, (int)pix);
+      // (a pixel past the plane, in the last group of an unaligned one: no residual to read for it)
+      o[j] = pix < P ? epilogue(p.ep, acc[m][j], m, ((long)n * p.M + m) * P + pix, n, (int)pix) : 0.f;
     }
     if (vec) {
       *reinterpret_cast<f4*>(yn + m * P + pix0) = o;

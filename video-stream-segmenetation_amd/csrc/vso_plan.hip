@@ -46,8 +46,9 @@ struct Planner {
   // Add operands computed inside the consuming convolution's epilogue instead
   // of by their own launches: MaxPool(2x2, s2) -> [Pad of the channel axis] -> Add
   struct ResFuse {
-    std::string src;  // the MaxPool's input, or the Pad's input
-    int mode;         // Epilogue::res_mode
+    std::string src;          // the MaxPool's input, or the Pad's input
+    int mode;                 // Epilogue::res_mode
+    int pool_node, pad_node;  // the nodes left without a launch (-1: none)
   };
   std::map<std::string, ResFuse> res_fuse;  // by the Add operand's name (find_residual_fusions)
   // MODNet's IBNorm (Conv2dIBNormRelu; the authors' src/models/modnet.py):
@@ -266,9 +267,11 @@ struct Planner {
           mode = 2;
         }
         if (mode == 0) continue;
+        // the source must exist when the Conv is planned: a graph input, or a value produced ahead of it
+        if (producer(cur) > pc) continue;
         if (pad_node >= 0) done.insert((size_t)pad_node);
         if (pool_node >= 0) done.insert((size_t)pool_node);
-        res_fuse[o] = ResFuse{cur, mode};
+        res_fuse[o] = ResFuse{cur, mode, pool_node, pad_node};
         break;
       }
     }
@@ -819,13 +822,24 @@ struct Planner {
       const Node& ad = g.nodes[c1];
       const std::string& other = ad.in[0] == c->out ? ad.in[1] : ad.in[0];
       auto rf = res_fuse.find(other);
+      if (rf != res_fuse.end()) {
+        // the epilogue addresses the source per image, channel and output pixel: an Add that broadcasts
+        // its operand (one image for the batch, one pixel for the plane) is not that — the MaxPool / Pad
+        // get their launches after all (they stay `done`: the walk does not plan them again)
+        const int mode = rf->second.mode;
+        Value* src = val(rf->second.src);
+        if (!src || src->is_const || src->shape.size() != 4 || src->shape[0] != p.N || src->shape[1] > p.M ||
+            (mode == 1 && (src->shape[2] != p.Ho || src->shape[3] != p.Wo)) ||
+            (mode == 2 && (src->shape[2] / 2 != p.Ho || src->shape[3] / 2 != p.Wo))) {
+          for (int k : {rf->second.pool_node, rf->second.pad_node})
+            if (k >= 0 && !plan_node((size_t)k)) return false;
+          res_fuse.erase(rf);
+          rf = res_fuse.end();
+        }
+      }
       Value* o = val(rf != res_fuse.end() ? rf->second.src : other);
       if (rf != res_fuse.end()) {  // the strided residual: the MaxPool / Pad computed here
         const int mode = rf->second.mode;
-        if (!o || o->is_const || o->shape.size() != 4 || o->shape[0] != p.N || o->shape[1] > p.M ||
-            (mode == 1 && (o->shape[2] != p.Ho || o->shape[3] != p.Wo)) ||
-            (mode == 2 && (o->shape[2] / 2 != p.Ho || o->shape[3] / 2 != p.Wo)))
-          return fail("Conv '" + g.nodes[ni].name + "': internal: fused residual shape");
         ep.res = dptr(*o);
         ep.res_mode = mode;
         ep.res_c = (int)o->shape[1];
