@@ -17,14 +17,16 @@
  * hipGraph.  Tensors are float32 NCHW.
  *
  * Supported operators: Conv, ConvTranspose, Relu, PRelu, LeakyRelu, Clip,
- * Sigmoid, Tanh, HardSigmoid, HardSwish, Add, Sub, Mul, Div (numpy
+ * Sigmoid, Tanh, HardSigmoid, HardSwish, Gelu, Erf, Add, Sub, Mul, Div (numpy
  * broadcasting), MaxPool, AveragePool, GlobalAveragePool, ReduceMean (over H
- * and W), Pad (constant), Concat, Split, Slice, Transpose,
+ * and W; over the last axis inside a decomposed LayerNorm), Pad (constant),
+ * Concat, Split, Slice, Transpose,
  * Reshape, Flatten, Squeeze, Unsqueeze, Identity, Dropout, Cast (float),
  * Resize/Upsample (nearest, linear; half_pixel, pytorch_half_pixel,
  * align_corners, asymmetric), InstanceNormalization, BatchNormalization,
- * MatMul, Gemm, Softmax, and Shape, Gather, Constant, ConstantOfShape,
- * Floor, Ceil, Cast on constants.  For q4f16 exports (model_q4f16.onnx's
+ * LayerNormalization, MatMul, Gemm, Softmax, Pow and Sqrt (inside a
+ * decomposed LayerNorm), and Shape, Gather, Constant, ConstantOfShape,
+ * Floor, Ceil, Cast, Sqrt, Erf, Pow on constants.  For q4f16 exports (model_q4f16.onnx's
  * form): float16 initializers, Cast to FLOAT16 (values rounded to halves and
  * kept as f32; later ops compute in f32), DequantizeLinear of int8 / uint8 /
  * int4 / uint4 weights (per tensor, per axis, opset-21 blocks; folded at
@@ -32,8 +34,8 @@
  * points, bias; dequantised once at create).  Anything else fails vso_create
  * with VSO_E_UNSUPPORTED naming the node.
  *
- * Attributes (tests/op_cases.py and tests/op_cases_deconv.py are the tables
- * the sessions are held to):
+ * Attributes (tests/op_cases.py, tests/op_cases_deconv.py and
+ * tests/op_cases_attn.py are the tables the sessions are held to):
  *   opset_import          read; it selects Softmax's form and Split's default.
  *   Conv                  2-D, constant weights and bias; group, strides,
  *                         dilations (0 or 2 values each), pads (0 or 4 values),
@@ -78,6 +80,38 @@
  *                         hard-swish of exports before opset 14, for any alpha
  *                         and beta, when that Mul is the HardSigmoid's only
  *                         consumer (one activation, x clamp(alpha x + beta)).
+ *   LayerNormalization    opset 17; input of rank >= 2; axis (default -1,
+ *                         negative forms accepted): the normalised extent D is
+ *                         the product of the dims from axis on, the rest are
+ *                         rows; epsilon (1e-5); constant Scale of D elements
+ *                         and optional constant B.  y = (x - mean) / sqrt(var +
+ *                         epsilon) * Scale + B, the variance taken about the
+ *                         mean over the resident row (never E[x^2] - mean^2),
+ *                         one k_layer_norm launch: a wave per row up to D =
+ *                         1024, a workgroup per row above.  The form PyTorch
+ *                         exports below opset 17 — ReduceMean(x, axes [-1],
+ *                         keepdims 1) -> Sub -> Pow(., 2) or Mul(d, d) ->
+ *                         ReduceMean -> Add(eps) -> Sqrt -> Div [-> Mul(gamma)]
+ *                         [-> Add(beta)], eps a scalar, gamma / beta constants
+ *                         of 1 or D elements, every interior value read inside
+ *                         the pattern only — is the same one launch.  Refused:
+ *                         a runtime Scale or B, a used Mean / InvStdDev
+ *                         output, stash_type other than 1; outside the pattern
+ *                         (the difference read a third time, keepdims 0,
+ *                         another axis) a ReduceMean over a non-spatial axis
+ *                         set, Pow and Sqrt of runtime tensors stay refused.
+ *   Gelu, Erf             Gelu (opset 20): approximate none (0.5 x (1 + erf(x /
+ *                         sqrt 2))) or tanh.  Erf: elementwise.  The erf form
+ *                         of older exports, x * 0.5 * (1 + Erf(x / sqrt 2)) —
+ *                         either association of the product, Div by sqrt 2 or
+ *                         Mul by 1 / sqrt 2, the constants matched to 1e-6
+ *                         relative — is the same one activation.  All three
+ *                         run in the epilogue of a producing Conv,
+ *                         ConvTranspose, Gemm or MatMul when they are all that
+ *                         reads it, else as one elementwise launch.  A
+ *                         constant that misses (0.7 for 0.70710678) leaves the
+ *                         nodes as they are: five launches, the same values.
+ *                         Refused: any other approximate.
  *   ReduceMean            rank-4 input; axes (attribute, or constant input from
  *                         opset 18) exactly the two spatial axes, negative
  *                         forms accepted; keepdims 0 or 1;
@@ -112,7 +146,26 @@
  *                         opset 18 on ceil-sized with a smaller last part.
  *                         Refused: an uneven default split below opset 18.
  *   Gemm                  transA, transB, alpha, beta, C broadcast to [M, N].
- *   MatMul                B of rank 2, of batch 1, or batched like A.
+ *   MatMul                B of rank 2, of batch 1, or batched like A.  By a
+ *                         constant B, a following Add of a constant [N] (or
+ *                         [1, .., N]) that is all that reads the product is the
+ *                         launch's bias (a Linear layer), and an activation
+ *                         behind it is still absorbed.
+ *   attention             MatMul(Q, Transpose(K: the last two axes swapped)) [->
+ *                         Mul or Div by a constant scalar] [-> Add(bias)] ->
+ *                         Softmax(last axis) -> MatMul(., V) is one k_attn
+ *                         launch that never writes the scores (vso_attn_count,
+ *                         below): Q [.., Nq, d], K [.., Nk, d], V [.., Nk, dv]
+ *                         runtime tensors with equal leading dims; every
+ *                         interior value read by the next node only; the bias
+ *                         constant or runtime, its last two dims [Nq, Nk], its
+ *                         leading ones 1 or Q's; a Mul by a constant scalar on
+ *                         Q or on K in front of the first MatMul, read by it
+ *                         only, is taken too; d and dv multiples of 4 up to
+ *                         128.  The K Transpose launches nothing when the
+ *                         pattern is all that reads it.  Anything else — the
+ *                         Softmax read elsewhere, other axes transposed, d = 6
+ *                         or 132, a constant K — keeps the five launches.
  *   Softmax               the last axis; below opset 13 the input flattened to
  *                         2-D at axis (default 1), every row normalised.
  *                         Refused: another axis from opset 13 on.
@@ -224,6 +277,18 @@ int vso_tile_conv_count(const vso_session* s);
  * launches; VSO_IR_B16=0 keeps the f32 form in 16-bit sessions; VSO_IR_CPS
  * (default 6) hidden 16-channel chunks per slice of a 16-bit block. */
 int vso_ir_block_count(const vso_session* s);
+/* Attention patterns (see "attention" above) the session runs as one fused
+ * launch each (vso_attn.hip, k_attn): a 256-thread workgroup owns one slice of
+ * the leading dims and 64 query rows, walks the keys in blocks of 32 staged in
+ * LDS, keeps the running row maximum and sum in registers (exp only of the
+ * difference from the maximum) and writes the output once; both products on
+ * v_mfma_f32_16x16x4_f32 (exact f32 products) in every session precision, so
+ * bf16 / f16 sessions are bitwise the f32 one on these nodes.  Planning knob,
+ * read once per process: VSO_ATTN=0 keeps the Transpose, MatMul, scale, bias,
+ * Softmax and MatMul launches; its outputs meet the same 1e-4 bar against the
+ * float64 reference but are not bitwise the fused ones (another order of the
+ * same sums). */
+int vso_attn_count(const vso_session* s);
 /* ConvTranspose at a stride above 1 (vso_deconv.hip): per output phase
  * ((oy + pad) mod stride, per axis) one stride-1 correlation over the taps
  * ky = phase + j stride, 1 / (sh sw) of the zero-stuffed form's multiply-adds.

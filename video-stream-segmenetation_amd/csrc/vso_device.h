@@ -47,6 +47,9 @@ __device__ __forceinline__ float act_apply(float v, int act, float a0, float a1,
     case ACT_F16: return __half2float(__float2half_rn(v));
     case ACT_HSIGMOID: return fminf(fmaxf(__builtin_fmaf(a0, v, a1), 0.f), 1.f);
     case ACT_HSWISH: return v * fminf(fmaxf(__builtin_fmaf(a0, v, a1), 0.f), 1.f);
+    case ACT_GELU: return 0.5f * v * (1.f + erff(v * 0.70710678118654752f));
+    case ACT_GELU_TANH: return 0.5f * v * (1.f + tanhf(0.79788456080286536f * (v + 0.044715f * v * v * v)));
+    case ACT_ERF: return erff(v);
     default: return v;
   }
 }

@@ -71,7 +71,17 @@ void fold_elementwise(const Node& nd, const Const& x, Const& r) {
       for (float& v : r.f) v = round_half(v);
   } else if (nd.op == "Floor" || nd.op == "Ceil") {
     for (float& v : r.f) v = nd.op == "Floor" ? std::floor(v) : std::ceil(v);
+  } else if (nd.op == "Sqrt" || nd.op == "Erf") {  // (float constants: an attention scale sqrt(d), a GELU table)
+    for (float& v : r.f) v = (float)(nd.op == "Sqrt" ? std::sqrt((double)v) : std::erf((double)v));
   }
+}
+
+// Pow of a float constant by one constant exponent
+bool fold_pow(const Node& nd, const Const& x, const Const& e, Const& r, std::string* err) {
+  if (x.is_int || e.numel() != 1 || e.f.empty()) return fail(err, "Pow '" + nd.name + "': a float constant to one constant exponent only");
+  r = x;
+  for (float& v : r.f) v = (float)std::pow((double)v, (double)e.f[0]);
+  return true;
 }
 
 // Add, Sub, Mul, Div with broadcasting on small constant tensors
@@ -243,6 +253,10 @@ bool fold(const Node& nd, const std::vector<Operand>& in, Const* out, std::strin
   } else if (op == "Shape") fold_shape(nd, *in[0].shape, r);
   else if (op == "ConstantOfShape") fold_constant_of_shape(nd, *in[0].c, r);
   else if (op == "Identity" || op == "Cast" || op == "Floor" || op == "Ceil") fold_elementwise(nd, *in[0].c, r);
+  else if ((op == "Sqrt" || op == "Erf") && !in[0].c->is_int) fold_elementwise(nd, *in[0].c, r);
+  else if (op == "Pow" && in.size() == 2) {
+    if (!fold_pow(nd, *in[0].c, *in[1].c, r, err)) return false;
+  }
   else if (op == "Add" || op == "Sub" || op == "Mul" || op == "Div") {
     if (!fold_arith(nd, *in[0].c, *in[1].c, r, err)) return false;
   } else if (op == "DequantizeLinear") {

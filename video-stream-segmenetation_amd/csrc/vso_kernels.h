@@ -15,7 +15,10 @@ constexpr int kMaxDims = 6;
 enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_CLIP = 2, ACT_PRELU = 3, ACT_LEAKY = 4, ACT_SIGMOID = 5, ACT_TANH = 6,
                  ACT_F16 = 7 /* Cast to float16: round to the nearest half (ties to even), kept as f32 */,
                  ACT_HSIGMOID = 8 /* HardSigmoid: clamp(a0 * x + a1, 0, 1) */,
-                 ACT_HSWISH = 9 /* x * clamp(a0 * x + a1, 0, 1): HardSwish (a0 1/6, a1 0.5), Mul(x, HardSigmoid(x)) */ };
+                 ACT_HSWISH = 9 /* x * clamp(a0 * x + a1, 0, 1): HardSwish (a0 1/6, a1 0.5), Mul(x, HardSigmoid(x)) */,
+                 ACT_GELU = 10 /* Gelu, approximate none: 0.5 x (1 + erf(x / sqrt 2)) */,
+                 ACT_GELU_TANH = 11 /* Gelu, approximate tanh: 0.5 x (1 + tanh(sqrt(2 / pi) (x + 0.044715 x^3))) */,
+                 ACT_ERF = 12 /* Erf (k_unary only) */ };
 
 struct Epilogue {
   const float* bias;   // [M] or null
@@ -207,6 +210,45 @@ struct GemmParams {  // y[b][m][n] = alpha * sum_k A[b][m][k] B[b][k][n] + beta 
   float alpha, beta;
   Epilogue ep;         // act only
 };
+
+// LayerNormalization of `rows` contiguous rows of D elements (k_layer_norm):
+// y = (x - mean) / sqrt(var + eps) * scale[i] + shift[i], the variance taken
+// about the mean over the register- or LDS-resident row.  A wave per row up
+// to kLnWaveMax elements, a workgroup per row above (the row in LDS up to
+// kLnLdsMax elements, re-read from global memory beyond).
+constexpr int kLnWaveMax = 1024, kLnLdsMax = 8192;
+struct LayerNormParams {
+  const float* x;
+  float* y;
+  long rows;
+  int D;
+  const float* scale;  // [D] or null (1)
+  const float* shift;  // [D] or null (0)
+  float eps;
+};
+const char* layer_norm_name(const LayerNormParams& p);
+void launch_layer_norm(const LayerNormParams& p, hipStream_t s);
+
+// Fused attention (vso_attn.hip, k_attn): y[b] = softmax(scale * Q[b] K[b]^T + bias) V[b]
+// for b < BH; Q [BH][Nq][d], K [BH][Nk][d], V [BH][Nk][dv], y [BH][Nq][dv], all
+// contiguous and 16-byte aligned; d and dv multiples of 4, at most kAttnMaxD.
+// bias (or null): [..][Nq][Nk], slice b's plane at bias + sum_k i_k * bstr[k]
+// with b unravelled over lead[0 .. nlead) (bstr 0 on a broadcast dim).
+constexpr int kAttnMaxD = 128, kAttnMaxLead = kMaxDims - 2;
+struct AttnParams {
+  const float* q;
+  const float* k;
+  const float* v;
+  const float* bias;
+  float* y;
+  int BH, Nq, Nk, d, dv;
+  float scale;
+  int nlead, lead[kAttnMaxLead];
+  long bstr[kAttnMaxLead];
+};
+bool attn_supported(const AttnParams& p);
+const char* attn_kernel_name(const AttnParams& p);
+void launch_attn(const AttnParams& p, hipStream_t s);
 
 // A MobileNetV2 inverted residual block — 1x1 expand + Clip -> 3x3 depthwise
 // (stride 1 / 2) + Clip -> 1x1 project (+ the block input) — in one launch

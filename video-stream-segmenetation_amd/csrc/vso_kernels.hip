@@ -14,8 +14,9 @@
 //   the rest    : broadcast binary ops, unary activations, one strided
 //                 gather-copy for Transpose / Slice / Split / Concat / Pad,
 //                 pooling, per-row reductions (GlobalAveragePool,
-//                 InstanceNormalization, Softmax), channel affine
-//                 (BatchNormalization), Resize and a small batched GEMM.
+//                 InstanceNormalization, LayerNormalization, Softmax),
+//                 channel affine (BatchNormalization), Resize and a small
+//                 batched GEMM.  (Fused attention: vso_attn.hip.)
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
@@ -1371,6 +1372,87 @@ __global__ __launch_bounds__(256) void k_softmax(RowParams p) {
   for (long i = threadIdx.x; i < p.inner; i += 256) s += expf(x[i] - m);
   s = block_sum(s, sh);
   for (long i = threadIdx.x; i < p.inner; i += 256) y[i] = expf(x[i] - m) / s;
+}
+
+// LayerNormalization.  NV > 0: a wave per row of D <= 64 NV elements, the row
+// in NV registers per lane (element lane + 64 k: coalesced), read once and
+// written once; four rows per workgroup.  NV == 0: a workgroup per row, the
+// row kept in LDS on its first read (D <= kLnLdsMax; a longer one is read
+// from global memory again, by the thread that read it first).  Both take
+// the mean first and the variance about it second, over the resident row:
+// E[x^2] - mean^2 loses |mean| / std squared of the variance's precision
+// (the statistics note).
+template <int NV>
+__global__ __launch_bounds__(256) void k_layer_norm(LayerNormParams p) {
+  const int lane = threadIdx.x & 63, D = p.D;
+  const float inv_d = 1.f / (float)D;
+  if constexpr (NV > 0) {
+    const long row = blockIdx.x * 4L + (threadIdx.x >> 6);
+    if (row >= p.rows) return;  // (whole waves: no barrier below)
+    const float* x = p.x + row * D;
+    float v[NV];
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+      const int i = lane + 64 * k;
+      v[k] = i < D ? x[i] : 0.f;
+      s += v[k];
+    }
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    const float mean = s * inv_d;
+    float q = 0.f;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+      const float c = lane + 64 * k < D ? v[k] - mean : 0.f;
+      v[k] = c;
+      q += c * c;
+    }
+    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
+    const float rstd = 1.f / sqrtf(q * inv_d + p.eps);
+    float* y = p.y + row * D;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+      const int i = lane + 64 * k;
+      if (i < D) y[i] = v[k] * rstd * (p.scale ? p.scale[i] : 1.f) + (p.shift ? p.shift[i] : 0.f);
+    }
+  } else {
+    __shared__ float rowv[kLnLdsMax];
+    __shared__ float sh[4];
+    const bool lds = D <= kLnLdsMax;
+    const float* x = p.x + (long)blockIdx.x * D;
+    float s = 0.f;
+    for (int i = threadIdx.x; i < D; i += 256) {
+      const float t = x[i];
+      if (lds) rowv[i] = t;
+      s += t;
+    }
+    const float mean = block_sum(s, sh) * inv_d;
+    float q = 0.f;
+    for (int i = threadIdx.x; i < D; i += 256) {  // (each thread reads back what it wrote: no barrier needed)
+      const float c = (lds ? rowv[i] : x[i]) - mean;
+      q += c * c;
+    }
+    const float rstd = 1.f / sqrtf(block_sum(q, sh) * inv_d + p.eps);
+    float* y = p.y + (long)blockIdx.x * D;
+    for (int i = threadIdx.x; i < D; i += 256)
+      y[i] = ((lds ? rowv[i] : x[i]) - mean) * rstd * (p.scale ? p.scale[i] : 1.f) + (p.shift ? p.shift[i] : 0.f);
+  }
+}
+
+static int layer_norm_nv(const LayerNormParams& p) { return p.D <= 256 ? 4 : p.D <= kLnWaveMax ? 16 : 0; }
+const char* layer_norm_name(const LayerNormParams& p) {
+  const int nv = layer_norm_nv(p);
+  return nv == 4    ? "void vso::k_layer_norm<4>(vso::LayerNormParams)"
+         : nv == 16 ? "void vso::k_layer_norm<16>(vso::LayerNormParams)"
+                    : "void vso::k_layer_norm<0>(vso::LayerNormParams)";
+}
+void launch_layer_norm(const LayerNormParams& p, hipStream_t s) {
+  if (p.rows <= 0 || p.D <= 0) return;
+  const int nv = layer_norm_nv(p);
+  const dim3 wave_grid((unsigned)((p.rows + 3) / 4));
+  if (nv == 4) hipLaunchKernelGGL(k_layer_norm<4>, wave_grid, dim3(256), 0, s, p);
+  else if (nv == 16) hipLaunchKernelGGL(k_layer_norm<16>, wave_grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(k_layer_norm<0>, dim3((unsigned)p.rows), dim3(256), 0, s, p);
 }
 
 __global__ __launch_bounds__(256) void k_affine(AffineParams p) {

@@ -1,7 +1,7 @@
 // vso_plan.hip — the ONNX sessions' planner: a parsed Graph (vso_onnx.h) and
 // the input shapes -> the session's launch list over preallocated HBM tensors
 // (vso_session.h), at create.  Host code; the kernels are vso_kernels.hip,
-// vso_conv.hip and vso_ir.hip.
+// vso_conv.hip, vso_ir.hip, vso_deconv.hip and vso_attn.hip.
 //
 // Planning rules:
 //  * every shape is static once input 0's shape is fixed; nodes whose inputs
@@ -14,7 +14,11 @@
 //    launch when each intermediate has exactly one consumer; a ConvTranspose
 //    absorbs them the same way (plan_conv_transpose);
 //  * the fusions found before planning (find_*): IBNorm, strided residuals,
-//    Concat inputs written in place, 2x upsamples computed by their consumer;
+//    Concat inputs written in place, 2x upsamples computed by their consumer,
+//    the erf form of GELU (one activation), attention (one k_attn launch);
+//  * a decomposed LayerNorm is found from its first ReduceMean when the walk
+//    reaches it (find_layernorm); a MatMul by a constant absorbs a constant
+//    bias Add, then an activation;
 //  * every other runtime node is one launch, by the plan_<op> of its operator.
 #include <hip/hip_runtime.h>
 
@@ -344,7 +348,119 @@ struct Planner {
     return -1;
   }
 
+  // a constant operand as the find_* passes can know it before the walk: an
+  // initializer, a value already folded, or a Constant node's tensor (into *tmp)
+  const Const* const_of(const std::string& n, Const* tmp) {
+    if (Value* v = val(n)) return v->is_const ? &v->c : nullptr;
+    const int p = producer(n);
+    std::string e;
+    if (p < 0 || g.nodes[p].op != "Constant" || !fold(g.nodes[p], {}, tmp, &e)) return nullptr;
+    return tmp;
+  }
+  bool scalar_of(const std::string& n, double* out) {
+    Const t;
+    const Const* c = const_of(n, &t);
+    if (!c || c->numel() != 1 || c->f.empty()) return false;
+    *out = c->f[0];
+    return true;
+  }
+  static bool near(double v, double want) { return std::fabs(v - want) <= 1e-6 * std::fabs(want); }
+  // nd = Mul / Add of `name` and a constant scalar (either order; a Div: name / scalar): the scalar
+  bool with_scalar(const Node& nd, const std::string& name, double* c) {
+    if (nd.in.size() != 2) return false;
+    if (nd.in[0] == name && scalar_of(nd.in[1], c)) return true;
+    return nd.op != "Div" && nd.in[1] == name && scalar_of(nd.in[0], c);
+  }
+
+  // The erf form of GELU (exports before opset 20):
+  //   x * 0.5 * (1 + Erf(x / sqrt 2))
+  // with the three-way product in either association — (x * (1 + erf)) * 0.5,
+  // x * ((1 + erf) * 0.5), (x * 0.5) * (1 + erf) — x / sqrt 2 a Div or a Mul by
+  // 1 / sqrt 2, the constants matched to 1e-6 relative, every interior value
+  // used inside the pattern only.  The earliest of the five nodes (the head)
+  // stands for the pattern, the others are done from here on: ACT_GELU in the
+  // epilogue of x's producer when the pattern is all that reads x (gelu_pair),
+  // else one k_unary launch when the walk reaches the head (plan_arith).
+  struct GeluFuse {
+    std::string x;
+    size_t last;  // the node whose output is the pattern's
+    std::vector<size_t> nodes;
+  };
+  std::map<size_t, GeluFuse> gelu;  // by head node (find_gelu)
+
+  void find_gelu() {
+    const double rt2 = std::sqrt(2.0);
+    for (size_t k = 0; k < g.nodes.size(); ++k) {
+      const Node& ef = g.nodes[k];
+      if (ef.op != "Erf" || ef.in.size() != 1 || done.count(k)) continue;
+      const int pe = producer(ef.in[0]);
+      if (pe < 0 || sole_consumer(ef.in[0], (size_t)pe) != (int)k) continue;
+      const Node& sc = g.nodes[pe];
+      if ((sc.op != "Div" && sc.op != "Mul") || sc.in.size() != 2) continue;
+      double c;
+      std::string x;
+      for (int side = 0; side < 2 && x.empty(); ++side)
+        if (with_scalar(sc, sc.in[side], &c) && near(c, sc.op == "Div" ? rt2 : 1.0 / rt2)) x = sc.in[side];
+      Const tmp;
+      if (x.empty() || const_of(x, &tmp)) continue;
+      const int a = sole_consumer(ef.out[0], k);
+      if (a < 0 || g.nodes[a].op != "Add" || !with_scalar(g.nodes[a], ef.out[0], &c) || !near(c, 1.0)) continue;
+      const std::string& one_erf = g.nodes[a].out[0];
+      const int m1 = sole_consumer(one_erf, (size_t)a);
+      if (m1 < 0 || g.nodes[m1].op != "Mul" || g.nodes[m1].in.size() != 2) continue;
+      const Node& mul1 = g.nodes[m1];
+      const std::string& o1 = mul1.in[0] == one_erf ? mul1.in[1] : mul1.in[0];
+      GeluFuse f{x, 0, {(size_t)pe, k, (size_t)a, (size_t)m1}};
+      const int ph = producer(o1);
+      if (o1 == x || (scalar_of(o1, &c) && near(c, 0.5))) {  // then the other of x and 0.5
+        const int m2 = sole_consumer(mul1.out[0], (size_t)m1);
+        if (m2 < 0 || g.nodes[m2].op != "Mul") continue;
+        const bool ok = o1 == x ? with_scalar(g.nodes[m2], mul1.out[0], &c) && near(c, 0.5)
+                                : g.nodes[m2].in.size() == 2 && (g.nodes[m2].in[0] == x) != (g.nodes[m2].in[1] == x);
+        if (!ok) continue;
+        f.last = (size_t)m2;
+        f.nodes.push_back((size_t)m2);
+      } else if (ph >= 0 && g.nodes[ph].op == "Mul" && sole_consumer(o1, (size_t)ph) == m1 &&
+                 with_scalar(g.nodes[ph], x, &c) && near(c, 0.5)) {
+        f.last = (size_t)m1;
+        f.nodes.push_back((size_t)ph);
+      } else {
+        continue;
+      }
+      bool taken = false;
+      for (size_t q : f.nodes) taken = taken || done.count(q);
+      if (taken) continue;
+      const size_t head = *std::min_element(f.nodes.begin(), f.nodes.end());
+      for (size_t q : f.nodes)
+        if (q != head) done.insert(q);
+      gelu[head] = f;
+    }
+  }
+
+  // `out` (a launch's output so far, written by node `last`) is read by an erf
+  // GELU and by nothing else: the activation into *ep, the pattern's nodes
+  // done; returns the pattern's last node for the caller to absorb, or -1
+  int gelu_pair(const std::string& out, size_t last, Epilogue* ep) {
+    if (gelu.empty() || consumers[out] != 2) return -1;
+    for (const IO& o : g.outputs)
+      if (o.name == out) return -1;
+    for (auto& kv : gelu) {
+      if (kv.first <= last || kv.second.x != out || done.count(kv.first)) continue;
+      ep->act = ACT_GELU;
+      done.insert(kv.first);
+      return (int)kv.second.last;
+    }
+    return -1;
+  }
+  // either decomposed activation behind `out`
+  int act_pair(const std::string& out, size_t last, Epilogue* ep) {
+    const int mul = hswish_pair(out, last, ep);
+    return mul >= 0 ? mul : gelu_pair(out, last, ep);
+  }
+
   // ---- the A/B knobs that change a plan ------------------------------------
+  // VSO_ATTN=0: an attention pattern stays its Transpose, MatMul, scale, bias, Softmax and MatMul launches
+  static bool attn_enabled() { static const bool on = env_on("VSO_ATTN"); return on; }
   // VSO_DECONV_TILE=0: every strided ConvTranspose on k_deconv_direct
   static bool deconv_tile_enabled() { static const bool on = env_on("VSO_DECONV_TILE"); return on; }
   // VSO_DECONV_PAIR=0 / 1: k_deconv_tile<1> (one x phase per workgroup, strided stores) / <2> (both, rows
@@ -478,7 +594,7 @@ struct Planner {
   // ---- graph queries -------------------------------------------------------
   static bool is_act(const std::string& op) {
     return op == "Relu" || op == "Clip" || op == "PRelu" || op == "LeakyRelu" || op == "Sigmoid" || op == "Tanh" ||
-           op == "HardSigmoid" || op == "HardSwish";
+           op == "HardSigmoid" || op == "HardSwish" || op == "Gelu";
   }
 
   // the single node consuming `name`, if exactly one and `name` is no graph output
@@ -507,6 +623,12 @@ struct Planner {
     else if (nd.op == "LeakyRelu") { ep->act = ACT_LEAKY; ep->a0 = nd.af("alpha", 0.01f); }
     else if (nd.op == "HardSigmoid") { ep->act = ACT_HSIGMOID; ep->a0 = nd.af("alpha", 0.2f); ep->a1 = nd.af("beta", 0.5f); }
     else if (nd.op == "HardSwish") { ep->act = ACT_HSWISH; ep->a0 = 1.f / 6.f; ep->a1 = 0.5f; }
+    else if (nd.op == "Erf") ep->act = ACT_ERF;
+    else if (nd.op == "Gelu") {
+      const std::string ap = nd.as("approximate", "none");
+      if (ap != "none" && ap != "tanh") return false;
+      ep->act = ap == "tanh" ? ACT_GELU_TANH : ACT_GELU;
+    }
     else if (nd.op == "Clip") {
       float lo = nd.af("min", -INFINITY), hi = nd.af("max", INFINITY);
       if (nd.in.size() > 1 && !nd.in[1].empty()) { Value* v = val(nd.in[1]); if (!v || !v->is_const) return false; lo = v->c.f[0]; }
@@ -856,7 +978,7 @@ struct Planner {
     }
     if (c1 >= 0 && is_act(g.nodes[c1].op) && act_of(g.nodes[c1], &ep, p.M)) absorb(c, c1, &c1);
     else if (c1 < 0 && !c->ib && ep.act == ACT_NONE) {
-      const int mul = hswish_pair(c->out, c->last, &ep);
+      const int mul = act_pair(c->out, c->last, &ep);
       if (mul >= 0) absorb(c, mul, &c1);
     }
     return err.empty();
@@ -1351,8 +1473,14 @@ struct Planner {
     return plan_unary(nd, *in[0], ep.act, ep.a0, ep.a1);
   }
 
-  bool plan_arith(size_t, const Node& nd, Ins& in) {
+  bool plan_arith(size_t ni, const Node& nd, Ins& in) {
     const std::string& op = nd.op;
+    const auto gf = gelu.find(ni);
+    if (gf != gelu.end()) {  // the head of an erf GELU no producer absorbed: one launch, written as the pattern's output
+      Value* xv = val(gf->second.x);
+      if (!xv || xv->is_const) return fail("Erf GELU of a constant (node '" + nd.name + "')");
+      return plan_unary(nd, *xv, ACT_GELU, 0.f, 0.f, &g.nodes[gf->second.last].out[0]);
+    }
     return plan_binary(nd, in[0], in[1], op == "Add" ? BIN_ADD : op == "Sub" ? BIN_SUB : op == "Mul" ? BIN_MUL : BIN_DIV);
   }
 
@@ -1509,10 +1637,18 @@ struct Planner {
   }
 
   // ReduceMean over exactly H and W of a rank-4 tensor: GlobalAveragePool's
-  // kernels; keepdims 0 is the same buffer seen as [N, C]
+  // kernels; keepdims 0 is the same buffer seen as [N, C].  Over the last axis
+  // it may head a decomposed LayerNorm (find_layernorm): one k_layer_norm
+  // launch; outside that pattern it is refused as any other axis set.
   bool plan_reduce_mean(size_t ni, const Node& nd, Ins& in) {
     const std::string who = "ReduceMean '" + nd.name + "'";
     const std::vector<int64_t>& xs = in[0]->shape;
+    LnMatch lm;
+    if (xs.size() >= 2 && !in[0]->is_const && find_layernorm(ni, xs, &lm)) {
+      for (size_t q : lm.nodes) done.insert(q);
+      return emit_layer_norm(*in[0], xs.back(), lm.has_gamma ? &lm.gamma : nullptr, lm.has_beta ? &lm.beta : nullptr,
+                             lm.eps, lm.out);
+    }
     if (xs.size() != 4) return fail(who + ": rank-4 input only");
     std::vector<int64_t> axes = nd.ais("axes");
     if (in.size() > 1 && in[1]) {  // opset 18 on: an input
@@ -1520,6 +1656,136 @@ struct Planner {
       axes = ints(*in[1]);
     }
     if (axes.empty() && nd.ai("noop_with_empty_axes", 0) != 0) return plan_alias(ni, nd, in);
+    return plan_reduce_mean_hw(ni, nd, in, axes);
+  }
+
+  // ---- LayerNormalization --------------------------------------------------
+  // one k_layer_norm launch: x's rows of D contiguous elements -> `out`
+  bool emit_layer_norm(Value& x, int64_t D, const Const* scale, const Const* shift, float eps, const std::string& out) {
+    LayerNormParams p{};
+    p.x = dptr(x);
+    p.D = (int)D;
+    p.rows = D > 0 ? x.numel() / D : 0;
+    p.eps = eps;
+    if (scale && !(p.scale = upload_vec(scale->f))) return false;
+    if (shift && !(p.shift = upload_vec(shift->f))) return false;
+    if (!(p.y = make_out(out, x.shape))) return false;
+    emit(layer_norm_name(p), p, launch_layer_norm);
+    return true;
+  }
+
+  bool plan_layer_norm(size_t, const Node& nd, Ins& in) {
+    const std::string who = "LayerNormalization '" + nd.name + "'";
+    Value* x = in[0];
+    const int64_t rk = (int64_t)x->shape.size();
+    if (rk < 2) return fail(who + ": rank >= 2 only");
+    int64_t ax = nd.ai("axis", -1);
+    if (ax < 0) ax += rk;
+    if (ax < 0 || ax >= rk) return fail(who + ": axis out of range");
+    if (nd.ai("stash_type", 1) != 1) return fail(who + ": stash_type 1 only");
+    for (size_t k = 1; k < nd.out.size(); ++k) {
+      bool used = !nd.out[k].empty() && consumers[nd.out[k]] > 0;
+      for (const IO& o : g.outputs) used = used || (!nd.out[k].empty() && o.name == nd.out[k]);
+      if (used) return fail(who + ": the Mean / InvStdDev outputs are not supported");
+    }
+    const int64_t D = inner_from(x->shape, (size_t)ax);
+    Value* sc = in.size() > 1 ? in[1] : nullptr;
+    Value* sh = in.size() > 2 ? in[2] : nullptr;
+    if (!sc || !sc->is_const || (sh && !sh->is_const)) return fail(who + ": constant Scale and B only");
+    if (sc->c.numel() != D || (sh && sh->c.numel() != D)) return fail(who + ": Scale / B must have the normalised extent's elements");
+    if (D >= (1LL << 31)) return fail(who + ": rows of 2^31 elements or more");
+    return emit_layer_norm(*x, D, &sc->c, sh ? &sh->c : nullptr, nd.af("epsilon", 1e-5f), nd.out[0]);
+  }
+
+  // LayerNorm as PyTorch exports it below opset 17, from its first ReduceMean `ni`:
+  //   m = ReduceMean(x, axes [-1], keepdims 1); d = Sub(x, m); Pow(d, 2) | Mul(d, d);
+  //   ReduceMean(axes [-1], keepdims 1); Add(eps); Sqrt; Div(d, .) [; Mul(gamma)] [; Add(beta)]
+  // every interior value read inside the pattern only (d by its square and the
+  // Div), eps a scalar, gamma / beta constants of 1 or D elements.
+  struct LnMatch {
+    std::vector<size_t> nodes;  // behind `ni`
+    float eps;
+    Const gamma, beta;
+    bool has_gamma = false, has_beta = false;
+    std::string out;
+  };
+  bool last_axis_mean(const Node& nd, int64_t rk) {
+    if (nd.op != "ReduceMean" || nd.in.empty() || nd.ai("keepdims", 1) != 1) return false;
+    std::vector<int64_t> axes = nd.ais("axes");
+    Const t;
+    if (nd.in.size() > 1 && !nd.in[1].empty()) {
+      const Const* c = const_of(nd.in[1], &t);
+      if (!c) return false;
+      axes = ints_of(*c);
+    }
+    return axes.size() == 1 && (axes[0] == -1 || axes[0] == rk - 1);
+  }
+  static std::vector<int64_t> ints_of(const Const& c) {
+    return c.is_int ? c.i : std::vector<int64_t>(c.f.begin(), c.f.end());
+  }
+  bool find_layernorm(size_t ni, const std::vector<int64_t>& xs, LnMatch* m) {
+    const Node& rm = g.nodes[ni];
+    const int64_t rk = (int64_t)xs.size(), D = xs.back();
+    if (!last_axis_mean(rm, rk)) return false;
+    const std::string& x = rm.in[0];
+    const int sb = sole_consumer(rm.out[0], ni);
+    if (sb < 0 || g.nodes[sb].op != "Sub" || g.nodes[sb].in.size() != 2 || g.nodes[sb].in[0] != x ||
+        g.nodes[sb].in[1] != rm.out[0])
+      return false;
+    const std::string& d = g.nodes[sb].out[0];
+    for (const IO& o : g.outputs)
+      if (o.name == d) return false;
+    // d's readers: its square and the Div, nothing else
+    int sq = -1, dv = -1, reads = 0;
+    for (size_t k = (size_t)sb + 1; k < g.nodes.size(); ++k)
+      for (const std::string& i : g.nodes[k].in)
+        if (i == d) {
+          ++reads;
+          const Node& c = g.nodes[k];
+          double e;
+          if (c.op == "Pow" && c.in.size() == 2 && c.in[0] == d && scalar_of(c.in[1], &e) && e == 2.0) sq = (int)k;
+          else if (c.op == "Mul" && c.in.size() == 2 && c.in[0] == d && c.in[1] == d) sq = (int)k;
+          else if (c.op == "Div" && c.in.size() == 2 && c.in[0] == d && c.in[1] != d) dv = (int)k;
+          else return false;
+        }
+    if (sq < 0 || dv < 0 || reads != (g.nodes[sq].op == "Mul" ? 3 : 2) || consumers[d] != reads) return false;
+    const int r2 = sole_consumer(g.nodes[sq].out[0], (size_t)sq);
+    if (r2 < 0 || !last_axis_mean(g.nodes[r2], rk)) return false;
+    const int ae = sole_consumer(g.nodes[r2].out[0], (size_t)r2);
+    double eps;
+    if (ae < 0 || g.nodes[ae].op != "Add" || !with_scalar(g.nodes[ae], g.nodes[r2].out[0], &eps)) return false;
+    const int sr = sole_consumer(g.nodes[ae].out[0], (size_t)ae);
+    if (sr < 0 || g.nodes[sr].op != "Sqrt") return false;
+    if (sole_consumer(g.nodes[sr].out[0], (size_t)sr) != dv || g.nodes[dv].in[1] != g.nodes[sr].out[0]) return false;
+    m->eps = (float)eps;
+    m->nodes = {(size_t)sb, (size_t)sq, (size_t)r2, (size_t)ae, (size_t)sr, (size_t)dv};
+    m->out = g.nodes[dv].out[0];
+    size_t last = (size_t)dv;
+    auto affine = [&](const char* op, Const* into) {
+      const int k = sole_consumer(m->out, last);
+      if (k < 0 || g.nodes[k].op != op || g.nodes[k].in.size() != 2) return false;
+      const Node& nd = g.nodes[k];
+      Const t;
+      const Const* c = const_of(nd.in[0] == m->out ? nd.in[1] : nd.in[0], &t);
+      if (!c || c->is_int || (c->numel() != 1 && !(c->numel() == D && c->dims.back() == D))) return false;
+      *into = *c;
+      if (c->numel() == 1) into->f.assign((size_t)D, c->f[0]);
+      m->nodes.push_back((size_t)k);
+      m->out = nd.out[0];
+      last = (size_t)k;
+      return true;
+    };
+    m->has_gamma = affine("Mul", &m->gamma);
+    m->has_beta = affine("Add", &m->beta);
+    for (size_t q : m->nodes)
+      if (done.count(q)) return false;
+    return true;
+  }
+
+  // ReduceMean over exactly H and W: see plan_reduce_mean
+  bool plan_reduce_mean_hw(size_t, const Node& nd, Ins& in, std::vector<int64_t> axes) {
+    const std::string who = "ReduceMean '" + nd.name + "'";
+    const std::vector<int64_t>& xs = in[0]->shape;
     for (int64_t& a : axes) a = a < 0 ? a + 4 : a;
     std::sort(axes.begin(), axes.end());
     if (axes != std::vector<int64_t>{2, 3}) return fail(who + ": the two spatial axes of an NCHW tensor only");
@@ -1834,14 +2100,15 @@ struct Planner {
   // a following elementwise activation (the SE blocks' Relu / Sigmoid) in a
   // Gemm / MatMul's epilogue (PRelu not: its slope's axis is ambiguous on [M, N]);
   // then the launch
-  bool emit_gemm(size_t ni, const Node& nd, GemmParams& p, const std::vector<int64_t>& os, bool absorb_act) {
-    std::string out = nd.out[0];
-    const int c1 = absorb_act && gemm_act_enabled() ? sole_consumer(out, ni) : -1;
+  // (last: the node whose output the launch writes so far — the MatMul, or the bias Add it absorbed)
+  bool emit_gemm(size_t last, GemmParams& p, const std::vector<int64_t>& os, bool absorb_act) {
+    std::string out = g.nodes[last].out[0];
+    const int c1 = absorb_act && gemm_act_enabled() ? sole_consumer(out, last) : -1;
     if (c1 >= 0 && is_act(g.nodes[c1].op) && g.nodes[c1].op != "PRelu" && act_of(g.nodes[c1], &p.ep, p.N)) {
       done.insert((size_t)c1);
       out = g.nodes[c1].out[0];
     } else if (c1 < 0 && absorb_act && gemm_act_enabled()) {
-      const int mul = hswish_pair(out, ni, &p.ep);
+      const int mul = act_pair(out, last, &p.ep);
       if (mul >= 0) {
         done.insert((size_t)mul);
         out = g.nodes[mul].out[0];
@@ -1876,7 +2143,7 @@ struct Planner {
     p.a = operand(*a);
     p.b = operand(*b);
     if (!p.a || !p.b) return false;
-    return emit_gemm(ni, nd, p, {p.M, p.N}, true);
+    return emit_gemm(ni, p, {p.M, p.N}, true);
   }
 
   bool plan_matmul(size_t ni, const Node& nd, Ins& in) {
@@ -1911,7 +2178,22 @@ struct Planner {
       p.b = operand(*b);
     }
     if (!p.a || !p.b) return false;
-    return emit_gemm(ni, nd, p, os, true);
+    // a Linear layer's bias: Add of a constant [N] (or [1, .., N]) that is all that reads the product
+    size_t last = ni;
+    const int ad = b->is_const ? sole_consumer(nd.out[0], ni) : -1;
+    if (ad >= 0 && g.nodes[ad].op == "Add" && g.nodes[ad].in.size() == 2) {
+      const Node& add = g.nodes[ad];
+      Const tmp;
+      const Const* bc = const_of(add.in[0] == nd.out[0] ? add.in[1] : add.in[0], &tmp);
+      if (bc && !bc->is_int && bc->numel() == p.N && !bc->dims.empty() && bc->dims.back() == p.N &&
+          bc->dims.size() <= os.size()) {
+        if (!(p.c = upload_vec(bc->f))) return false;
+        p.scm = 0; p.scn = 1;
+        done.insert((size_t)ad);
+        last = (size_t)ad;
+      }
+    }
+    return emit_gemm(last, p, os, true);
   }
 
   // com.microsoft MatMulNBits (the q4 layers of a q4f16 export): Y = A @ W^T
@@ -1963,7 +2245,153 @@ struct Planner {
     if (!p.a || !p.b || (bias && !p.c)) return false;
     std::vector<int64_t> os(a->shape.begin(), a->shape.end() - 1);
     os.push_back(N);
-    return emit_gemm(ni, nd, p, os, false);
+    return emit_gemm(ni, p, os, false);
+  }
+
+  // ---- fused attention (vso_attn.hip) --------------------------------------
+  //   MatMul(Q, Transpose(K: last two axes swapped)) [-> Mul | Div by a constant
+  //   scalar] [-> Add(bias)] -> Softmax(last axis) -> MatMul(., V)
+  // every interior value read by the next node only; a Mul by a constant
+  // scalar in front of the first MatMul, on Q or on K, read by that MatMul
+  // only, is part of it.  Found by structure before the walk (find_attention):
+  // the nodes ahead of the second MatMul are done from there on and that
+  // MatMul stands for the pattern.  Its plan (try_plan_attn) sees the shapes:
+  // Q, K, V runtime tensors with equal leading dims, d and dv multiples of 4 up
+  // to kAttnMaxD, a bias whose last two dims are [Nq, Nk] and whose leading ones
+  // are 1 or Q's.  Anything else: the nodes get today's launches, in order.
+  struct AttnFuse {
+    std::vector<size_t> pre;  // the nodes ahead of the second MatMul, in node order (a shared Transpose not among them)
+    std::string q, k, v, bias;  // k: the Transpose's input
+    double scale;
+  };
+  std::map<size_t, AttnFuse> attn;  // by the second MatMul (find_attention)
+
+  // `name` = Mul(t, constant scalar) read by node `by` only: t and the scalar
+  bool scaled_operand(const std::string& name, int by, std::string* t, double* c, int* node) {
+    const int p = producer(name);
+    if (p < 0 || g.nodes[p].op != "Mul" || g.nodes[p].in.size() != 2 || sole_consumer(name, (size_t)p) != by) return false;
+    for (int side = 0; side < 2; ++side)
+      if (scalar_of(g.nodes[p].in[1 - side], c)) {
+        *t = g.nodes[p].in[side];
+        *node = p;
+        return true;
+      }
+    return false;
+  }
+
+  void find_attention() {
+    for (size_t k = 0; k < g.nodes.size(); ++k) {
+      const Node& m1 = g.nodes[k];
+      if (m1.op != "MatMul" || m1.in.size() != 2 || done.count(k)) continue;
+      AttnFuse f;
+      f.scale = 1.0;
+      f.q = m1.in[0];
+      std::string kt = m1.in[1], t;
+      double c;
+      int node;
+      if (scaled_operand(f.q, (int)k, &t, &c, &node)) { f.q = t; f.scale *= c; f.pre.push_back((size_t)node); }
+      if (scaled_operand(kt, (int)k, &t, &c, &node)) { kt = t; f.scale *= c; f.pre.push_back((size_t)node); }
+      const int tr = producer(kt);
+      if (tr < 0 || g.nodes[tr].op != "Transpose") continue;
+      const std::vector<int64_t> perm = g.nodes[tr].ais("perm");
+      const size_t rk = perm.size();
+      bool swap = rk >= 2;
+      for (size_t a = 0; swap && a < rk; ++a) swap = perm[a] == (int64_t)(a + 2 < rk ? a : a + 2 == rk ? rk - 1 : rk - 2);
+      if (!swap) continue;
+      f.k = g.nodes[tr].in[0];
+      // (read by the pattern only: no launch; else the Transpose stays and the fused node reads its input all the same)
+      const int tc = sole_consumer(kt, (size_t)tr);
+      if (tc == (int)k || (tc >= 0 && !f.pre.empty() && tc == (int)f.pre.back())) f.pre.push_back((size_t)tr);
+      f.pre.push_back(k);
+      std::string cur = m1.out[0];
+      int nx = sole_consumer(cur, k);
+      if (nx >= 0 && (g.nodes[nx].op == "Mul" || g.nodes[nx].op == "Div") && with_scalar(g.nodes[nx], cur, &c)) {
+        f.scale = g.nodes[nx].op == "Mul" ? f.scale * c : f.scale / c;
+        f.pre.push_back((size_t)nx);
+        cur = g.nodes[nx].out[0];
+        nx = sole_consumer(cur, (size_t)nx);
+      }
+      if (nx >= 0 && g.nodes[nx].op == "Add" && g.nodes[nx].in.size() == 2 && g.nodes[nx].in[0] != g.nodes[nx].in[1]) {
+        f.bias = g.nodes[nx].in[0] == cur ? g.nodes[nx].in[1] : g.nodes[nx].in[0];
+        f.pre.push_back((size_t)nx);
+        cur = g.nodes[nx].out[0];
+        nx = sole_consumer(cur, (size_t)nx);
+      }
+      if (nx < 0 || g.nodes[nx].op != "Softmax") continue;
+      int64_t ax = g.nodes[nx].ai("axis", g.opset > 0 && g.opset < 13 ? 1 : -1);
+      if (ax < 0) ax += (int64_t)rk;
+      if (ax != (int64_t)rk - 1) continue;
+      f.pre.push_back((size_t)nx);
+      cur = g.nodes[nx].out[0];
+      const int m2 = sole_consumer(cur, (size_t)nx);
+      if (m2 < 0 || g.nodes[m2].op != "MatMul" || g.nodes[m2].in.size() != 2 || g.nodes[m2].in[0] != cur ||
+          g.nodes[m2].in[1] == cur)
+        continue;
+      f.v = g.nodes[m2].in[1];
+      bool taken = done.count((size_t)m2) != 0;
+      for (size_t q : f.pre) taken = taken || done.count(q);
+      if (taken) continue;
+      std::sort(f.pre.begin(), f.pre.end());
+      for (size_t q : f.pre) done.insert(q);
+      attn[(size_t)m2] = f;
+    }
+  }
+
+  // The second MatMul `ni` of an attention pattern as one k_attn launch.  1:
+  // planned; 0: not this shape class — the nodes ahead got their own launches
+  // and `ni` goes to plan_matmul; -1: an error.
+  int try_plan_attn(size_t ni) {
+    const AttnFuse f = attn[ni];
+    attn.erase(ni);
+    auto decline = [&]() {
+      for (size_t q : f.pre)
+        if (!plan_node(q)) return -1;
+      return 0;
+    };
+    Value *q = val(f.q), *k = val(f.k), *v = val(f.v), *bias = f.bias.empty() ? nullptr : val(f.bias);
+    if (!q || !k || !v || q->is_const || k->is_const || v->is_const || (!f.bias.empty() && !bias)) return decline();
+    const std::vector<int64_t>&qs = q->shape, &ks = k->shape, &vs = v->shape;
+    const size_t rk = qs.size();
+    if (rk < 2 || rk > (size_t)kMaxDims || ks.size() != rk || vs.size() != rk) return decline();
+    AttnParams p{};
+    int64_t bh = 1;
+    for (size_t a = 0; a + 2 < rk; ++a) {
+      if (ks[a] != qs[a] || vs[a] != qs[a]) return decline();
+      bh *= qs[a];
+      p.lead[a] = (int)qs[a];
+    }
+    p.nlead = (int)rk - 2;
+    const int64_t Nq = qs[rk - 2], d = qs[rk - 1], Nk = ks[rk - 2], dv = vs[rk - 1];
+    if (ks[rk - 1] != d || vs[rk - 2] != Nk || bh < 1 || Nq < 1 || Nk < 1 || bh * Nq * std::max(d, dv) >= (1LL << 31) ||
+        bh * Nk * std::max(d, dv) >= (1LL << 31) || !std::isfinite(f.scale))
+      return decline();
+    if (bias) {
+      const std::vector<int64_t>& bs = bias->shape;
+      const size_t rb = bs.size();
+      if (rb < 2 || rb > rk || bs[rb - 2] != Nq || bs[rb - 1] != Nk) return decline();
+      std::vector<int64_t> st;
+      fill_strides(bs, &st);
+      for (size_t a = 0; a + 2 < rb; ++a) {
+        const size_t qa = a + rk - rb;
+        if (bs[a] != 1 && bs[a] != qs[qa]) return decline();
+        p.bstr[qa] = bs[a] == 1 ? 0 : st[a];
+      }
+    }
+    p.BH = (int)bh; p.Nq = (int)Nq; p.Nk = (int)Nk; p.d = (int)d; p.dv = (int)dv;
+    p.scale = (float)f.scale;
+    for (const std::string* n : {&f.q, &f.k, &f.v, &f.bias})
+      if (!n->empty()) flush_input(*n);
+    p.q = dptr(*q); p.k = dptr(*k); p.v = dptr(*v);
+    if (bias && !(p.bias = operand(*bias))) return -1;
+    std::vector<int64_t> os(qs.begin(), qs.end() - 1);
+    os.push_back(dv);
+    // (a placeholder output for the support test: the real one is made once the plan is taken)
+    p.y = dptr(*q);
+    if (!attn_supported(p)) return decline();
+    if (!(p.y = make_out(g.nodes[ni].out[0], os))) return -1;
+    emit(attn_kernel_name(p), p, launch_attn);
+    s->attn_nodes++;
+    return 1;
   }
 
   // ---- the walk ------------------------------------------------------------
@@ -1984,6 +2412,8 @@ struct Planner {
         {"PRelu", &Planner::plan_activation}, {"LeakyRelu", &Planner::plan_activation},
         {"Sigmoid", &Planner::plan_activation}, {"Tanh", &Planner::plan_activation},
         {"HardSigmoid", &Planner::plan_activation}, {"HardSwish", &Planner::plan_activation},
+        {"Gelu", &Planner::plan_activation}, {"Erf", &Planner::plan_activation},
+        {"LayerNormalization", &Planner::plan_layer_norm},
         {"ConvTranspose", &Planner::plan_conv_transpose}, {"ReduceMean", &Planner::plan_reduce_mean},
         {"Add", &Planner::plan_arith}, {"Sub", &Planner::plan_arith},
         {"Mul", &Planner::plan_arith}, {"Div", &Planner::plan_arith},
@@ -2003,6 +2433,10 @@ struct Planner {
   // input resolution, then: a constant node is folded on the host, a runtime
   // node goes to its operator's plan
   bool plan_node(size_t ni) {
+    if (attn.count(ni)) {  // the second MatMul of an attention pattern: one k_attn launch, or the nodes as they are
+      const int r = try_plan_attn(ni);
+      if (r != 0) return r > 0;
+    }
     const Node& nd = g.nodes[ni];
     const std::string& op = nd.op;
     Ins in;
@@ -2039,6 +2473,8 @@ struct Planner {
       s->in_bufs.push_back(vals[g.inputs[k].name].buf);
     }
     find_hswish();
+    find_gelu();
+    if (attn_enabled()) find_attention();
     find_residual_fusions();
     find_ibnorm();
     find_concat_direct();

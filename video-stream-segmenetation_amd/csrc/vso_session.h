@@ -53,6 +53,7 @@ struct vso_session {
   int conv_precision = 0;  // ConvPrec
   int tile_convs = 0;      // convolutions planned on k_conv_tile
   int ir_blocks = 0;       // inverted residual blocks planned on k_ir
+  int attn_nodes = 0;      // attention patterns planned on k_attn (vso_attn_count)
   hipStream_t stream = nullptr;
   std::string err;
   std::vector<std::string> in_names, out_names;
