@@ -21,10 +21,13 @@
  * broadcasting), MaxPool, AveragePool, GlobalAveragePool, ReduceMean (over H
  * and W; over the last axis inside a decomposed LayerNorm), Pad (constant),
  * Concat, Split, Slice, Transpose,
- * Reshape, Flatten, Squeeze, Unsqueeze, Identity, Dropout, Cast (float),
+ * Reshape, Flatten, Squeeze, Unsqueeze, Identity, Dropout, Cast (float; of
+ * an index tensor also INT64, INT32, UINT8),
  * Resize/Upsample (nearest, linear; half_pixel, pytorch_half_pixel,
  * align_corners, asymmetric), InstanceNormalization, BatchNormalization,
- * LayerNormalization, MatMul, Gemm, Softmax, Pow and Sqrt (inside a
+ * LayerNormalization, MatMul, Gemm, Softmax, LogSoftmax, ArgMax, ReduceMax
+ * (the last three over the channel axis), Gather (one constant index), Equal
+ * (inside ArgMax -> Equal -> Cast), Pow and Sqrt (inside a
  * decomposed LayerNorm), and Shape, Gather, Constant, ConstantOfShape,
  * Floor, Ceil, Cast, Sqrt, Erf, Pow on constants.  For q4f16 exports (model_q4f16.onnx's
  * form): float16 initializers, Cast to FLOAT16 (values rounded to halves and
@@ -35,7 +38,8 @@
  * with VSO_E_UNSUPPORTED naming the node.
  *
  * Attributes (tests/op_cases.py, tests/op_cases_deconv.py and
- * tests/op_cases_attn.py are the tables the sessions are held to):
+ * tests/op_cases_attn.py and tests/op_cases_head.py are the tables the
+ * sessions are held to):
  *   opset_import          read; it selects Softmax's form and Split's default.
  *   Conv                  2-D, constant weights and bias; group, strides,
  *                         dilations (0 or 2 values each), pads (0 or 4 values),
@@ -167,8 +171,46 @@
  *                         Softmax read elsewhere, other axes transposed, d = 6
  *                         or 132, a constant K — keeps the five launches.
  *   Softmax               the last axis; below opset 13 the input flattened to
- *                         2-D at axis (default 1), every row normalised.
- *                         Refused: another axis from opset 13 on.
+ *                         2-D at axis (default 1), every row normalised.  From
+ *                         opset 13 on also the channel axis (1 or -3) of rank-4
+ *                         input: a class head, below.  Refused: any other axis
+ *                         from opset 13 on.
+ *   LogSoftmax            opset 13 on, the channel axis (1 or -3) of rank-4
+ *                         input: x - max - log(sum exp(x - max)).  Refused: any
+ *                         other axis, rank or opset.
+ *   ArgMax                rank-4 input, axis 1 or -3; keepdims 0 or 1;
+ *                         select_last_index 0 (the first index of the maximum)
+ *                         or 1 (the last); fewer than 2^24 classes.  The result
+ *                         is an index tensor: float32 in HBM holding the exact
+ *                         integer (vso_output_type).  Refused: any other axis or
+ *                         rank.
+ *   ReduceMax             rank-4 input; axes (attribute, or constant input from
+ *                         opset 18) exactly [1] or [-3]; keepdims 0 or 1.
+ *                         Refused: every other axis set or rank.
+ *   class heads           each of the four above is one k_class_head launch
+ *                         (vso_head.hip: a thread per pixel, the classes reduced
+ *                         in registers).  Fused into that launch, every interior
+ *                         value read by the next node only (vso_head_count):
+ *                         a linear Resize (any of the four transformations,
+ *                         constant scales or sizes) in front of it — each logit
+ *                         interpolated on the fly with k_resize's arithmetic, the
+ *                         full-size logits never written; behind a Softmax, a
+ *                         Slice (axis 1, step 1), a Split with one used output
+ *                         or a Gather (axis 1, one constant index) — only those
+ *                         channels are written; behind an ArgMax, Equal(constant
+ *                         scalar, int64 or float) -> Cast(to FLOAT) — 1.0 where
+ *                         the label is that class.  A near miss (the Resize or
+ *                         the Softmax read twice, a nearest Resize, a Slice with
+ *                         step 2) keeps separate launches with the same values.
+ *   Equal                 inside ArgMax -> Equal -> Cast only.  Refused elsewhere.
+ *   Gather                of a runtime tensor: a constant scalar or one-element
+ *                         index (negative accepted), any axis; a strided copy,
+ *                         the axis dropped for a scalar index.  Refused: any
+ *                         other index shape, a runtime index.
+ *   Cast                  to FLOAT: an alias; to FLOAT16: rounded to halves;
+ *                         of an index tensor (an ArgMax result or a view of it)
+ *                         to INT64, INT32 or UINT8: an alias.  Refused: any
+ *                         other runtime tensor to a non-float type.
  *   BatchNormalization    constant parameters, rank >= 2 (inference form).
  *   InstanceNormalization constant scale and B, rank >= 3.
  *
@@ -238,6 +280,12 @@ int vso_input_name(const vso_session* s, int i, char* buf, int cap);
 int vso_output_name(const vso_session* s, int i, char* buf, int cap);
 int vso_input_shape(const vso_session* s, int i, int64_t* dims, int cap);
 int vso_output_shape(const vso_session* s, int i, int64_t* dims, int cap);
+/* Output i's element type as the model declares it, an ONNX TensorProto code:
+ * 1 FLOAT, 7 INT64, 6 INT32, 2 UINT8 (1 when the model states none).  The
+ * buffers vso_run and vso_run_device fill are float32 whatever it returns — an
+ * integer-typed output (ArgMax labels) holds exact integers in float32, as a
+ * float16-typed value holds exact halves; the hosts convert (ort.py, segment.ts). */
+int vso_output_type(const vso_session* s, int i);
 
 /* Replaces session.run(feeds) (frameProcessorTest.ts:91) / _OrtRun (:53) for
  * host buffers: inputs[i] = float32 data of input i (its shape as above),
@@ -289,6 +337,14 @@ int vso_ir_block_count(const vso_session* s);
  * float64 reference but are not bitwise the fused ones (another order of the
  * same sums). */
 int vso_attn_count(const vso_session* s);
+/* Class heads (see "class heads" above) whose launch stands for more than its
+ * own node: a Resize in front, a channel selection or Equal -> Cast behind.
+ * The head computes on f32 operands in every session precision.  Planning
+ * knob, read once per process: VSO_HEAD=0 keeps the Resize (k_resize), the
+ * plain head and the selection's copy as launches of their own — the same
+ * device functions in the same order, so its outputs are bitwise the fused
+ * plan's (ArgMax -> Equal -> Cast stays one launch: Equal has no kernel). */
+int vso_head_count(const vso_session* s);
 /* ConvTranspose at a stride above 1 (vso_deconv.hip): per output phase
  * ((oy + pad) mod stride, per axis) one stride-1 correlation over the taps
  * ky = phase + j stride, 1 / (sh sw) of the zero-stuffed form's multiply-adds.

@@ -250,6 +250,30 @@ bool attn_supported(const AttnParams& p);
 const char* attn_kernel_name(const AttnParams& p);
 void launch_attn(const AttnParams& p, hipStream_t s);
 
+// A class head (vso_head.hip, k_class_head): a reduction of [N][C][Ho][Wo]
+// logits over the channel axis, a thread per output pixel (four of a row where
+// Wo is a multiple of 4).  The logits are x itself (rz.linear 0: plain form,
+// rz.H x rz.W == Ho x Wo), or the linear Resize `rz` of x [N][C][rz.H][rz.W]
+// (upsampled form: each logit interpolated on the fly with k_resize's own
+// arithmetic, vso_resize.h; the full-size logits are never written).
+//   HEAD_SOFTMAX / HEAD_LOGSOFTMAX: classes [c0, c0 + n) of the (log-)softmax
+//     over all C -> y [N][n][Ho][Wo] (c0 0, n C: the whole operator);
+//   HEAD_ARGMAX: the first (last: select_last_index) index of the maximum, as a
+//     float holding the exact integer (C < 2^24) -> y [N][1][Ho][Wo];
+//   HEAD_ARGMAX_EQ: 1.0 where that index equals k, else 0.0;
+//   HEAD_MAX: the maximum (ReduceMax).
+enum HeadOp : int { HEAD_SOFTMAX = 0, HEAD_LOGSOFTMAX = 1, HEAD_ARGMAX = 2, HEAD_ARGMAX_EQ = 3, HEAD_MAX = 4 };
+struct HeadParams {
+  ResizeParams rz;  // x, N, C, H, W (the source planes), Ho, Wo; sy, sx, ctm and linear 1 in the upsampled form
+  float* y;
+  int op;           // HeadOp
+  int c0, n;        // softmax forms: the classes written
+  int last;         // arg forms: select_last_index
+  float k;          // HEAD_ARGMAX_EQ: the class compared with
+};
+const char* head_kernel_name(const HeadParams& p);
+void launch_head(const HeadParams& p, hipStream_t s);
+
 // A MobileNetV2 inverted residual block — 1x1 expand + Clip -> 3x3 depthwise
 // (stride 1 / 2) + Clip -> 1x1 project (+ the block input) — in one launch
 // (vso_ir.hip, k_ir): output tiles of kIrTH x 16 pixels, all output channels,

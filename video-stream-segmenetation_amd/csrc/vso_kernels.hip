@@ -16,12 +16,13 @@
 //                 pooling, per-row reductions (GlobalAveragePool,
 //                 InstanceNormalization, LayerNormalization, Softmax),
 //                 channel affine (BatchNormalization), Resize and a small
-//                 batched GEMM.  (Fused attention: vso_attn.hip.)
+//                 batched GEMM.  (Fused attention: vso_attn.hip; the class heads: vso_head.hip.)
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
 #include "vso_device.h"
 #include "vso_kernels.h"
+#include "vso_resize.h"
 
 namespace vso {
 
@@ -1462,65 +1463,7 @@ __global__ __launch_bounds__(256) void k_affine(AffineParams p) {
   }
 }
 
-__device__ __forceinline__ float resize_src(int o, float scale, int in, int out, int ctm) {
-  switch (ctm) {
-    case 0: return ((float)o + 0.5f) / scale - 0.5f;
-    case 1: return out > 1 ? ((float)o + 0.5f) / scale - 0.5f : 0.f;
-    case 2: return out > 1 ? (float)o * (float)(in - 1) / (float)(out - 1) : 0.f;
-    default: return (float)o / scale;
-  }
-}
-
-__device__ __forceinline__ int nearest_idx(float v, int mode, int in) {
-  float r;
-  if (mode == 0) r = (v == floorf(v) + 0.5f) ? floorf(v) : rintf(v);        // round_prefer_floor
-  else if (mode == 1) r = floorf(v + 0.5f);                                   // round_prefer_ceil
-  else if (mode == 2) r = floorf(v);
-  else r = ceilf(v);
-  const int i = (int)r;
-  return i < 0 ? 0 : (i > in - 1 ? in - 1 : i);
-}
-
-// The source coordinate with the division by the scale as a multiplication
-// when the scale is a power of two (2, 0.5, ...: the reciprocal is exact, so
-// the value is the division's bit for bit); other scales divide.
-__device__ __forceinline__ float resize_src_fast(int o, float scale, float inv, bool pow2, int in, int out, int ctm) {
-  if ((ctm == 0 || (ctm == 1 && out > 1)) && pow2) return ((float)o + 0.5f) * inv - 0.5f;
-  return resize_src(o, scale, in, out, ctm);
-}
-
-// One output row's source rows (linear) or row (nearest), worked out once
-// for all the outputs of a thread (they share oy).
-struct ResizeRow {
-  const float* r0;
-  const float* r1;
-  float ly;
-};
-
-__device__ __forceinline__ ResizeRow resize_row(const ResizeParams& p, const float* __restrict__ xc, int oy, float inv,
-                                                bool pow2) {
-  const float fy = resize_src_fast(oy, p.sy, inv, pow2, p.H, p.Ho, p.ctm);
-  if (!p.linear) {
-    const float* r = xc + nearest_idx(fy, p.nearest, p.H) * p.W;
-    return {r, r, 0.f};
-  }
-  const float sy = fminf(fmaxf(fy, 0.f), (float)(p.H - 1));
-  const int y0 = (int)sy, y1 = min(y0 + 1, p.H - 1);
-  return {xc + y0 * p.W, xc + y1 * p.W, sy - (float)y0};
-}
-
-__device__ __forceinline__ float resize_col(const ResizeParams& p, const ResizeRow& rw, int ox, float inv, bool pow2) {
-  const float fx = resize_src_fast(ox, p.sx, inv, pow2, p.W, p.Wo, p.ctm);
-  if (!p.linear) return rw.r0[nearest_idx(fx, p.nearest, p.W)];
-  const float sx = fminf(fmaxf(fx, 0.f), (float)(p.W - 1));
-  const int x0 = (int)sx, x1 = min(x0 + 1, p.W - 1);
-  const float ly = rw.ly, lx = sx - (float)x0;
-  const float v00 = rw.r0[x0], v01 = rw.r0[x1], v10 = rw.r1[x0], v11 = rw.r1[x1];
-  return (1.f - ly) * ((1.f - lx) * v00 + lx * v01) + ly * ((1.f - lx) * v10 + lx * v11);
-}
-
-__device__ __forceinline__ bool pow2f(float v) { return v > 0.f && (__float_as_uint(v) & 0x7FFFFFu) == 0; }
-
+// (the Resize arithmetic — resize_src, resize_row, resize_col — is vso_resize.h: the class head shares it)
 // Four consecutive outputs of one row per thread (rows of a multiple of 4:
 // one index split and one source row per 4 outputs, one float4 store; other
 // widths one output per thread), 32-bit index math — the flat 64-bit index's

@@ -292,6 +292,9 @@ int vso_input_name(const vso_session* s, int i, char* buf, int cap) { return s ?
 int vso_output_name(const vso_session* s, int i, char* buf, int cap) { return s ? copy_name(s->out_names, i, buf, cap) : VSO_E_INVALID_ARG; }
 int vso_input_shape(const vso_session* s, int i, int64_t* dims, int cap) { return s ? copy_shape(s->in_shapes, i, dims, cap) : VSO_E_INVALID_ARG; }
 int vso_output_shape(const vso_session* s, int i, int64_t* dims, int cap) { return s ? copy_shape(s->out_shapes, i, dims, cap) : VSO_E_INVALID_ARG; }
+int vso_output_type(const vso_session* s, int i) {
+  return s && i >= 0 && i < (int)s->out_types.size() ? s->out_types[i] : VSO_E_INVALID_ARG;
+}
 
 // inputs -> the session's tensors, the launch list, the outputs back, all on
 // `st`; host: the callers' pointers are host memory, and the call waits
@@ -333,6 +336,7 @@ int vso_launch_count(const vso_session* s) { return s ? (int)s->launches.size() 
 int vso_tile_conv_count(const vso_session* s) { return s ? s->tile_convs : VSO_E_INVALID_ARG; }
 int vso_ir_block_count(const vso_session* s) { return s ? s->ir_blocks : VSO_E_INVALID_ARG; }
 int vso_attn_count(const vso_session* s) { return s ? s->attn_nodes : VSO_E_INVALID_ARG; }
+int vso_head_count(const vso_session* s) { return s ? s->head_nodes : VSO_E_INVALID_ARG; }
 int vso_lane_count(const vso_session* s) { return s ? (s->graph ? s->lanes_used : 0) : VSO_E_INVALID_ARG; }
 
 int vso_launch_name(const vso_session* s, int k, char* buf, int cap) {

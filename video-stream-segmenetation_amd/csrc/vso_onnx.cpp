@@ -218,21 +218,28 @@ bool parse_attr(PB pb, std::string* name, Attr* a, std::string* err) {
   return true;
 }
 
-// ValueInfoProto {name = 1, type = 2 {tensor_type = 1 {shape = 2 {dim = 1 {dim_value = 1}}}}}
+// ValueInfoProto {name = 1, type = 2 {tensor_type = 1 {elem_type = 1, shape = 2 {dim = 1 {dim_value = 1}}}}}
 bool parse_value_info(PB pb, IO* io) {
   uint32_t f, wt;
   while (pb.more() && pb.key(f, wt)) {
     if (f == 1) io->name = pb.str();
     else if (f == 2)
-      pb.sub().each(1, [&](PB tt) { tt.each(2, [&](PB sh) { sh.each(1, [&](PB dm) {
-        int64_t d = -1;
-        uint32_t f5, w5;
-        while (dm.more() && dm.key(f5, w5)) {
-          if (f5 == 1) d = (int64_t)dm.varint();
-          else dm.skip(w5);
+      pb.sub().each(1, [&](PB tt) {
+        uint32_t f3, w3;
+        while (tt.more() && tt.key(f3, w3)) {
+          if (f3 == 1 && w3 == 0) io->elem_type = (int)tt.varint();
+          else if (f3 == 2 && w3 == 2) tt.sub().each(1, [&](PB dm) {
+            int64_t d = -1;
+            uint32_t f5, w5;
+            while (dm.more() && dm.key(f5, w5)) {
+              if (f5 == 1) d = (int64_t)dm.varint();
+              else dm.skip(w5);
+            }
+            io->dims.push_back(d);
+          });
+          else tt.skip(w3);
         }
-        io->dims.push_back(d);
-      }); }); });
+      });
     else pb.skip(wt);
   }
   return !pb.bad;

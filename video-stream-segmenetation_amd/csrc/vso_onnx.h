@@ -68,6 +68,7 @@ struct Node {
 struct IO {
   std::string name;
   std::vector<int64_t> dims;  // -1 = symbolic
+  int elem_type = 0;          // the declared TensorProto.DataType (0: none stated)
 };
 
 struct Graph {

@@ -1,7 +1,7 @@
 // vso_plan.hip — the ONNX sessions' planner: a parsed Graph (vso_onnx.h) and
 // the input shapes -> the session's launch list over preallocated HBM tensors
 // (vso_session.h), at create.  Host code; the kernels are vso_kernels.hip,
-// vso_conv.hip, vso_ir.hip, vso_deconv.hip and vso_attn.hip.
+// vso_conv.hip, vso_ir.hip, vso_deconv.hip, vso_attn.hip and vso_head.hip.
 //
 // Planning rules:
 //  * every shape is static once input 0's shape is fixed; nodes whose inputs
@@ -15,7 +15,11 @@
 //    absorbs them the same way (plan_conv_transpose);
 //  * the fusions found before planning (find_*): IBNorm, strided residuals,
 //    Concat inputs written in place, 2x upsamples computed by their consumer,
-//    the erf form of GELU (one activation), attention (one k_attn launch);
+//    the erf form of GELU (one activation), attention (one k_attn launch),
+//    the linear Resize in front of a class head (find_heads);
+//  * Softmax / LogSoftmax / ArgMax / ReduceMax over the channel axis of a
+//    rank-4 tensor are one k_class_head launch, which also takes that Resize,
+//    a Softmax's channel selection and ArgMax -> Equal -> Cast (plan_*_head);
 //  * a decomposed LayerNorm is found from its first ReduceMean when the walk
 //    reaches it (find_layernorm); a MatMul by a constant absorbs a constant
 //    bias Add, then an activation;
@@ -83,6 +87,13 @@ struct Planner {
   // (hswish_pair), else one k_unary launch (plan_activation).
   std::map<size_t, size_t> hswish;
 
+  // Linear Resizes whose only reader is a Softmax, LogSoftmax, ArgMax or
+  // ReduceMax (find_heads): candidates for the upsampled form of k_class_head
+  std::set<std::string> head_up;
+  // Index tensors: ArgMax outputs (and views of them) — float32 in HBM holding
+  // exact integers, so a Cast of one to an integer type is an alias
+  std::set<std::string> index_vals;
+
   // ---- work left by one node to a later one, by value name -----------------
   // Each entry is set by the producer's plan and cleared by the consumer that
   // takes it, or by the flush_* that launches it after all; run() fails if one
@@ -100,6 +111,10 @@ struct Planner {
   // cat_up: per Concat output, the channel ranges of its inputs still in
   //   up_pending.  Set: plan_concat.  Read by plan_conv_dense and flush_input
   //   (stale ranges are harmless: flush_up of a launched Resize does nothing).
+  // head_pending: a Resize in head_up, planned without an output tensor.  Set:
+  //   plan_resize.  Cleared: emit_head (the head interpolates on the fly), or
+  //   flush_head, which allocates the tensor and launches k_resize after all.
+  std::map<std::string, ResizeParams> head_pending;
   struct UpRange { std::string name; int c0, c1; };
   std::map<std::string, std::vector<UpRange>> cat_up;
   // cat_patch: per cat_direct value, patches re-pointing its producing
@@ -135,6 +150,17 @@ struct Planner {
     if (it == up_pending.end()) return;
     add(resize_kernel_name(*it->second), it->second, launch_resize);
     up_pending.erase(it);
+  }
+  bool flush_head(const std::string& name) {
+    auto it = head_pending.find(name);
+    if (it == head_pending.end()) return true;
+    ResizeParams p = it->second;
+    head_pending.erase(it);
+    Value& v = vals[name];
+    if ((v.buf = new_buf(v.numel())) < 0) return false;
+    p.y = dptr(v);
+    emit(resize_kernel_name(p), p, launch_resize);
+    return true;
   }
   bool flush_tail(const std::string& name) {
     auto t = cat_tail.find(name);
@@ -461,6 +487,8 @@ struct Planner {
   // ---- the A/B knobs that change a plan ------------------------------------
   // VSO_ATTN=0: an attention pattern stays its Transpose, MatMul, scale, bias, Softmax and MatMul launches
   static bool attn_enabled() { static const bool on = env_on("VSO_ATTN"); return on; }
+  // VSO_HEAD=0: a class head's Resize, channel selection and Equal -> Cast keep their own launches
+  static bool head_enabled() { static const bool on = env_on("VSO_HEAD"); return on; }
   // VSO_DECONV_TILE=0: every strided ConvTranspose on k_deconv_direct
   static bool deconv_tile_enabled() { static const bool on = env_on("VSO_DECONV_TILE"); return on; }
   // VSO_DECONV_PAIR=0 / 1: k_deconv_tile<1> (one x phase per workgroup, strided stores) / <2> (both, rows
@@ -1425,10 +1453,12 @@ struct Planner {
   bool plan_view(size_t, const Node& nd, Ins& in) {  // Reshape, Flatten, Squeeze, Unsqueeze: an alias
     std::vector<int64_t> shp;
     if (!infer_view(nd, operands(in), &shp, &err)) return false;
+    if (index_vals.count(nd.in[0])) index_vals.insert(nd.out[0]);
     return set_runtime(nd.out[0], shp, in[0]->buf);
   }
 
   bool plan_alias(size_t, const Node& nd, Ins& in) {  // Identity, Dropout
+    if (index_vals.count(nd.in[0])) index_vals.insert(nd.out[0]);
     return set_runtime(nd.out[0], in[0]->shape, in[0]->buf);
   }
 
@@ -1448,7 +1478,9 @@ struct Planner {
     // float16 storage semantics: round to the nearest half (the values stay
     // f32 in HBM; later ops compute in f32, a superset of the f16 precision)
     if (to == DT_FLOAT16) return plan_unary(nd, *in[0], ACT_F16, 0.f, 0.f);
-    if (to != DT_FLOAT) return fail("Cast of a runtime tensor to a non-float type");
+    // an index tensor holds exact integers in f32: its integer types are the same bytes
+    const bool index = index_vals.count(nd.in[0]) && (to == DT_INT64 || to == DT_INT32 || to == DT_UINT8);
+    if (to != DT_FLOAT && !index) return fail("Cast of a runtime tensor to a non-float type");
     return plan_alias(ni, nd, in);
   }
 
@@ -1866,7 +1898,7 @@ struct Planner {
     return true;
   }
 
-  bool plan_softmax(size_t, const Node& nd, Ins& in) {
+  bool plan_softmax(size_t ni, const Node& nd, Ins& in) {
     const std::vector<int64_t>& xs = in[0]->shape;
     // opset 13 on: along `axis` (default -1), here the last axis only.  Before:
     // the input flattened to 2-D at `axis` (default 1), each row normalised.
@@ -1875,13 +1907,202 @@ struct Planner {
     int64_t ax = nd.ai("axis", flat ? 1 : -1);
     if (ax < 0) ax += rk;
     if (ax < 0 || ax >= rk) return fail("Softmax: axis out of range");
-    if (!flat && ax != rk - 1) return fail("Softmax: last axis only");
+    if (!flat && ax != rk - 1) {
+      if (rk == 4 && ax == 1) return plan_softmax_head(ni, nd, in, HEAD_SOFTMAX);
+      return fail("Softmax: last axis only");
+    }
+    if (!flush_head(nd.in[0])) return false;
     RowParams p{};
     p.x = dptr(*in[0]);
     p.inner = inner_from(xs, (size_t)ax);
     p.rows = in[0]->numel() / std::max<int64_t>(p.inner, 1);
     if (!(p.y = make_out(nd.out[0], xs))) return false;
     emit("vso::k_softmax(vso::RowParams)", p, launch_softmax);
+    return true;
+  }
+
+  // ---- class heads (vso_head.hip) ------------------------------------------
+  static bool is_head_op(const std::string& op) {
+    return op == "Softmax" || op == "LogSoftmax" || op == "ArgMax" || op == "ReduceMax";
+  }
+  // Resizes read by one class head only: plan_resize leaves them to it
+  void find_heads() {
+    for (size_t k = 0; k < g.nodes.size(); ++k) {
+      const Node& nd = g.nodes[k];
+      if (nd.op != "Resize" || nd.out.empty()) continue;
+      const int c = sole_consumer(nd.out[0], k);
+      if (c >= 0 && is_head_op(g.nodes[c].op) && g.nodes[c].in[0] == nd.out[0]) head_up.insert(nd.out[0]);
+    }
+  }
+  // a constant a later node of a pattern reads, when a Constant node after the
+  // pattern's head produces it: folded now
+  Value* const_ahead(const std::string& name) {
+    if (name.empty()) return nullptr;
+    if (!val(name)) {
+      const int p = producer(name);
+      if (p < 0 || g.nodes[p].op != "Constant" || done.count((size_t)p) || !plan_node((size_t)p)) return nullptr;
+      done.insert((size_t)p);
+    }
+    Value* v = val(name);
+    return v && v->is_const ? v : nullptr;
+  }
+  // the channel axis of a rank-4 tensor, as 1 or -3
+  static bool channel_axis(const std::vector<int64_t>& xs, int64_t ax) { return xs.size() == 4 && (ax == 1 || ax == -3); }
+
+  // One k_class_head launch over `in_name` ([N, C, H, W]; its pending Resize
+  // computed on the fly): classes [c0, c0 + n) for the softmax forms -> `out`
+  // of shape `os`.  `fused`: the launch stands for more than its own node.
+  bool emit_head(const std::string& in_name, const std::string& who, int op, int64_t c0, int64_t n, int last, float k,
+                 const std::string& out, const std::vector<int64_t>& os, bool fused) {
+    Value& x = vals[in_name];
+    const std::vector<int64_t> xs = x.shape;
+    HeadParams p{};
+    auto hp = head_pending.find(in_name);
+    if (hp != head_pending.end()) {
+      p.rz = hp->second;
+      head_pending.erase(hp);
+      fused = true;
+    } else {
+      p.rz.x = dptr(x);
+      p.rz.N = (int)xs[0]; p.rz.C = (int)xs[1];
+      p.rz.H = p.rz.Ho = (int)xs[2]; p.rz.W = p.rz.Wo = (int)xs[3];
+      p.rz.sy = p.rz.sx = 1.f;
+    }
+    if (xs[1] < 1) return fail(who + ": no classes");
+    if (x.numel() >= (1LL << 31) || (int64_t)p.rz.N * p.rz.C * p.rz.H * p.rz.W >= (1LL << 31))
+      return fail(who + ": input of 2^31 elements or more");
+    p.op = op; p.c0 = (int)c0; p.n = (int)n; p.last = last; p.k = k;
+    if (!(p.y = make_out(out, os))) return false;
+    emit(head_kernel_name(p), p, launch_head);
+    if (fused && head_enabled()) s->head_nodes++;
+    return true;
+  }
+
+  // Softmax / LogSoftmax over the channel axis.  A Slice (axis 1, step 1), a
+  // Split with one used output or a Gather (axis 1, one constant index) that
+  // alone reads the result makes it the selected-channels form.
+  bool plan_softmax_head(size_t ni, const Node& nd, Ins& in, int op) {
+    const std::vector<int64_t> xs = in[0]->shape;
+    const int64_t C = xs[1];
+    int64_t c0 = 0, n = C;
+    std::string out = nd.out[0];
+    std::vector<int64_t> os = xs;
+    const int k = head_enabled() ? sole_consumer(nd.out[0], ni) : -1;
+    if (k >= 0 && g.nodes[k].in[0] == nd.out[0]) {
+      const Node& cn = g.nodes[k];
+      bool take = false;
+      int64_t b = 0, e = 0;
+      if (cn.op == "Slice") {
+        for (size_t q = 1; q < cn.in.size(); ++q) const_ahead(cn.in[q]);
+        if (slice_range(cn, C, &b, &e) && e > b) { take = true; c0 = b; n = e - b; os[1] = n; out = cn.out[0]; }
+      } else if (cn.op == "Split") {
+        const Value* sp = cn.in.size() > 1 ? const_ahead(cn.in[1]) : nullptr;
+        int used = -1, nused = 0;
+        for (size_t q = 0; q < cn.out.size(); ++q) {
+          bool u = !cn.out[q].empty() && consumers[cn.out[q]] > 0;
+          for (const IO& o : g.outputs) u = u || (!cn.out[q].empty() && o.name == cn.out[q]);
+          if (u) { used = (int)q; ++nused; }
+        }
+        int64_t ax = 0;
+        std::vector<int64_t> sizes;
+        if (nused == 1 && (cn.in.size() < 2 || cn.in[1].empty() || sp) && split_sizes(cn, xs, sp, &ax, &sizes) && ax == 1 &&
+            sizes[used] > 0) {
+          for (int q = 0; q < used; ++q) b += sizes[q];
+          take = true; c0 = b; n = sizes[used]; os[1] = n; out = cn.out[used];
+        }
+        err.clear();  // (a Split this declined reports its own error when it is planned)
+      } else if (cn.op == "Gather" && cn.in.size() > 1) {
+        const Value* iv = const_ahead(cn.in[1]);
+        int64_t ax = cn.ai("axis", 0);
+        if (ax < 0) ax += 4;
+        if (iv && ax == 1 && iv->c.numel() == 1 && iv->c.dims.size() <= 1) {
+          int64_t idx = ints(*iv)[0];
+          if (idx < 0) idx += C;
+          if (idx >= 0 && idx < C) {
+            take = true; c0 = idx; n = 1; out = cn.out[0];
+            if (iv->c.dims.empty()) os = {xs[0], xs[2], xs[3]};
+            else os[1] = 1;
+          }
+        }
+      }
+      if (take) done.insert((size_t)k);
+    }
+    return emit_head(nd.in[0], nd.op + " '" + nd.name + "'", op, c0, n, 0, 0.f, out, os, out != nd.out[0]);
+  }
+
+  bool plan_log_softmax(size_t ni, const Node& nd, Ins& in) {
+    const bool flat = g.opset > 0 && g.opset < 13;
+    if (flat || !channel_axis(in[0]->shape, nd.ai("axis", -1)))
+      return fail("LogSoftmax '" + nd.name + "': the channel axis of rank-4 input only (opset 13 on)");
+    return plan_softmax_head(ni, nd, in, HEAD_LOGSOFTMAX);
+  }
+
+  // ArgMax over the channel axis: the index as a float holding the exact
+  // integer (an index tensor: plan_cast).  ArgMax -> Equal(constant scalar) ->
+  // Cast(FLOAT), each read by the next only, is the ArgMax == k form — with
+  // VSO_HEAD=0 too: Equal has no launch of its own.
+  bool plan_argmax(size_t ni, const Node& nd, Ins& in) {
+    const std::string who = "ArgMax '" + nd.name + "'";
+    const std::vector<int64_t> xs = in[0]->shape;
+    if (!channel_axis(xs, nd.ai("axis", 0))) return fail(who + ": the channel axis of rank-4 input only");
+    if (xs[1] >= (1 << 24)) return fail(who + ": 2^24 classes or more");
+    const int64_t keep = nd.ai("keepdims", 1), last = nd.ai("select_last_index", 0);
+    if ((keep != 0 && keep != 1) || (last != 0 && last != 1)) return fail(who + ": keepdims / select_last_index must be 0 or 1");
+    const std::vector<int64_t> os = keep ? std::vector<int64_t>{xs[0], 1, xs[2], xs[3]} : std::vector<int64_t>{xs[0], xs[2], xs[3]};
+    const int k1 = sole_consumer(nd.out[0], ni);
+    if (k1 >= 0 && g.nodes[k1].op == "Equal" && g.nodes[k1].in.size() == 2) {
+      const Node& eq = g.nodes[k1];
+      const Value* cv = const_ahead(eq.in[0] == nd.out[0] ? eq.in[1] : eq.in[0]);
+      const int k2 = sole_consumer(eq.out[0], (size_t)k1);
+      if (cv && cv->c.numel() == 1 && k2 >= 0 && g.nodes[k2].op == "Cast" && g.nodes[k2].ai("to", DT_FLOAT) == DT_FLOAT) {
+        done.insert((size_t)k1);
+        done.insert((size_t)k2);
+        const float kv = cv->c.is_int ? (float)cv->c.i[0] : cv->c.f[0];
+        return emit_head(nd.in[0], who, HEAD_ARGMAX_EQ, 0, 1, (int)last, kv, g.nodes[k2].out[0], os, true);
+      }
+    }
+    if (!emit_head(nd.in[0], who, HEAD_ARGMAX, 0, 1, (int)last, 0.f, nd.out[0], os, false)) return false;
+    index_vals.insert(nd.out[0]);
+    return true;
+  }
+
+  // ReduceMax over the channel axis alone
+  bool plan_reduce_max(size_t, const Node& nd, Ins& in) {
+    const std::string who = "ReduceMax '" + nd.name + "'";
+    const std::vector<int64_t> xs = in[0]->shape;
+    std::vector<int64_t> axes = nd.ais("axes");
+    if (in.size() > 1 && in[1]) {  // opset 18 on: an input
+      if (!in[1]->is_const) return fail(who + ": constant axes only");
+      axes = ints(*in[1]);
+    }
+    if (axes.size() != 1 || !channel_axis(xs, axes[0])) return fail(who + ": over the channel axis of rank-4 input only");
+    const int64_t keep = nd.ai("keepdims", 1);
+    if (keep != 0 && keep != 1) return fail(who + ": keepdims must be 0 or 1");
+    const std::vector<int64_t> os = keep ? std::vector<int64_t>{xs[0], 1, xs[2], xs[3]} : std::vector<int64_t>{xs[0], xs[2], xs[3]};
+    return emit_head(nd.in[0], who, HEAD_MAX, 0, 1, 0, 0.f, nd.out[0], os, false);
+  }
+
+  // Gather of a runtime tensor by one constant index: a strided copy, the axis
+  // dropped for a scalar index
+  bool plan_gather(size_t, const Node& nd, Ins& in) {
+    const std::string who = "Gather '" + nd.name + "'";
+    const std::vector<int64_t>& xs = in[0]->shape;
+    const size_t rk = xs.size();
+    if (in.size() < 2 || !in[1] || !in[1]->is_const) return fail(who + ": constant indices only");
+    if (in[0]->is_const) return fail(who + ": constant data with a runtime index");
+    if (in[1]->c.numel() != 1 || in[1]->c.dims.size() > 1) return fail(who + ": a scalar or one-element index only");
+    int64_t ax = nd.ai("axis", 0);
+    if (ax < 0) ax += (int64_t)rk;
+    if (ax < 0 || ax >= (int64_t)rk) return fail(who + ": axis out of range");
+    int64_t idx = ints(*in[1])[0];
+    if (idx < 0) idx += xs[ax];
+    if (idx < 0 || idx >= xs[ax]) return fail(who + ": index out of range");
+    std::vector<int64_t> os = xs, start(rk, 0);
+    os[ax] = 1;
+    start[ax] = idx;
+    if (index_vals.count(nd.in[0])) index_vals.insert(nd.out[0]);
+    if (!plan_copy_out(nd.out[0], os, dptr(*in[0]), xs, start, std::vector<int64_t>(rk, 1), {}, 0.f)) return false;
+    if (in[1]->c.dims.empty()) vals[nd.out[0]].shape.erase(vals[nd.out[0]].shape.begin() + ax);
     return true;
   }
 
@@ -1980,13 +2201,13 @@ struct Planner {
     return true;
   }
 
-  bool plan_split(size_t, const Node& nd, Ins& in) {
-    const std::vector<int64_t>& xs = in[0]->shape;
+  // a Split's axis and part sizes (split: the attribute's or the input's values, or null)
+  bool split_sizes(const Node& nd, const std::vector<int64_t>& xs, const Value* split, int64_t* axis,
+                   std::vector<int64_t>* sizes) {
     int64_t ax = nd.ai("axis", 0);
-    const size_t rk = xs.size();
-    if (ax < 0) ax += (int64_t)rk;
+    if (ax < 0) ax += (int64_t)xs.size();
     std::vector<int64_t> sp = nd.ais("split");
-    if (in.size() > 1 && in[1]) sp = in[1]->c.i;
+    if (split) sp = split->c.i;
     const int64_t k = (int64_t)nd.out.size();
     if (sp.empty()) {
       // opset 18: ceil-sized parts, the last one smaller; before, even parts only
@@ -1998,6 +2219,18 @@ struct Planner {
     int64_t sum = 0;
     for (int64_t v : sp) sum += v;
     if ((int64_t)sp.size() != k || sum != xs[ax]) return fail("Split '" + nd.name + "': sizes do not add up to the axis");
+    *axis = ax;
+    *sizes = sp;
+    return true;
+  }
+
+  bool plan_split(size_t, const Node& nd, Ins& in) {
+    const std::vector<int64_t>& xs = in[0]->shape;
+    const size_t rk = xs.size();
+    int64_t ax = 0;
+    std::vector<int64_t> sp;
+    if (!split_sizes(nd, xs, in.size() > 1 ? in[1] : nullptr, &ax, &sp)) return false;
+    const int64_t k = (int64_t)nd.out.size();
     int64_t off = 0;
     for (int64_t q = 0; q < k; ++q) {
       std::vector<int64_t> os = xs;
@@ -2085,6 +2318,13 @@ struct Planner {
     if (nd.as("keep_aspect_ratio_policy", "stretch") != "stretch")
       return fail("Resize: keep_aspect_ratio_policy " + nd.as("keep_aspect_ratio_policy", "") + " is not supported");
     p.x = dptr(*in[0]);
+    if (head_up.count(nd.out[0]) && p.linear && p.Ho > 0 && p.Wo > 0 && (long)p.N * p.C * p.Ho * p.Wo < (1L << 31)) {
+      Value v;  // no tensor yet: the class head reading it interpolates on the fly (or flush_head makes it)
+      v.shape = {xs[0], xs[1], p.Ho, p.Wo};
+      vals[nd.out[0]] = v;
+      head_pending[nd.out[0]] = p;
+      return true;
+    }
     if (!(p.y = make_out(nd.out[0], {xs[0], xs[1], p.Ho, p.Wo}))) return false;
     if ((long)p.N * p.C * p.Ho * p.Wo >= (1L << 31)) return fail("Resize: output of 2^31 elements or more");
     std::shared_ptr<ResizeParams> pp;
@@ -2421,7 +2661,9 @@ struct Planner {
         {"GlobalAveragePool", &Planner::plan_global_pool},
         {"InstanceNormalization", &Planner::plan_instance_norm},
         {"BatchNormalization", &Planner::plan_batch_norm},
-        {"Softmax", &Planner::plan_softmax}, {"Transpose", &Planner::plan_transpose}, {"Pad", &Planner::plan_pad},
+        {"Softmax", &Planner::plan_softmax}, {"LogSoftmax", &Planner::plan_log_softmax},
+        {"ArgMax", &Planner::plan_argmax}, {"ReduceMax", &Planner::plan_reduce_max}, {"Gather", &Planner::plan_gather},
+        {"Transpose", &Planner::plan_transpose}, {"Pad", &Planner::plan_pad},
         {"Concat", &Planner::plan_concat}, {"Split", &Planner::plan_split}, {"Slice", &Planner::plan_slice},
         {"Resize", &Planner::plan_resize}, {"Upsample", &Planner::plan_resize},
         {"Gemm", &Planner::plan_gemm}, {"MatMul", &Planner::plan_matmul},
@@ -2450,6 +2692,9 @@ struct Planner {
     }
     if (op != "Conv" && op != "Concat")
       for (const std::string& n : nd.in) flush_up(n);
+    if (!is_head_op(op))
+      for (const std::string& n : nd.in)
+        if (!flush_head(n)) return false;
     if (op == "Shape" || (all_const && !in.empty() && op != "Conv") || op == "Constant") {
       Const r;
       if (!fold(nd, operands(in), &r, &err)) return false;
@@ -2479,11 +2724,13 @@ struct Planner {
     find_ibnorm();
     find_concat_direct();
     if (s->conv_precision != PREC_F32) find_up_fusions();
+    if (head_enabled()) find_heads();
     for (size_t k = 0; k < g.nodes.size(); ++k) {
       if (done.count(k)) continue;
       if (!plan_node(k)) return false;
     }
     if (!up_pending.empty()) return fail("internal: Resize '" + up_pending.begin()->first + "' never launched");
+    if (!head_pending.empty()) return fail("internal: Resize '" + head_pending.begin()->first + "' never computed");
     if (!cat_tail.empty()) return fail("internal: Concat input copy into '" + cat_tail.begin()->first + "' never launched");
     if (!norm_pending.empty()) return fail("internal: InstanceNorm of '" + norm_pending.begin()->first + "' never applied");
     if (!pending_dw.empty()) return fail("internal: depthwise Conv into '" + pending_dw.begin()->first + "' never computed");
@@ -2501,6 +2748,7 @@ struct Planner {
       }
       s->out_names.push_back(o.name);
       s->out_shapes.push_back(v->shape);
+      s->out_types.push_back(o.elem_type ? o.elem_type : (int)DT_FLOAT);
       s->out_bufs.push_back(v->buf);
     }
     return true;

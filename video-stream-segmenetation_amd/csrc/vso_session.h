@@ -54,10 +54,12 @@ struct vso_session {
   int tile_convs = 0;      // convolutions planned on k_conv_tile
   int ir_blocks = 0;       // inverted residual blocks planned on k_ir
   int attn_nodes = 0;      // attention patterns planned on k_attn (vso_attn_count)
+  int head_nodes = 0;      // fused class heads planned on k_class_head (vso_head_count)
   hipStream_t stream = nullptr;
   std::string err;
   std::vector<std::string> in_names, out_names;
   std::vector<std::vector<int64_t>> in_shapes, out_shapes;
+  std::vector<int> out_types;  // each output's declared ONNX element type (vso_output_type; the buffers are f32)
   std::vector<float*> bufs;
   std::vector<int64_t> buf_elems;
   std::vector<int> in_bufs, out_bufs;

@@ -9,7 +9,10 @@ becomes
     session = InferenceSession(path_or_bytes)                      # vso_create
     outputs = session.run({"image": array})                        # vso_run -> {name: np.ndarray}
 
-Tensors are float32 NCHW numpy arrays.  Fails loudly (VsoError) when the
+Tensors are float32 NCHW numpy arrays; an output the model declares int64,
+int32 or uint8 (ArgMax labels) comes back from run() in that dtype, as
+onnxruntime returns it — on the device it is float32 holding exact integers
+(vso_output_type), and run_device hands out those float32 buffers.  Fails loudly (VsoError) when the
 library or an operator is missing: there is no CPU fallback.
 """
 from __future__ import annotations
@@ -22,6 +25,8 @@ from . import lib as _vss_lib
 
 VSO_OK, VSO_E_INVALID_ARG, VSO_E_HIP, VSO_E_PARSE, VSO_E_UNSUPPORTED, VSO_E_OOM = 0, -1, -2, -3, -4, -5
 PRECISIONS = {"f32": 0, "bf16": 1, "f16": 2}  # vso_options.conv_precision
+# vso_output_type's ONNX element types -> what run() returns (anything else: float32)
+OUTPUT_DTYPES = {1: np.float32, 7: np.int64, 6: np.int32, 2: np.uint8}
 
 
 class Options(ctypes.Structure):
@@ -49,6 +54,8 @@ def lib():
             "vso_tile_conv_count": ([P], I),
             "vso_ir_block_count": ([P], I),
             "vso_attn_count": ([P], I),
+            "vso_head_count": ([P], I),
+            "vso_output_type": ([P, I], I),
             "vso_lane_count": ([P], I),
             "vso_destroy": ([P], None),
             "vso_last_error": ([P], ctypes.c_char_p),
@@ -108,6 +115,8 @@ class InferenceSession:
         self.output_names = [self._name(lib().vso_output_name, i) for i in range(no.value)]
         self.input_shapes = [self._shape(lib().vso_input_shape, i) for i in range(ni.value)]
         self.output_shapes = [self._shape(lib().vso_output_shape, i) for i in range(no.value)]
+        self.output_types = [np.dtype(OUTPUT_DTYPES.get(_check(lib().vso_output_type(self._h, i), self._h), np.float32))
+                             for i in range(no.value)]
 
     def _name(self, fn, i):
         buf = ctypes.create_string_buffer(512)
@@ -120,7 +129,8 @@ class InferenceSession:
         return tuple(dims[k] for k in range(n))
 
     def run(self, feeds: dict, output_names=None) -> dict:
-        """session.run(feeds) -> {output name: float32 array} (host memory)."""
+        """session.run(feeds) -> {output name: array} (host memory): float32, or the
+        declared integer dtype of an index output (output_types)."""
         ins = []
         for name, shape in zip(self.input_names, self.input_shapes):
             if name not in feeds:
@@ -133,11 +143,13 @@ class InferenceSession:
         pin = (ctypes.c_void_p * len(ins))(*[a.ctypes.data for a in ins])
         pout = (ctypes.c_void_p * len(outs))(*[o.ctypes.data for o in outs])
         _check(lib().vso_run(self._h, pin, pout), self._h)
+        outs = [o if t == np.float32 else o.astype(t) for o, t in zip(outs, self.output_types)]
         res = dict(zip(self.output_names, outs))
         return {k: res[k] for k in (output_names or self.output_names)}
 
     def run_device(self, in_ptrs, out_ptrs, stream: int = 0):
-        """HBM pointers (one per input / output), enqueued on `stream`."""
+        """HBM pointers (one per input / output), enqueued on `stream`.  Every
+        buffer is float32, an integer-typed output's too (exact integers)."""
         pin = (ctypes.c_void_p * len(in_ptrs))(*in_ptrs)
         pout = (ctypes.c_void_p * len(out_ptrs))(*out_ptrs)
         _check(lib().vso_run_device(self._h, pin, pout, stream or None), self._h)
@@ -158,6 +170,10 @@ class InferenceSession:
     def attn_nodes(self) -> int:
         """Attention patterns planned as one fused launch each (k_attn)."""
         return _check(lib().vso_attn_count(self._h), self._h)
+
+    def head_nodes(self) -> int:
+        """Class heads planned fused with their Resize, channel selection or Equal -> Cast (k_class_head)."""
+        return _check(lib().vso_head_count(self._h), self._h)
 
     def lanes(self) -> int:
         """Capture lanes of the session's graph (0 before its first run)."""

@@ -53,7 +53,8 @@
 //       -> Promise<Uint8Array>   opaque RGBA frames, the person over the background
 //   ortCreate(modelBytes: Uint8Array, inputDims: number[] | null, deviceId, convPrecision) -> session
 //       ONNX sessions (include/vso.h) behind InferenceSession.create (model.ts:14, :38, :61)
-//   ortInfo(session) -> {inputNames, outputNames, inputShapes, outputShapes}
+//   ortInfo(session) -> {inputNames, outputNames, inputShapes, outputShapes, outputTypes, headNodes}
+//                       (outputTypes: vso_output_type's ONNX element types; ortRun's buffers are float32)
 //   ortRun(session, inputs: Float32Array[]) -> Promise<Float32Array[]>   (session.run)
 //   ortDestroy(session)              (throws while a face tracker uses the session)
 //   faceCreate(detector, landmarks, config?, deviceId?) -> tracker
@@ -2113,6 +2114,7 @@ struct OrtSess {
   int users = 0;  // face trackers driving this session
   std::vector<std::string> in_names, out_names;
   std::vector<std::vector<int64_t>> in_shapes, out_shapes;
+  std::vector<int> out_types;  // vso_output_type per output
 };
 
 void finalize_ort(napi_env, void* data, void*) {
@@ -2197,6 +2199,7 @@ napi_value OrtCreate(napi_env env, napi_callback_info info) {
     o->out_names.push_back(name);
     const int r = vso_output_shape(s, k, d, 16);
     o->out_shapes.emplace_back(d, d + std::max(0, std::min(r, 16)));
+    o->out_types.push_back(vso_output_type(s, k));
   }
   napi_value ext;
   NAPI_OK(env, napi_create_external(env, o, finalize_ort, nullptr, &ext));
@@ -2239,6 +2242,15 @@ napi_value OrtInfo(napi_env env, napi_callback_info info) {
   napi_set_named_property(env, r, "outputNames", names_array(env, o->out_names));
   napi_set_named_property(env, r, "inputShapes", shapes_array(env, o->in_shapes));
   napi_set_named_property(env, r, "outputShapes", shapes_array(env, o->out_shapes));
+  napi_value types, e;
+  napi_create_array_with_length(env, o->out_types.size(), &types);
+  for (size_t k = 0; k < o->out_types.size(); ++k) {
+    napi_create_int32(env, o->out_types[k], &e);
+    napi_set_element(env, types, (uint32_t)k, e);
+  }
+  napi_set_named_property(env, r, "outputTypes", types);
+  napi_create_int32(env, vso_head_count(o->s), &e);
+  napi_set_named_property(env, r, "headNodes", e);
   return r;
 }
 
