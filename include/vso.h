@@ -29,7 +29,9 @@
  * (the last three over the channel axis), Gather (one constant index), Equal
  * (inside ArgMax -> Equal -> Cast), Pow and Sqrt (inside a
  * decomposed LayerNorm), and Shape, Gather, Constant, ConstantOfShape,
- * Floor, Ceil, Cast, Sqrt, Erf, Pow on constants.  For q4f16 exports (model_q4f16.onnx's
+ * Floor, Ceil, Cast, Sqrt, Erf, Pow on constants; QuantizeLinear and
+ * DequantizeLinear of runtime tensors (statically quantised models in the QDQ
+ * format, below).  For q4f16 exports (model_q4f16.onnx's
  * form): float16 initializers, Cast to FLOAT16 (values rounded to halves and
  * kept as f32; later ops compute in f32), DequantizeLinear of int8 / uint8 /
  * int4 / uint4 weights (per tensor, per axis, opset-21 blocks; folded at
@@ -38,8 +40,8 @@
  * with VSO_E_UNSUPPORTED naming the node.
  *
  * Attributes (tests/op_cases.py, tests/op_cases_deconv.py and
- * tests/op_cases_attn.py and tests/op_cases_head.py are the tables the
- * sessions are held to):
+ * tests/op_cases_attn.py, tests/op_cases_head.py and tests/op_cases_quant.py
+ * are the tables the sessions are held to):
  *   opset_import          read; it selects Softmax's form and Split's default.
  *   Conv                  2-D, constant weights and bias; group, strides,
  *                         dilations (0 or 2 values each), pads (0 or 4 values),
@@ -211,6 +213,48 @@
  *                         of an index tensor (an ArgMax result or a view of it)
  *                         to INT64, INT32 or UINT8: an alias.  Refused: any
  *                         other runtime tensor to a non-float type.
+ *   QuantizeLinear        opset 10 to 21, of a runtime float32 tensor: y =
+ *                         saturate(round_half_even(x / y_scale) + y_zero_point),
+ *                         a quantised tensor of the zero point's type — uint8
+ *                         [0, 255] (also when it is absent) or int8 [-128,
+ *                         127] — one byte per element in HBM.  Scale and zero
+ *                         point: constants of one element.  One k_quantize
+ *                         launch.  Refused: a runtime scale or zero point,
+ *                         per-axis or blocked quantisation, a zero point (or
+ *                         output_dtype) of any other type — 16-bit, 4-bit,
+ *                         float8 —, saturate 0.
+ *   DequantizeLinear      of a runtime quantised tensor: (x - zero_point) *
+ *                         scale in float32, the same restrictions, one
+ *                         k_dequantize launch; of constants (weights, int32
+ *                         biases): folded at create, as before.  Refused: a
+ *                         runtime input that is not a quantised tensor.  Only
+ *                         DequantizeLinear may read a quantised tensor: any
+ *                         other operator on one is refused.  A quantised graph
+ *                         output follows the index tensors' convention: the
+ *                         buffer holds the exact integers in float32 and
+ *                         vso_output_type reports 2 (UINT8) or 3 (INT8).
+ *   quantised patterns    between a DequantizeLinear and a QuantizeLinear, three
+ *                         patterns run on the integers, one launch each
+ *                         (vso_qconv_count), every interior value read by the
+ *                         next node only: DequantizeLinear(xq) -> Conv(.,
+ *                         DequantizeLinear(Wq), [B]) [-> Relu | Clip(constant
+ *                         bounds)] -> QuantizeLinear with group 1 (k_qconv_tile,
+ *                         v_mfma_i32_16x16x64_i8, any kernel, stride, dilation
+ *                         and pads) or depthwise (k_qconv_dw: group = C, kernel
+ *                         up to 7x7, stride 1 or 2) — Wq a constant int8 /
+ *                         uint8 tensor, scale and zero point per tensor or per
+ *                         output channel (axis 0), Wq - zero point within int8;
+ *                         B a float constant or DequantizeLinear of an int32
+ *                         one — and Add(DequantizeLinear(a), DequantizeLinear(b))
+ *                         [-> Relu] -> QuantizeLinear of equal shapes (k_qadd).
+ *                         A near miss (a DequantizeLinear or the Conv read
+ *                         twice, weights that leave int8) keeps k_dequantize,
+ *                         the float kernel and k_quantize: the same values
+ *                         wherever float32 is exact.  Everything else between
+ *                         Q / DQ pairs (Resize, pools, Concat, Gemm, MatMul,
+ *                         ConvTranspose) runs that way too.  QLinearConv,
+ *                         ConvInteger, MatMulInteger, QLinearMatMul and
+ *                         QLinearAdd (the QOperator format) are refused.
  *   BatchNormalization    constant parameters, rank >= 2 (inference form).
  *   InstanceNormalization constant scale and B, rank >= 3.
  *
@@ -281,10 +325,12 @@ int vso_output_name(const vso_session* s, int i, char* buf, int cap);
 int vso_input_shape(const vso_session* s, int i, int64_t* dims, int cap);
 int vso_output_shape(const vso_session* s, int i, int64_t* dims, int cap);
 /* Output i's element type as the model declares it, an ONNX TensorProto code:
- * 1 FLOAT, 7 INT64, 6 INT32, 2 UINT8 (1 when the model states none).  The
- * buffers vso_run and vso_run_device fill are float32 whatever it returns — an
- * integer-typed output (ArgMax labels) holds exact integers in float32, as a
- * float16-typed value holds exact halves; the hosts convert (ort.py, segment.ts). */
+ * 1 FLOAT, 7 INT64, 6 INT32, 2 UINT8 (1 when the model states none); a quantised
+ * output reports its own type, 2 UINT8 or 3 INT8, whatever the model declares.
+ * The buffers vso_run and vso_run_device fill are float32 whatever it returns —
+ * an integer-typed output (ArgMax labels, a quantised tensor) holds exact
+ * integers in float32, as a float16-typed value holds exact halves; the hosts
+ * convert (ort.py, segment.ts). */
 int vso_output_type(const vso_session* s, int i);
 
 /* Replaces session.run(feeds) (frameProcessorTest.ts:91) / _OrtRun (:53) for
@@ -345,6 +391,17 @@ int vso_attn_count(const vso_session* s);
  * device functions in the same order, so its outputs are bitwise the fused
  * plan's (ArgMax -> Equal -> Cast stays one launch: Equal has no kernel). */
 int vso_head_count(const vso_session* s);
+/* Quantised patterns (see "quantised patterns" above) the session runs on the
+ * integers, one launch each: k_qconv_tile + k_qconv_dw + k_qadd (vso_quant.hip).
+ * k_qconv_tile: an implicit GEMM over K = C kh kw on v_mfma_i32_16x16x64_i8 —
+ * 8-bit activations read (uint8 with the top bit flipped, the zero point folded
+ * as sum x w - zx sum w, spatial padding contributing zx), int32 accumulation,
+ * the requantisation acc (sx sw[m]) + bias[m] -> activation -> / sy -> round
+ * half to even -> + zy -> saturate in the epilogue, 8-bit activations written.
+ * They compute in integers in every session precision: bf16 / f16 sessions are
+ * bitwise the f32 one on them.  Planning knob, read once per process:
+ * VSO_QDQ=0 plans every pattern as k_dequantize, the float kernel, k_quantize. */
+int vso_qconv_count(const vso_session* s);
 /* ConvTranspose at a stride above 1 (vso_deconv.hip): per output phase
  * ((oy + pad) mod stride, per axis) one stride-1 correlation over the taps
  * ky = phase + j stride, 1 / (sh sw) of the zero-stuffed form's multiply-adds.

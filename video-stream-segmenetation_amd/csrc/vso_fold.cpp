@@ -66,6 +66,7 @@ void fold_elementwise(const Node& nd, const Const& x, Const& r) {
     const bool to_int = to == DT_INT64 || to == DT_INT32 || to == DT_INT8 || to == DT_UINT8 || to == DT_BOOL;
     if (to_int && !r.is_int) { r.i.clear(); for (float v : r.f) r.i.push_back((int64_t)v); }
     r.is_int = to_int;
+    r.dtype = (int)to;
     r.f16 = to == DT_FLOAT16;
     if (r.f16)
       for (float& v : r.f) v = round_half(v);

@@ -369,6 +369,77 @@ void launch_deconv_tile(const DeconvParams& p, hipStream_t s);
 void launch_deconv_direct(const DeconvParams& p, hipStream_t s);
 size_t deconv_tile_lds(const DeconvParams& p);
 
+// Statically quantised (QDQ) graphs (vso_quant.hip).  A quantised runtime
+// tensor is 8 bits per element in HBM — the model's own uint8 / int8 values,
+// NCHW, one byte each — and exists between QuantizeLinear and DequantizeLinear
+// only; `sgn` says which of the two types the bytes are.
+//  * k_quantize: y = saturate(rne(x / scale) + zp) of f32 x; k_dequantize:
+//    y = (x - zp) * scale in f32 (scale 1, zp 0: a quantised graph output as
+//    the exact integers in float32).
+//  * the fused forms end in the same requantisation (Requant): the float value
+//    v -> activation (ACT_NONE / ACT_RELU / ACT_CLIP to [lo, hi]) -> v / sy ->
+//    round half to even -> + zy -> saturate to [qmin, qmax].
+struct QuantParams {
+  const float* x;
+  unsigned char* y;
+  long n;
+  float scale;
+  int zp, qmin, qmax;
+};
+struct DequantParams {
+  const unsigned char* x;
+  float* y;
+  long n;
+  float scale;
+  int zp, sgn;
+};
+struct Requant {
+  float sy;
+  int zy, qmin, qmax;
+  int act;
+  float lo, hi;
+};
+// k_qconv_tile: DequantizeLinear -> Conv (group 1) [-> Relu / Clip] ->
+// QuantizeLinear as an implicit GEMM on v_mfma_i32_16x16x64_i8, K = C * kh * kw
+// in the weights' own (c, ky, kx) order, padded with zero weights to Kp (a
+// multiple of kQK); w: int8 (Wq - zw) packed [Mp][Kp], Mp = M rounded up to
+// kQBM.  The MFMA multiplies signed bytes: a uint8 activation is read as
+// xq ^ 0x80 = xq - 128 (xflip 0x80) and carries zx - 128 as its zero point;
+// xpad is that zero point as a byte, what a tap outside the image contributes.
+// corr[m] = zero point * sum_k w[m][k], so acc - corr[m] = sum (x - zx) w.
+// k_qconv_dw: the same pattern of a depthwise Conv (group = C = M) on the VALU,
+// w: int8 (Wq - zw) [C][kh * kw]; a tap outside the image is x - zx = 0.
+constexpr int kQK = 64, kQBM = 64, kQPix = 64;
+struct QConvParams {
+  const unsigned char* x;  // [N][C][H][W]
+  unsigned char* y;        // [N][M][Ho][Wo]
+  const signed char* w;
+  const int* corr;         // [M] (k_qconv_tile)
+  const float* mult;       // [M]: sx * sw[m]
+  const float* bias;       // [M] or null
+  int N, C, H, W, M, Ho, Wo;
+  int kh, kw, sh, sw, dh, dw, pt, pl;
+  int K, Kp, Mp;
+  int xflip, xpad;         // k_qconv_tile
+  int zx, xsgn;            // k_qconv_dw: the activations' zero point and type
+  Requant rq;
+};
+// k_qadd: Add(DequantizeLinear(a), DequantizeLinear(b)) [-> Relu] -> QuantizeLinear, equal shapes
+struct QAddParams {
+  const unsigned char* a;
+  const unsigned char* b;
+  unsigned char* y;
+  long n;
+  float sa, sb;
+  int za, zb, asgn, bsgn;
+  Requant rq;
+};
+void launch_quantize(const QuantParams& p, hipStream_t s);
+void launch_dequantize(const DequantParams& p, hipStream_t s);
+void launch_qconv_tile(const QConvParams& p, hipStream_t s);
+void launch_qconv_dw(const QConvParams& p, hipStream_t s);
+void launch_qadd(const QAddParams& p, hipStream_t s);
+
 const char* conv_kernel_name(const ConvParams& p);
 // a depthwise -> 1x1 pair of N images of P pixels into M channels runs fused
 // on k_conv_pw (vso_kernels.hip: where that measured faster)

@@ -140,6 +140,7 @@ bool parse_tensor(PB pb, std::string* name, Const* c, std::string* err) {
     } else pb.skip(wt);
   }
   if (pb.bad) { *err = "malformed TensorProto"; return false; }
+  c->dtype = dt;
   const int64_t n = c->numel();
   auto set_ints = [&](const std::vector<int64_t>& v) {
     c->is_int = true;
@@ -194,6 +195,14 @@ bool parse_tensor(PB pb, std::string* name, Const* c, std::string* err) {
       set_ints(v);
       break;
     }
+    case DT_UINT16: case DT_INT16: case DT_FLOAT8E4M3FN: case DT_FLOAT8E4M3FNUZ: case DT_FLOAT8E5M2:
+    case DT_FLOAT8E5M2FNUZ:
+      // a type no operator here computes on: the tensor keeps its type and dims, not its values, so that the
+      // node reading it is refused by name (the planner: opaque_type) instead of the whole model by the reader
+      // (only as many elements as the tensor's own data holds: a size that does not match its dims fails below)
+      if ((int64_t)(has_raw ? raw.size() / (dt == DT_UINT16 || dt == DT_INT16 ? 2 : 1) : i32.size()) == n)
+        c->f.assign((size_t)std::max<int64_t>(n, 0), 0.f);
+      break;
     default:
       *err = "tensor data type " + std::to_string(dt) + " is not supported";
       return false;

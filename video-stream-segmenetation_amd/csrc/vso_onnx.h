@@ -15,14 +15,18 @@
 namespace vso_onnx __attribute__((visibility("hidden"))) {
 
 // TensorProto.DataType
-enum { DT_FLOAT = 1, DT_UINT8 = 2, DT_INT8 = 3, DT_INT32 = 6, DT_INT64 = 7, DT_BOOL = 9, DT_FLOAT16 = 10,
-       DT_DOUBLE = 11, DT_UINT4 = 21, DT_INT4 = 22 };
+enum { DT_FLOAT = 1, DT_UINT8 = 2, DT_INT8 = 3, DT_UINT16 = 4, DT_INT16 = 5, DT_INT32 = 6, DT_INT64 = 7, DT_BOOL = 9, DT_FLOAT16 = 10,
+       DT_DOUBLE = 11, DT_FLOAT8E4M3FN = 17, DT_FLOAT8E4M3FNUZ = 18, DT_FLOAT8E5M2 = 19, DT_FLOAT8E5M2FNUZ = 20,
+       DT_UINT4 = 21, DT_INT4 = 22 };
+// 16-bit integer and float8 tensors are read as their type and dims only (vso_onnx.cpp: parse_tensor)
+inline bool opaque_type(int dt) { return dt == DT_UINT16 || dt == DT_INT16 || (dt >= DT_FLOAT8E4M3FN && dt <= DT_FLOAT8E5M2FNUZ); }
 
 // A constant tensor (initializer / attribute / folded value).
 struct Const {
   std::vector<int64_t> dims;
   bool is_int = false;
   bool f16 = false;        // float16-typed (values are exact halves)
+  int dtype = 0;           // an initializer's / tensor attribute's TensorProto.DataType (0: a computed value)
   std::vector<float> f;    // float data (also filled for ints, as doubles would be)
   std::vector<int64_t> i;  // integer data
   int64_t numel() const {

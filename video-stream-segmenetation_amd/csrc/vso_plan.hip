@@ -1,7 +1,7 @@
 // vso_plan.hip — the ONNX sessions' planner: a parsed Graph (vso_onnx.h) and
 // the input shapes -> the session's launch list over preallocated HBM tensors
 // (vso_session.h), at create.  Host code; the kernels are vso_kernels.hip,
-// vso_conv.hip, vso_ir.hip, vso_deconv.hip, vso_attn.hip and vso_head.hip.
+// vso_conv.hip, vso_ir.hip, vso_deconv.hip, vso_attn.hip, vso_head.hip and vso_quant.hip.
 //
 // Planning rules:
 //  * every shape is static once input 0's shape is fixed; nodes whose inputs
@@ -23,6 +23,9 @@
 //  * a decomposed LayerNorm is found from its first ReduceMean when the walk
 //    reaches it (find_layernorm); a MatMul by a constant absorbs a constant
 //    bias Add, then an activation;
+//  * QuantizeLinear / DequantizeLinear of runtime tensors are k_quantize /
+//    k_dequantize over 8-bit buffers; DequantizeLinear -> Conv | Add [-> Relu |
+//    Clip] -> QuantizeLinear run on the integers in one launch (find_qdq);
 //  * every other runtime node is one launch, by the plan_<op> of its operator.
 #include <hip/hip_runtime.h>
 
@@ -2634,6 +2637,365 @@ struct Planner {
     return 1;
   }
 
+  // ---- statically quantised (QDQ) graphs (vso_quant.hip) -------------------
+  // QuantizeLinear of a runtime f32 tensor gives a quantised runtime tensor
+  // (Value::qtype; one byte per element, its buffer a quarter of the floats);
+  // DequantizeLinear of one gives f32 again: k_quantize / k_dequantize, and
+  // between them the float kernels — the plan that always works.  Three
+  // patterns run on the integers instead, one launch each (find_qdq), every
+  // interior value read by the next node only:
+  //   DequantizeLinear(xq) -> Conv(., DequantizeLinear(Wq const), [B]) [-> Relu
+  //   | Clip] -> QuantizeLinear: k_qconv_tile (group 1) or k_qconv_dw (depthwise);
+  //   Add(DequantizeLinear(a), DequantizeLinear(b)) [-> Relu] -> QuantizeLinear
+  //   of equal shapes: k_qadd.
+  // Nothing else may read a quantised tensor.  A quantised graph output is
+  // written out as the exact integers in float32 (a k_dequantize of scale 1,
+  // zero point 0, launched where the tensor is produced).
+  struct QParams {
+    float scale = 1.f;
+    int zp = 0;
+    int type = DT_UINT8;  // DT_UINT8 / DT_INT8
+    bool has_zp = false;
+    int qmin() const { return type == DT_INT8 ? -128 : 0; }
+    int qmax() const { return type == DT_INT8 ? 127 : 255; }
+  };
+  // scale and zero point of a Quantize / DequantizeLinear node over a runtime
+  // tensor: constants of one element each, uint8 / int8; else *why says what
+  // is refused
+  bool q_params(const Node& nd, QParams* q, std::string* why) {
+    const std::string at = nd.op + " '" + nd.name + "': unsupported: ";
+    Const ts, tz;
+    const Const* sc = nd.in.size() > 1 ? const_of(nd.in[1], &ts) : nullptr;
+    if (!sc) return *why = at + "the scale of a runtime tensor must be a constant", false;
+    const bool has_zp = nd.in.size() > 2 && !nd.in[2].empty();
+    const Const* zp = has_zp ? const_of(nd.in[2], &tz) : nullptr;
+    if (has_zp && !zp) return *why = at + "the zero point of a runtime tensor must be a constant", false;
+    if (sc->numel() != 1 || (zp && zp->numel() != 1) || nd.ai("block_size", 0) != 0)
+      return *why = at + "a runtime tensor is quantised per tensor only (one scale, one zero point)", false;
+    if (sc->is_int || sc->f16 || sc->f.empty() || !(sc->f[0] > 0.f) || !std::isfinite(sc->f[0]))
+      return *why = at + "a positive float32 scale only", false;
+    q->scale = sc->f[0];
+    q->has_zp = zp != nullptr;
+    if (zp) {
+      if (!zp->is_int || (zp->dtype != DT_UINT8 && zp->dtype != DT_INT8))
+        return *why = at + "runtime tensors of uint8 and int8 only (zero point of type " + std::to_string(zp->dtype) + ")", false;
+      q->type = zp->dtype;
+      q->zp = (int)zp->i[0];
+    }
+    if (nd.op == "QuantizeLinear" && !zp) {
+      const int64_t od = nd.ai("output_dtype", 0);
+      if (od != 0 && od != DT_UINT8 && od != DT_INT8)
+        return *why = at + "runtime tensors of uint8 and int8 only (output_dtype " + std::to_string(od) + ")", false;
+      if (od) q->type = (int)od;
+    }
+    if (nd.ai("saturate", 1) != 1) return *why = at + "saturate 1 only", false;
+    return true;
+  }
+
+  static bool qdq_enabled() { static const bool on = env_on("VSO_QDQ"); return on; }
+
+  // a new quantised runtime tensor (null: err set); a graph output also gets its float32 form
+  std::map<std::string, int> q_out;  // quantised graph outputs: the float32 buffer holding the exact integers
+  bool is_graph_output(const std::string& name) const {
+    for (const IO& o : g.outputs)
+      if (o.name == name) return true;
+    return false;
+  }
+  unsigned char* make_q_out(const std::string& name, const std::vector<int64_t>& shape, int type) {
+    Value v;
+    v.shape = shape;
+    v.qtype = type;
+    if (v.numel() >= (int64_t{1} << 30)) return fail("quantised tensor '" + name + "': 2^30 elements or more"), nullptr;
+    if ((v.buf = new_buf((v.numel() + 3) / 4)) < 0) return nullptr;
+    vals[name] = v;
+    return reinterpret_cast<unsigned char*>(s->bufs[v.buf]);
+  }
+  const unsigned char* qptr(const Value& v) { return reinterpret_cast<const unsigned char*>(s->bufs[v.buf]); }
+  // after the launch producing quantised `name`: its float32 form when it is a graph output
+  bool q_publish(const std::string& name) {
+    if (!is_graph_output(name)) return true;
+    const Value& v = vals[name];
+    const int b = new_buf(v.numel());
+    if (b < 0) return false;
+    emit("vso::k_dequantize(vso::DequantParams)",
+         DequantParams{qptr(v), s->bufs[b], (long)v.numel(), 1.f, 0, v.qtype == DT_INT8}, launch_dequantize);
+    q_out[name] = b;
+    return true;
+  }
+
+  bool plan_quantize(size_t, const Node& nd, Ins& in) {
+    QParams q;
+    if (!q_params(nd, &q, &err)) return false;
+    Value& x = *in[0];
+    if (x.is_const || x.qtype) return fail(nd.op + " '" + nd.name + "': unsupported: a runtime float32 input only");
+    const float* xp = dptr(x);
+    const long n = (long)x.numel();
+    unsigned char* y = make_q_out(nd.out[0], x.shape, q.type);
+    if (!y) return false;
+    emit("vso::k_quantize(vso::QuantParams)", QuantParams{xp, y, n, q.scale, q.zp, q.qmin(), q.qmax()}, launch_quantize);
+    return q_publish(nd.out[0]);
+  }
+
+  // DequantizeLinear of a runtime tensor (of constants: folded on the host, vso_fold.cpp)
+  bool plan_dequantize(size_t, const Node& nd, Ins& in) {
+    Value& x = *in[0];
+    if (x.is_const) return fail("DequantizeLinear '" + nd.name + "': unsupported: a constant input with a runtime scale");
+    if (!x.qtype)
+      return fail("DequantizeLinear '" + nd.name + "': unsupported: its runtime input is not a quantised tensor");
+    QParams q;
+    if (!q_params(nd, &q, &err)) return false;
+    if (q.has_zp && q.type != x.qtype)
+      return fail("DequantizeLinear '" + nd.name + "': unsupported: the zero point's type differs from the input's");
+    const unsigned char* xp = qptr(x);
+    const long n = (long)x.numel();
+    const int sgn = x.qtype == DT_INT8;
+    const std::vector<int64_t> shape = x.shape;
+    float* y = make_out(nd.out[0], shape);
+    if (!y) return false;
+    emit("vso::k_dequantize(vso::DequantParams)", DequantParams{xp, y, n, q.scale, q.zp, sgn}, launch_dequantize);
+    return true;
+  }
+
+  // Only DequantizeLinear may read a QuantizeLinear's output — its buffer is a quarter of the floats — whichever
+  // plan its reader ends up in: checked on the graph, ahead of the pre-passes that absorb nodes into other launches
+  bool check_quantised_readers() {
+    std::set<std::string> q;
+    for (const Node& nd : g.nodes)
+      if (nd.op == "QuantizeLinear" && !nd.out.empty()) q.insert(nd.out[0]);
+    if (q.empty()) return true;
+    for (const Node& nd : g.nodes)
+      for (size_t k = 0; k < nd.in.size(); ++k)
+        if (q.count(nd.in[k]) && !(nd.op == "DequantizeLinear" && k == 0))
+          return fail(nd.op + " '" + nd.name + "': unsupported: a quantised tensor is read by DequantizeLinear only");
+    return true;
+  }
+
+  struct QFuse {
+    int kind;         // 0 k_qconv_tile, 1 k_qconv_dw, 2 k_qadd
+    int dq_a, dq_b;   // the DequantizeLinear nodes of the runtime operands (dq_b: k_qadd)
+    int dq_w;         // the constant weights' DequantizeLinear
+    int act, q;       // the Relu / Clip (-1: none) and the QuantizeLinear
+  };
+  std::map<size_t, QFuse> qfuse;  // by Conv / Add node (find_qdq)
+
+  // `name` is DequantizeLinear of a runtime tensor, read by node `by` only: that node, or -1
+  int runtime_dq(const std::string& name, size_t by) {
+    const int p = producer(name);
+    if (p < 0 || g.nodes[p].op != "DequantizeLinear" || g.nodes[p].in.empty() || done.count((size_t)p)) return -1;
+    Const t;
+    QParams q;
+    std::string why;
+    if (const_of(g.nodes[p].in[0], &t) || !q_params(g.nodes[p], &q, &why)) return -1;
+    return sole_consumer(name, (size_t)p) == (int)by ? p : -1;
+  }
+  // the constant weights of a fused Conv: int8 / uint8 [M][Cg][kh][kw], scale and zero point per tensor or per
+  // output channel (axis 0), Wq - zw within int8 -> wi [M][Cg * kh * kw], sw [M]
+  bool q_weights(const Node& dq, std::vector<signed char>* wi, std::vector<float>* sw) {
+    Const t0, t1, t2;
+    const Const* w = dq.in.size() > 1 ? const_of(dq.in[0], &t0) : nullptr;
+    const Const* sc = w ? const_of(dq.in[1], &t1) : nullptr;
+    const bool has_zp = dq.in.size() > 2 && !dq.in[2].empty();
+    const Const* zp = has_zp && sc ? const_of(dq.in[2], &t2) : nullptr;
+    if (!w || !sc || (has_zp && !zp) || !w->is_int || (w->dtype != DT_INT8 && w->dtype != DT_UINT8) ||
+        w->dims.size() != 4 || sc->is_int || sc->f16 || dq.ai("block_size", 0) != 0)
+      return false;
+    const int64_t M = w->dims[0], per = w->numel() / std::max<int64_t>(M, 1), ns = sc->numel();
+    if (M < 1 || (ns != 1 && (ns != M || dq.ai("axis", 1) != 0)) || (zp && (zp->numel() != ns || !zp->is_int))) return false;
+    wi->resize((size_t)w->numel());
+    sw->resize((size_t)M);
+    for (int64_t m = 0; m < M; ++m) {
+      (*sw)[m] = sc->f[ns == 1 ? 0 : m];
+      const int64_t z = zp ? zp->i[ns == 1 ? 0 : m] : 0;
+      for (int64_t k = 0; k < per; ++k) {
+        const int64_t v = w->i[m * per + k] - z;
+        if (v < -128 || v > 127) return false;
+        (*wi)[m * per + k] = (signed char)v;
+      }
+    }
+    return true;
+  }
+  bool const_known(const std::string& n) {
+    Const t;
+    return const_of(n, &t) != nullptr;
+  }
+  // [-> Relu | Clip(constant bounds)] -> QuantizeLinear behind `out` (written by node `last`), each read once
+  bool q_tail(const std::string& out, size_t last, bool clip_ok, int* act, int* q) {
+    int c = sole_consumer(out, last);
+    *act = -1;
+    if (c >= 0 && (g.nodes[c].op == "Relu" || (clip_ok && g.nodes[c].op == "Clip")) && g.nodes[c].in[0] == out) {
+      const Node& a = g.nodes[c];
+      for (size_t k = 1; k < a.in.size(); ++k)
+        if (!a.in[k].empty() && !const_known(a.in[k])) return false;
+      *act = c;
+      c = sole_consumer(a.out[0], (size_t)c);
+    }
+    if (c < 0 || g.nodes[c].op != "QuantizeLinear" || g.nodes[c].in.empty()) return false;
+    if (g.nodes[c].in[0] != (*act >= 0 ? g.nodes[*act].out[0] : out)) return false;
+    QParams qp;
+    std::string why;
+    if (!q_params(g.nodes[c], &qp, &why)) return false;
+    *q = c;
+    return true;
+  }
+
+  void find_qdq() {
+    for (size_t k = 0; k < g.nodes.size(); ++k) {
+      const Node& nd = g.nodes[k];
+      if (done.count(k) || nd.out.empty()) continue;
+      QFuse f{0, -1, -1, -1, -1, -1};
+      if (nd.op == "Conv" && nd.in.size() >= 2) {
+        f.dq_a = runtime_dq(nd.in[0], k);
+        f.dq_w = producer(nd.in[1]);
+        if (f.dq_a < 0 || f.dq_w < 0 || g.nodes[f.dq_w].op != "DequantizeLinear") continue;
+        std::vector<signed char> wi;
+        std::vector<float> sw;
+        if (!q_weights(g.nodes[f.dq_w], &wi, &sw)) continue;
+        Const t;
+        const Const* w = const_of(g.nodes[f.dq_w].in[0], &t);
+        const int64_t G = nd.ai("group", 1), M = w->dims[0];
+        // (one channel to one channel is both: the depthwise form where it has the shape)
+        if (G == M && w->dims[1] == 1 && w->dims[2] <= 7 && w->dims[3] <= 7) f.kind = 1;
+        else if (G == 1) f.kind = 0;
+        else continue;
+        if (nd.in.size() > 2 && !nd.in[2].empty() && !const_known(nd.in[2])) {  // a float constant, or DequantizeLinear of one
+          const int pb = producer(nd.in[2]);
+          bool ok = pb >= 0 && g.nodes[pb].op == "DequantizeLinear";
+          for (size_t q = 0; ok && q < g.nodes[pb].in.size(); ++q)
+            ok = g.nodes[pb].in[q].empty() || const_known(g.nodes[pb].in[q]);
+          if (!ok) continue;
+        }
+        if (!q_tail(nd.out[0], k, true, &f.act, &f.q)) continue;
+      } else if (nd.op == "Add" && nd.in.size() == 2 && nd.in[0] != nd.in[1]) {
+        f.kind = 2;
+        f.dq_a = runtime_dq(nd.in[0], k);
+        f.dq_b = runtime_dq(nd.in[1], k);
+        if (f.dq_a < 0 || f.dq_b < 0 || !q_tail(nd.out[0], k, false, &f.act, &f.q)) continue;
+      } else {
+        continue;
+      }
+      for (int q : {f.dq_a, f.dq_b, f.act, f.q})
+        if (q >= 0) done.insert((size_t)q);
+      qfuse[k] = f;
+    }
+  }
+
+  // the pattern cannot run fused after all (shapes, sizes): its DequantizeLinear nodes get their launches now,
+  // the activation and the QuantizeLinear theirs when the walk reaches them
+  int q_unfuse(const QFuse& f) {
+    for (int q : {f.act, f.q})
+      if (q >= 0) done.erase((size_t)q);
+    for (int q : {f.dq_a, f.dq_b})
+      if (q >= 0 && !plan_node((size_t)q)) return -1;
+    return 0;
+  }
+
+  // false: the QuantizeLinear's constants or the Clip's bounds are not values yet (a Constant node placed behind
+  // the pattern's head): the caller leaves the pattern unfused
+  bool q_requant(const QFuse& f, int channels, Requant* rq, int* type) {
+    QParams q;
+    std::string why;
+    if (!q_params(g.nodes[f.q], &q, &why)) return false;
+    Epilogue ep{};
+    if (f.act >= 0 && !act_of(g.nodes[f.act], &ep, channels)) return false;
+    *rq = Requant{q.scale, q.zp, q.qmin(), q.qmax(), ep.act, ep.a0, ep.a1};
+    *type = q.type;
+    return true;
+  }
+
+  // the node heading a pattern of find_qdq: 1 planned as one launch, 0 left to the nodes as they are, -1 failed
+  int try_plan_q(size_t ni) {
+    const QFuse f = qfuse[ni];
+    qfuse.erase(ni);
+    const Node& nd = g.nodes[ni];
+    const Node& da = g.nodes[f.dq_a];
+    Value* a = val(da.in[0]);
+    QParams qa, qb;
+    std::string why;
+    if (!a || a->is_const || !a->qtype || !q_params(da, &qa, &why) || (qa.has_zp && qa.type != a->qtype)) return q_unfuse(f);
+    const int asgn = a->qtype == DT_INT8;
+    if (f.kind == 2) {
+      const Node& db = g.nodes[f.dq_b];
+      Value* b = val(db.in[0]);
+      if (!b || b->is_const || !b->qtype || !q_params(db, &qb, &why) || (qb.has_zp && qb.type != b->qtype) ||
+          b->shape != a->shape)
+        return q_unfuse(f);
+      QAddParams p{};
+      int type;
+      if (!q_requant(f, 0, &p.rq, &type)) return q_unfuse(f);
+      p.a = qptr(*a);
+      p.b = qptr(*b);
+      p.n = (long)a->numel();
+      p.sa = qa.scale; p.sb = qb.scale; p.za = qa.zp; p.zb = qb.zp;
+      p.asgn = asgn; p.bsgn = b->qtype == DT_INT8;
+      const std::string& out = g.nodes[f.q].out[0];
+      const std::vector<int64_t> shape = a->shape;
+      if (!(p.y = make_q_out(out, shape, type))) return -1;
+      emit("vso::k_qadd(vso::QAddParams)", p, launch_qadd);
+      s->qconv_nodes++;
+      return q_publish(out) ? 1 : -1;
+    }
+    // the Conv's geometry from the quantised tensor's shape (the DequantizeLinear's output has no tensor)
+    Value ph;
+    ph.shape = a->shape;
+    vals[da.out[0]] = ph;
+    ConvPlan c;
+    if (!conv_geometry(nd, &c)) return -1;
+    const ConvParams& cp = c.p;
+    std::vector<signed char> wi;
+    std::vector<float> sw;
+    if (!q_weights(g.nodes[f.dq_w], &wi, &sw)) return fail("internal: the weights of a quantised Conv"), -1;
+    const bool dw = f.kind == 1 && !(cp.G == 1 && ((cp.sh != 1 && cp.sh != 2) || (cp.sw != 1 && cp.sw != 2)));
+    QConvParams p{};
+    int type;
+    // (sizes: 32-bit indices with room for a grid stride; K: |x| |w| <= 2^14 per term, so the int32 accumulator
+    // and zero-point correction hold below 2^16 terms)
+    if (!q_requant(f, cp.M, &p.rq, &type) || (int64_t)cp.Cg * cp.kh * cp.kw >= (1 << 16) ||
+        (int64_t)cp.N * cp.C * cp.H * cp.W >= (int64_t{1} << 30) || (int64_t)cp.N * cp.M * cp.Ho * cp.Wo >= (int64_t{1} << 30) ||
+        (dw && (cp.G != cp.C || cp.Cg != 1 || (cp.sh != 1 && cp.sh != 2) || (cp.sw != 1 && cp.sw != 2))) ||
+        (!dw && cp.G != 1)) {
+      vals.erase(da.out[0]);
+      return q_unfuse(f);
+    }
+    p.N = cp.N; p.C = cp.C; p.H = cp.H; p.W = cp.W; p.M = cp.M; p.Ho = cp.Ho; p.Wo = cp.Wo;
+    p.kh = cp.kh; p.kw = cp.kw; p.sh = cp.sh; p.sw = cp.sw; p.dh = cp.dh; p.dw = cp.dw; p.pt = cp.pt; p.pl = cp.pl;
+    p.K = cp.Cg * cp.kh * cp.kw;
+    std::vector<float> mult((size_t)cp.M);
+    for (int m = 0; m < cp.M; ++m) mult[m] = qa.scale * sw[m];
+    if (!(p.mult = upload_vec(mult))) return -1;
+    if (c.has_bias && !(p.bias = upload_vec(c.bias))) return -1;
+    if (dw) {
+      p.zx = qa.zp;
+      p.xsgn = asgn;
+      if (!(p.w = static_cast<const signed char*>(upload_bytes(wi.data(), wi.size())))) return -1;
+    } else {
+      // signed operands: a uint8 activation is read as xq - 128 with the zero point zx - 128
+      const int zxs = asgn ? qa.zp : qa.zp - 128;
+      p.xflip = asgn ? 0 : 0x80;
+      p.xpad = zxs & 0xff;
+      p.Kp = (p.K + kQK - 1) / kQK * kQK;
+      p.Mp = (p.M + kQBM - 1) / kQBM * kQBM;
+      std::vector<signed char> packed((size_t)p.Mp * p.Kp, 0);
+      std::vector<int> corr((size_t)p.M);
+      for (int m = 0; m < p.M; ++m) {
+        int sum = 0;
+        for (int k = 0; k < p.K; ++k) {
+          packed[(size_t)m * p.Kp + k] = wi[(size_t)m * p.K + k];
+          sum += wi[(size_t)m * p.K + k];
+        }
+        corr[m] = zxs * sum;
+      }
+      if (!(p.w = static_cast<const signed char*>(upload_bytes(packed.data(), packed.size())))) return -1;
+      if (!(p.corr = static_cast<const int*>(upload_bytes(corr.data(), corr.size() * 4)))) return -1;
+    }
+    p.x = qptr(*a);
+    const std::string& out = g.nodes[f.q].out[0];
+    if (!(p.y = make_q_out(out, c.oshape, type))) return -1;
+    if (dw) emit("vso::k_qconv_dw(vso::QConvParams)", p, launch_qconv_dw);
+    else emit("vso::k_qconv_tile(vso::QConvParams)", p, launch_qconv_tile);
+    s->qconv_nodes++;
+    return q_publish(out) ? 1 : -1;
+  }
+
   // ---- the walk ------------------------------------------------------------
   static std::vector<Operand> operands(const Ins& in) {
     std::vector<Operand> o;
@@ -2667,7 +3029,8 @@ struct Planner {
         {"Concat", &Planner::plan_concat}, {"Split", &Planner::plan_split}, {"Slice", &Planner::plan_slice},
         {"Resize", &Planner::plan_resize}, {"Upsample", &Planner::plan_resize},
         {"Gemm", &Planner::plan_gemm}, {"MatMul", &Planner::plan_matmul},
-        {"MatMulNBits", &Planner::plan_matmul_nbits}};
+        {"MatMulNBits", &Planner::plan_matmul_nbits},
+        {"QuantizeLinear", &Planner::plan_quantize}, {"DequantizeLinear", &Planner::plan_dequantize}};
     auto it = ops.find(op);
     return it == ops.end() ? nullptr : it->second;
   }
@@ -2677,6 +3040,10 @@ struct Planner {
   bool plan_node(size_t ni) {
     if (attn.count(ni)) {  // the second MatMul of an attention pattern: one k_attn launch, or the nodes as they are
       const int r = try_plan_attn(ni);
+      if (r != 0) return r > 0;
+    }
+    if (qfuse.count(ni)) {  // the Conv / Add of a quantised pattern: one launch on the integers, or the nodes as they are
+      const int r = try_plan_q(ni);
       if (r != 0) return r > 0;
     }
     const Node& nd = g.nodes[ni];
@@ -2690,6 +3057,13 @@ struct Planner {
       in.push_back(v);
       all_const = all_const && v->is_const;
     }
+    // a 16-bit integer or float8 constant (read as its type alone): Quantize / DequantizeLinear of a runtime
+    // tensor say so themselves (q_params), nothing else reads one
+    for (const Value* v : in)
+      if (v && v->is_const && opaque_type(v->c.dtype) &&
+          !((op == "QuantizeLinear" || op == "DequantizeLinear") && in[0] && !in[0]->is_const))
+        return fail(op + " '" + nd.name + "': unsupported: a constant of type " + std::to_string(v->c.dtype) +
+                    " (16-bit integer and float8 tensors are not computed on)");
     if (op != "Conv" && op != "Concat")
       for (const std::string& n : nd.in) flush_up(n);
     if (!is_head_op(op))
@@ -2703,6 +3077,10 @@ struct Planner {
     }
     const PlanOp plan = plan_of(op);
     if (!plan) return fail("unsupported operator " + op + " (node '" + nd.name + "')");
+    if (op != "DequantizeLinear")  // (a quantised tensor's buffer is a quarter of the floats: no float kernel may read it)
+      for (const Value* v : in)
+        if (v && v->qtype)
+          return fail(op + " '" + nd.name + "': unsupported: a quantised tensor is read by DequantizeLinear only");
     return (this->*plan)(ni, nd, in);
   }
 
@@ -2717,6 +3095,7 @@ struct Planner {
       s->in_shapes.push_back(in_shapes[k]);
       s->in_bufs.push_back(vals[g.inputs[k].name].buf);
     }
+    if (!check_quantised_readers()) return false;
     find_hswish();
     find_gelu();
     if (attn_enabled()) find_attention();
@@ -2725,6 +3104,7 @@ struct Planner {
     find_concat_direct();
     if (s->conv_precision != PREC_F32) find_up_fusions();
     if (head_enabled()) find_heads();
+    if (qdq_enabled()) find_qdq();
     for (size_t k = 0; k < g.nodes.size(); ++k) {
       if (done.count(k)) continue;
       if (!plan_node(k)) return false;
@@ -2748,8 +3128,9 @@ struct Planner {
       }
       s->out_names.push_back(o.name);
       s->out_shapes.push_back(v->shape);
-      s->out_types.push_back(o.elem_type ? o.elem_type : (int)DT_FLOAT);
-      s->out_bufs.push_back(v->buf);
+      // (a quantised output: its type whatever the model declares, the buffer q_publish filled)
+      s->out_types.push_back(v->qtype ? v->qtype : o.elem_type ? o.elem_type : (int)DT_FLOAT);
+      s->out_bufs.push_back(v->qtype ? q_out.at(o.name) : v->buf);
     }
     return true;
   }

@@ -10,8 +10,9 @@ becomes
     outputs = session.run({"image": array})                        # vso_run -> {name: np.ndarray}
 
 Tensors are float32 NCHW numpy arrays; an output the model declares int64,
-int32 or uint8 (ArgMax labels) comes back from run() in that dtype, as
-onnxruntime returns it — on the device it is float32 holding exact integers
+int32 or uint8 (ArgMax labels), or that is a quantised uint8 / int8 tensor
+(QuantizeLinear), comes back from run() in that dtype, as onnxruntime returns
+it — on the device it is float32 holding exact integers
 (vso_output_type), and run_device hands out those float32 buffers.  Fails loudly (VsoError) when the
 library or an operator is missing: there is no CPU fallback.
 """
@@ -26,7 +27,7 @@ from . import lib as _vss_lib
 VSO_OK, VSO_E_INVALID_ARG, VSO_E_HIP, VSO_E_PARSE, VSO_E_UNSUPPORTED, VSO_E_OOM = 0, -1, -2, -3, -4, -5
 PRECISIONS = {"f32": 0, "bf16": 1, "f16": 2}  # vso_options.conv_precision
 # vso_output_type's ONNX element types -> what run() returns (anything else: float32)
-OUTPUT_DTYPES = {1: np.float32, 7: np.int64, 6: np.int32, 2: np.uint8}
+OUTPUT_DTYPES = {1: np.float32, 7: np.int64, 6: np.int32, 2: np.uint8, 3: np.int8}
 
 
 class Options(ctypes.Structure):
@@ -55,6 +56,7 @@ def lib():
             "vso_ir_block_count": ([P], I),
             "vso_attn_count": ([P], I),
             "vso_head_count": ([P], I),
+            "vso_qconv_count": ([P], I),
             "vso_output_type": ([P, I], I),
             "vso_lane_count": ([P], I),
             "vso_destroy": ([P], None),
@@ -174,6 +176,10 @@ class InferenceSession:
     def head_nodes(self) -> int:
         """Class heads planned fused with their Resize, channel selection or Equal -> Cast (k_class_head)."""
         return _check(lib().vso_head_count(self._h), self._h)
+
+    def qconv_nodes(self) -> int:
+        """Quantised patterns planned as one launch on the integers each (k_qconv_tile, k_qconv_dw, k_qadd)."""
+        return _check(lib().vso_qconv_count(self._h), self._h)
 
     def lanes(self) -> int:
         """Capture lanes of the session's graph (0 before its first run)."""

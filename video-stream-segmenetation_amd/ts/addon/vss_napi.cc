@@ -53,7 +53,7 @@
 //       -> Promise<Uint8Array>   opaque RGBA frames, the person over the background
 //   ortCreate(modelBytes: Uint8Array, inputDims: number[] | null, deviceId, convPrecision) -> session
 //       ONNX sessions (include/vso.h) behind InferenceSession.create (model.ts:14, :38, :61)
-//   ortInfo(session) -> {inputNames, outputNames, inputShapes, outputShapes, outputTypes, headNodes}
+//   ortInfo(session) -> {inputNames, outputNames, inputShapes, outputShapes, outputTypes, headNodes, qconvNodes}
 //                       (outputTypes: vso_output_type's ONNX element types; ortRun's buffers are float32)
 //   ortRun(session, inputs: Float32Array[]) -> Promise<Float32Array[]>   (session.run)
 //   ortDestroy(session)              (throws while a face tracker uses the session)
@@ -2251,6 +2251,8 @@ napi_value OrtInfo(napi_env env, napi_callback_info info) {
   napi_set_named_property(env, r, "outputTypes", types);
   napi_create_int32(env, vso_head_count(o->s), &e);
   napi_set_named_property(env, r, "headNodes", e);
+  napi_create_int32(env, vso_qconv_count(o->s), &e);
+  napi_set_named_property(env, r, "qconvNodes", e);
   return r;
 }
 
