@@ -31,7 +31,8 @@
  * decomposed LayerNorm), and Shape, Gather, Constant, ConstantOfShape,
  * Floor, Ceil, Cast, Sqrt, Erf, Pow on constants; QuantizeLinear and
  * DequantizeLinear of runtime tensors (statically quantised models in the QDQ
- * format, below).  For q4f16 exports (model_q4f16.onnx's
+ * format, below); DynamicQuantizeLinear, ConvInteger and MatMulInteger
+ * (dynamically quantised models, what quantize_dynamic writes, below).  For q4f16 exports (model_q4f16.onnx's
  * form): float16 initializers, Cast to FLOAT16 (values rounded to halves and
  * kept as f32; later ops compute in f32), DequantizeLinear of int8 / uint8 /
  * int4 / uint4 weights (per tensor, per axis, opset-21 blocks; folded at
@@ -40,8 +41,8 @@
  * with VSO_E_UNSUPPORTED naming the node.
  *
  * Attributes (tests/op_cases.py, tests/op_cases_deconv.py and
- * tests/op_cases_attn.py, tests/op_cases_head.py and tests/op_cases_quant.py
- * are the tables the sessions are held to):
+ * tests/op_cases_attn.py, tests/op_cases_head.py, tests/op_cases_quant.py and
+ * tests/op_cases_dynq.py are the tables the sessions are held to):
  *   opset_import          read; it selects Softmax's form and Split's default.
  *   Conv                  2-D, constant weights and bias; group, strides,
  *                         dilations (0 or 2 values each), pads (0 or 4 values),
@@ -211,7 +212,9 @@
  *                         other index shape, a runtime index.
  *   Cast                  to FLOAT: an alias; to FLOAT16: rounded to halves;
  *                         of an index tensor (an ArgMax result or a view of it)
- *                         to INT64, INT32 or UINT8: an alias.  Refused: any
+ *                         to INT64, INT32 or UINT8: an alias; of an int32
+ *                         tensor (ConvInteger, MatMulInteger) to FLOAT: one
+ *                         conversion per element (k_cast_i32).  Refused: any
  *                         other runtime tensor to a non-float type.
  *   QuantizeLinear        opset 10 to 21, of a runtime float32 tensor: y =
  *                         saturate(round_half_even(x / y_scale) + y_zero_point),
@@ -253,8 +256,60 @@
  *                         wherever float32 is exact.  Everything else between
  *                         Q / DQ pairs (Resize, pools, Concat, Gemm, MatMul,
  *                         ConvTranspose) runs that way too.  QLinearConv,
- *                         ConvInteger, MatMulInteger, QLinearMatMul and
- *                         QLinearAdd (the QOperator format) are refused.
+ *                         QLinearMatMul and QLinearAdd (the QOperator format)
+ *                         are refused.
+ *   DynamicQuantizeLinear opset 11, of a runtime float32 tensor, the whole
+ *                         tensor (batch included), uint8.  The operator text
+ *                         in float32, each step rounded once: mn = min(0, min
+ *                         x), mx = max(0, max x), y_scale = (mx - mn) / 255,
+ *                         y_zero_point = saturate(rne((0 - mn) / y_scale)), y =
+ *                         saturate(rne(x / y_scale) + y_zero_point); mx == mn
+ *                         (all zero; left open by the text) gives scale 1, zero
+ *                         point 0, y 0, as onnxruntime does.  Two launches
+ *                         (k_dyn_minmax, k_dyn_quantize); nothing goes back to
+ *                         the host: y is a quantised uint8 tensor, y_scale a
+ *                         float32 runtime tensor of rank 0, y_zero_point a
+ *                         one-element quantised tensor, each a legal graph
+ *                         output (y and the zero point as UINT8).  y is read by
+ *                         ConvInteger / MatMulInteger (input 0) or
+ *                         DequantizeLinear only, the zero point as their input 2
+ *                         only; y_scale is a float like any other.
+ *   ConvInteger /         input 0 a quantised runtime tensor (uint8 / int8),
+ *   MatMulInteger         its zero point (input 2) one value of that type —
+ *                         a DynamicQuantizeLinear's, or a constant —; the
+ *                         weights (W; B of rank 2) a constant uint8 / int8
+ *                         tensor, their zero point (input 3) a constant of the
+ *                         same type, one value or one per output channel /
+ *                         column.  ConvInteger: auto_pad, dilations, group,
+ *                         kernel_shape, pads, strides as Conv (the same list
+ *                         lengths and refusals).  The exact int32 sum of
+ *                         (x - x_zero_point)(w - w_zero_point): group 1 and
+ *                         C kh kw < 2^15 on k_iconv_tile
+ *                         (v_mfma_i32_16x16x64_i8; MatMulInteger as its 1x1
+ *                         case, rows as pixels), anything else on
+ *                         k_iconv_direct.  The int32 tensor is read by Cast to
+ *                         FLOAT only (k_cast_i32) and is no graph output.
+ *                         Refused: runtime weights, an input 0 that is not a
+ *                         quantised tensor, a runtime weight zero point, a zero
+ *                         point of the wrong size or type, a B of rank other
+ *                         than 2.
+ *   dynamic patterns      ConvInteger | MatMulInteger -> Cast(FLOAT) -> Mul(., s)
+ *                         [-> Add(constant bias)] [-> Relu | Clip(constant
+ *                         bounds)] with s = Mul(x_scale, w_scale) in either
+ *                         operand order — x_scale the y_scale of the
+ *                         DynamicQuantizeLinear that made input 0, w_scale and
+ *                         the bias constants of one value (w_scale) or one per
+ *                         output channel lying along the channel axis ([M,1,1],
+ *                         [1,M,1,1] behind a ConvInteger, [N] behind a
+ *                         MatMulInteger), every interior value and s read by
+ *                         the next node only — is one launch (vso_dynq_count)
+ *                         storing float32 act(float(acc) * (x_scale *
+ *                         w_scale[m]) + bias[m]), each step rounded once: bit
+ *                         for bit what the separate launches store.  The
+ *                         DynamicQuantizeLinear is not part of the pattern: it
+ *                         may feed several layers.  A near miss (the Cast or s
+ *                         read twice, a runtime bias, a w_scale of another size
+ *                         or along another axis) keeps every node's own launch.
  *   BatchNormalization    constant parameters, rank >= 2 (inference form).
  *   InstanceNormalization constant scale and B, rank >= 3.
  *
@@ -402,6 +457,19 @@ int vso_head_count(const vso_session* s);
  * bitwise the f32 one on them.  Planning knob, read once per process:
  * VSO_QDQ=0 plans every pattern as k_dequantize, the float kernel, k_quantize. */
 int vso_qconv_count(const vso_session* s);
+/* Dynamic patterns (see "dynamic patterns" above) the session runs as one
+ * launch each: k_iconv_tile + k_iconv_direct with the float epilogue
+ * (vso_dynq.hip).  k_iconv_tile is k_qconv_tile's implicit GEMM with the
+ * activations' zero point read from HBM and the weights' zero point kept out
+ * of the bytes: with signed bytes x' = x - 128, w' = w - 128 (uint8; int8 as
+ * they are) and zero points moved alike, sum (x - zx)(w - zw[m]) = acc - zx'
+ * sum_k w'[m] - zw'[m] sum_k x'[pixel] + K zx' zw'[m] in wrapping 32-bit
+ * arithmetic, the window sum of x' taken by the threads that stage it.  They
+ * compute in integers in every session precision: bf16 / f16 sessions are
+ * bitwise the f32 one on them.  Planning knob, read once per process:
+ * VSO_DYNQ=0 plans every pattern as the integer launch, k_cast_i32 and the
+ * Mul / Add / Relu / Clip launches — the same bits. */
+int vso_dynq_count(const vso_session* s);
 /* ConvTranspose at a stride above 1 (vso_deconv.hip): per output phase
  * ((oy + pad) mod stride, per axis) one stride-1 correlation over the taps
  * ky = phase + j stride, 1 / (sh sw) of the zero-stuffed form's multiply-adds.

@@ -440,6 +440,66 @@ void launch_qconv_tile(const QConvParams& p, hipStream_t s);
 void launch_qconv_dw(const QConvParams& p, hipStream_t s);
 void launch_qadd(const QAddParams& p, hipStream_t s);
 
+// Dynamically quantised graphs (vso_dynq.hip): DynamicQuantizeLinear,
+// ConvInteger, MatMulInteger.  The byte tensors are the QDQ graphs' (above); an
+// int32 runtime tensor (a ConvInteger / MatMulInteger output nothing fused) is
+// four bytes per element.
+//  * k_dyn_minmax + k_dyn_quantize: DynamicQuantizeLinear of the whole tensor
+//    (uint8): `blocks` (min, max) pairs in `part`, reduced again by every
+//    workgroup of the second launch; y_scale and y_zero_point stay in HBM.
+constexpr int kDynParts = 256;  // (min, max) pairs at the most: one per thread of the second launch
+struct DynQParams {
+  const float* x;
+  unsigned char* y;
+  float* scale;        // y_scale, one float
+  unsigned char* zp;   // y_zero_point, one byte
+  float* part;         // [blocks][2]
+  long n;
+  int blocks;          // workgroups of k_dyn_minmax, <= kDynParts
+};
+//  * k_iconv_tile (group 1, K < 2^15) and k_iconv_direct (any group): the exact
+//    sum_k (x - zx) (w - zw[m]) of ConvInteger, and of MatMulInteger as the 1x1
+//    convolution of N = rows, C = K, H = W = 1.  zx is one byte in HBM, read by
+//    the kernel (null: 0).  w holds signed bytes w' = Wq - 128 (uint8 weights)
+//    or Wq (int8), zw[m] their zero point moved alike (null: all 0), wsum[m] =
+//    sum_k w'[m][k].  k_iconv_tile: w packed [Mp][Kp] as k_qconv_tile's, the
+//    activations read as x ^ xflip; k_iconv_direct: w [M][Cg * kh * kw].
+//    Epilogue: yi (int32) — or, yi null, yf = act(float(v) * (xscale[0] *
+//    wscale[m]) + bias[m]), every step rounded once: the roundings of the
+//    launches Cast, Mul, Mul, Add, Relu | Clip it stands for.
+struct IConvParams {
+  const unsigned char* x;   // [N][C][H][W]
+  const unsigned char* zx;  // the activations' zero point (their type), or null
+  const signed char* w;
+  const int* wsum;          // [M] (k_iconv_tile)
+  const int* zw;            // [M] or null
+  int* yi;                  // [N][M][Ho][Wo], or null: the float epilogue
+  float* yf;
+  const float* xscale;      // one float in HBM
+  const float* wscale;      // [M]
+  const float* bias;        // [M] or null
+  int act;                  // ACT_NONE / ACT_RELU / ACT_CLIP
+  float lo, hi;
+  int N, C, H, W, M, Ho, Wo;
+  int G, Cg, Mg;
+  int kh, kw, sh, sw, dh, dw, pt, pl;
+  int K, Kp, Mp;
+  int xflip;                // 0x80: uint8 activations, 0: int8
+  int rows;                 // k_iconv_tile: H = W = 1, 1x1, no pads — a pixel's K bytes are contiguous (MatMulInteger)
+};
+void launch_dyn_minmax(const DynQParams& p, hipStream_t s);
+void launch_dyn_quantize(const DynQParams& p, hipStream_t s);
+void launch_iconv_tile(const IConvParams& p, hipStream_t s);
+void launch_iconv_direct(const IConvParams& p, hipStream_t s);
+int dyn_blocks(long n);  // k_dyn_minmax's workgroups for n elements
+// Cast of an int32 runtime tensor to float32 (vso_kernels.hip)
+struct CastI32Params {
+  const int* x;
+  float* y;
+  long n;
+};
+void launch_cast_i32(const CastI32Params& p, hipStream_t s);
+
 const char* conv_kernel_name(const ConvParams& p);
 // a depthwise -> 1x1 pair of N images of P pixels into M channels runs fused
 // on k_conv_pw (vso_kernels.hip: where that measured faster)

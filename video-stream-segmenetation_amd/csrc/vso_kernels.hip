@@ -911,6 +911,11 @@ __global__ __launch_bounds__(256) void k_unary(UnaryParams p) {
     p.y[i] = act_apply(p.x[i], p.act, p.a0, p.a1, nullptr, 0, 0);
 }
 
+// Cast of an int32 runtime tensor (a ConvInteger / MatMulInteger output) to float32: one conversion, ties to even
+__global__ __launch_bounds__(256) void k_cast_i32(CastI32Params p) {
+  for (long i = blockIdx.x * 256L + threadIdx.x; i < p.n; i += (long)gridDim.x * 256) p.y[i] = (float)p.x[i];
+}
+
 template <typename I>
 __device__ __forceinline__ void copy_body(const CopyParams& p) {
   for (I i = (I)blockIdx.x * 256 + (I)threadIdx.x; i < (I)p.n; i += (I)gridDim.x * 256) {
@@ -1588,6 +1593,9 @@ void launch_binary(const BinParams& p, hipStream_t s) {
 }
 void launch_unary(const UnaryParams& p, hipStream_t s) {
   hipLaunchKernelGGL(k_unary, dim3(grid_for(p.n)), dim3(256), 0, s, p);
+}
+void launch_cast_i32(const CastI32Params& p, hipStream_t s) {
+  if (p.n > 0) hipLaunchKernelGGL(k_cast_i32, dim3(grid_for(p.n)), dim3(256), 0, s, p);
 }
 void launch_copy(const CopyParams& p, hipStream_t s) {
   hipLaunchKernelGGL(k_copy, dim3(grid_for(p.n)), dim3(256), 0, s, p);

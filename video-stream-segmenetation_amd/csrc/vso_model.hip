@@ -338,6 +338,7 @@ int vso_ir_block_count(const vso_session* s) { return s ? s->ir_blocks : VSO_E_I
 int vso_attn_count(const vso_session* s) { return s ? s->attn_nodes : VSO_E_INVALID_ARG; }
 int vso_head_count(const vso_session* s) { return s ? s->head_nodes : VSO_E_INVALID_ARG; }
 int vso_qconv_count(const vso_session* s) { return s ? s->qconv_nodes : VSO_E_INVALID_ARG; }
+int vso_dynq_count(const vso_session* s) { return s ? s->dynq_nodes : VSO_E_INVALID_ARG; }
 int vso_lane_count(const vso_session* s) { return s ? (s->graph ? s->lanes_used : 0) : VSO_E_INVALID_ARG; }
 
 int vso_launch_name(const vso_session* s, int k, char* buf, int cap) {

@@ -1,7 +1,7 @@
 // vso_plan.hip — the ONNX sessions' planner: a parsed Graph (vso_onnx.h) and
 // the input shapes -> the session's launch list over preallocated HBM tensors
 // (vso_session.h), at create.  Host code; the kernels are vso_kernels.hip,
-// vso_conv.hip, vso_ir.hip, vso_deconv.hip, vso_attn.hip, vso_head.hip and vso_quant.hip.
+// vso_conv.hip, vso_ir.hip, vso_deconv.hip, vso_attn.hip, vso_head.hip, vso_quant.hip and vso_dynq.hip.
 //
 // Planning rules:
 //  * every shape is static once input 0's shape is fixed; nodes whose inputs
@@ -26,6 +26,10 @@
 //  * QuantizeLinear / DequantizeLinear of runtime tensors are k_quantize /
 //    k_dequantize over 8-bit buffers; DequantizeLinear -> Conv | Add [-> Relu |
 //    Clip] -> QuantizeLinear run on the integers in one launch (find_qdq);
+//  * DynamicQuantizeLinear is k_dyn_minmax + k_dyn_quantize, its scale and
+//    zero point staying in HBM; ConvInteger / MatMulInteger are k_iconv_tile /
+//    k_iconv_direct, and with the Cast -> Mul [-> Add] [-> Relu | Clip] behind
+//    them one launch ending in float32 (find_dynq);
 //  * every other runtime node is one launch, by the plan_<op> of its operator.
 #include <hip/hip_runtime.h>
 
@@ -1478,6 +1482,16 @@ struct Planner {
 
   bool plan_cast(size_t ni, const Node& nd, Ins& in) {
     const int64_t to = nd.ai("to", DT_FLOAT);
+    if (in[0]->qtype == DT_INT32) {  // a ConvInteger / MatMulInteger output: one conversion per element
+      if (to != DT_FLOAT) return fail("Cast '" + nd.name + "': unsupported: an int32 tensor is cast to FLOAT only");
+      const int* xp = reinterpret_cast<const int*>(s->bufs[in[0]->buf]);
+      const long n = (long)in[0]->numel();
+      const std::vector<int64_t> shape = in[0]->shape;
+      float* y = make_out(nd.out[0], shape);
+      if (!y) return false;
+      emit("vso::k_cast_i32(vso::CastI32Params)", CastI32Params{xp, y, n}, launch_cast_i32);
+      return true;
+    }
     // float16 storage semantics: round to the nearest half (the values stay
     // f32 in HBM; later ops compute in f32, a superset of the f16 precision)
     if (to == DT_FLOAT16) return plan_unary(nd, *in[0], ACT_F16, 0.f, 0.f);
@@ -2706,7 +2720,7 @@ struct Planner {
     v.shape = shape;
     v.qtype = type;
     if (v.numel() >= (int64_t{1} << 30)) return fail("quantised tensor '" + name + "': 2^30 elements or more"), nullptr;
-    if ((v.buf = new_buf((v.numel() + 3) / 4)) < 0) return nullptr;
+    if ((v.buf = new_buf(type == DT_INT32 ? v.numel() : (v.numel() + 3) / 4)) < 0) return nullptr;
     vals[name] = v;
     return reinterpret_cast<unsigned char*>(s->bufs[v.buf]);
   }
@@ -2756,17 +2770,41 @@ struct Planner {
     return true;
   }
 
-  // Only DequantizeLinear may read a QuantizeLinear's output — its buffer is a quarter of the floats — whichever
-  // plan its reader ends up in: checked on the graph, ahead of the pre-passes that absorb nodes into other launches
+  // Only DequantizeLinear (and ConvInteger / MatMulInteger as input 0) may read a QuantizeLinear's output — its
+  // buffer is a quarter of the floats — whichever plan its reader ends up in: checked on the graph, ahead of the
+  // pre-passes that absorb nodes into other launches
+  // The dynamic form's tensors alike: a DynamicQuantizeLinear's y is read by DequantizeLinear or as input 0 of
+  // ConvInteger / MatMulInteger, its zero point as their input 2 only; their int32 output by Cast to FLOAT only,
+  // and it is no graph output (the outputs leave as float32, which cannot hold it)
   bool check_quantised_readers() {
-    std::set<std::string> q;
-    for (const Node& nd : g.nodes)
+    std::set<std::string> q, dy, dz, i32;
+    for (const Node& nd : g.nodes) {
       if (nd.op == "QuantizeLinear" && !nd.out.empty()) q.insert(nd.out[0]);
-    if (q.empty()) return true;
-    for (const Node& nd : g.nodes)
-      for (size_t k = 0; k < nd.in.size(); ++k)
-        if (q.count(nd.in[k]) && !(nd.op == "DequantizeLinear" && k == 0))
-          return fail(nd.op + " '" + nd.name + "': unsupported: a quantised tensor is read by DequantizeLinear only");
+      if (nd.op == "DynamicQuantizeLinear") {
+        if (!nd.out.empty() && !nd.out[0].empty()) dy.insert(nd.out[0]);
+        if (nd.out.size() > 2 && !nd.out[2].empty()) dz.insert(nd.out[2]);
+      }
+      if ((nd.op == "ConvInteger" || nd.op == "MatMulInteger") && !nd.out.empty()) i32.insert(nd.out[0]);
+    }
+    if (q.empty() && dy.empty() && i32.empty()) return true;
+    for (const Node& nd : g.nodes) {
+      const bool integer = nd.op == "ConvInteger" || nd.op == "MatMulInteger";
+      const std::string at = nd.op + " '" + nd.name + "': unsupported: ";
+      for (size_t k = 0; k < nd.in.size(); ++k) {
+        if (q.count(nd.in[k]) && !((nd.op == "DequantizeLinear" || integer) && k == 0))
+          return fail(at + "a quantised tensor is read by DequantizeLinear only");
+        if (dy.count(nd.in[k]) && !((nd.op == "DequantizeLinear" || integer) && k == 0))
+          return fail(at + "a dynamically quantised tensor is read by ConvInteger, MatMulInteger (input 0) and DequantizeLinear only");
+        if (dz.count(nd.in[k]) && !(integer && k == 2))
+          return fail(at + "a DynamicQuantizeLinear's zero point is read by ConvInteger and MatMulInteger (input 2) only");
+        if (i32.count(nd.in[k]) && !(nd.op == "Cast" && k == 0 && nd.ai("to", DT_FLOAT) == DT_FLOAT))
+          return fail(at + "an int32 tensor is read by Cast to FLOAT only");
+      }
+    }
+    for (const IO& o : g.outputs)
+      if (i32.count(o.name))
+        return fail("graph output '" + o.name + "': unsupported: an int32 tensor (ConvInteger, MatMulInteger) is no graph "
+                    "output: Cast it to FLOAT");
     return true;
   }
 
@@ -2996,6 +3034,274 @@ struct Planner {
     return q_publish(out) ? 1 : -1;
   }
 
+  // ---- dynamically quantised graphs (vso_dynq.hip) --------------------------
+  // What onnxruntime's quantize_dynamic writes.  DynamicQuantizeLinear of a
+  // runtime f32 tensor: two launches (k_dyn_minmax, k_dyn_quantize) giving a
+  // uint8 byte tensor, y_scale (a rank-0 float32 runtime tensor) and
+  // y_zero_point (a one-element byte tensor), all three in HBM.  ConvInteger /
+  // MatMulInteger of a byte tensor by constant weights: one launch giving an
+  // int32 runtime tensor (Value::qtype DT_INT32), which only Cast to FLOAT
+  // reads — the plan that always works.  find_dynq finds the chain
+  //   ConvInteger | MatMulInteger -> Cast(FLOAT) -> Mul(., s) [-> Add(constant
+  //   bias)] [-> Relu | Clip(constant bounds)],  s = Mul(x_scale, w_scale)
+  // every interior value and s read by the next node only: one launch with the
+  // float epilogue (the same roundings, so the same bits), the scalar Mul none.
+  static bool dynq_enabled() { static const bool on = env_on("VSO_DYNQ"); return on; }
+
+  bool plan_dynamic_quantize(size_t ni, const Node& nd, Ins& in) {
+    const std::string at = "DynamicQuantizeLinear '" + nd.name + "': unsupported: ";
+    if (in.empty() || !in[0] || in[0]->is_const || in[0]->qtype) return fail(at + "a runtime float32 input only");
+    if (nd.out.size() != 3) return fail(at + "three outputs only");
+    DynQParams p{};
+    p.x = dptr(*in[0]);
+    p.n = (long)in[0]->numel();
+    const std::vector<int64_t> shape = in[0]->shape;
+    std::string names[3];
+    for (int k = 0; k < 3; ++k) names[k] = nd.out[k].empty() ? "\x01" "dynq" + std::to_string(ni) + "." + std::to_string(k) : nd.out[k];
+    if (!(p.y = make_q_out(names[0], shape, DT_UINT8))) return false;
+    if (!(p.scale = make_out(names[1], {}))) return false;
+    if (!(p.zp = make_q_out(names[2], {}, DT_UINT8))) return false;
+    if (!dalloc(&p.part, (size_t)kDynParts * 2 * sizeof(float))) return false;
+    p.blocks = dyn_blocks(p.n);
+    emit("vso::k_dyn_minmax(vso::DynQParams)", p, launch_dyn_minmax);
+    emit("vso::k_dyn_quantize(vso::DynQParams)", p, launch_dyn_quantize);
+    return q_publish(names[0]) && q_publish(names[2]);
+  }
+
+  struct DynFuse {
+    int cast, mul, smul;  // Cast, Mul(., s), s = Mul(x_scale, w_scale)
+    int add, act;         // Add(constant bias), Relu / Clip (-1: none)
+  };
+  std::map<size_t, DynFuse> dynfuse;  // by ConvInteger / MatMulInteger node (find_dynq)
+
+  // a value the walk will know as a constant: an initializer, or computed from such alone
+  bool const_deep(const std::string& n, int depth = 0) {
+    if (n.empty() || depth > 8) return false;
+    if (Value* v = val(n)) return v->is_const;
+    const int p = producer(n);
+    if (p < 0) return false;
+    const Node& nd = g.nodes[p];
+    if (nd.op == "Constant") return true;
+    if (nd.in.empty()) return false;
+    for (const std::string& i : nd.in)
+      if (!i.empty() && !const_deep(i, depth + 1)) return false;
+    return true;
+  }
+  static const std::string& other_operand(const Node& nd, const std::string& name) {
+    return nd.in[0] == name ? nd.in[1] : nd.in[0];
+  }
+
+  void find_dynq() {
+    for (size_t k = 0; k < g.nodes.size(); ++k) {
+      const Node& nd = g.nodes[k];
+      if ((nd.op != "ConvInteger" && nd.op != "MatMulInteger") || done.count(k) || nd.out.empty() || nd.in.size() < 2) continue;
+      DynFuse f{-1, -1, -1, -1, -1};
+      f.cast = sole_consumer(nd.out[0], k);
+      if (f.cast < 0 || g.nodes[f.cast].op != "Cast" || g.nodes[f.cast].ai("to", DT_FLOAT) != DT_FLOAT || done.count((size_t)f.cast))
+        continue;
+      const std::string& fl = g.nodes[f.cast].out[0];
+      f.mul = sole_consumer(fl, (size_t)f.cast);
+      if (f.mul < 0 || g.nodes[f.mul].op != "Mul" || g.nodes[f.mul].in.size() != 2 || done.count((size_t)f.mul)) continue;
+      const std::string& sname = other_operand(g.nodes[f.mul], fl);
+      f.smul = producer(sname);
+      if (sname == fl || f.smul < 0 || g.nodes[f.smul].op != "Mul" || g.nodes[f.smul].in.size() != 2 ||
+          done.count((size_t)f.smul) || consumers[sname] != 1 || is_graph_output(sname))
+        continue;
+      // x_scale: output 1 of the DynamicQuantizeLinear that made input 0; w_scale: a constant
+      const int pd = producer(nd.in[0]);
+      if (pd < 0 || g.nodes[pd].op != "DynamicQuantizeLinear" || g.nodes[pd].out.size() < 2 || g.nodes[pd].out[1].empty()) continue;
+      const std::string& xs = g.nodes[pd].out[1];
+      const Node& sm = g.nodes[f.smul];
+      if ((sm.in[0] == xs) == (sm.in[1] == xs) || !const_deep(other_operand(sm, xs))) continue;
+      std::string out = g.nodes[f.mul].out[0];
+      size_t last = (size_t)f.mul;
+      int c = sole_consumer(out, last);
+      if (c >= 0 && g.nodes[c].op == "Add" && g.nodes[c].in.size() == 2 && !done.count((size_t)c)) {
+        const std::string& b = other_operand(g.nodes[c], out);
+        if (b == out || !const_deep(b)) continue;  // (a runtime bias: the nodes as they are)
+        f.add = c;
+        out = g.nodes[c].out[0];
+        last = (size_t)c;
+        c = sole_consumer(out, last);
+      }
+      if (c >= 0 && (g.nodes[c].op == "Relu" || g.nodes[c].op == "Clip") && g.nodes[c].in[0] == out && !done.count((size_t)c)) {
+        bool ok = true;
+        for (size_t q = 1; q < g.nodes[c].in.size(); ++q) ok = ok && (g.nodes[c].in[q].empty() || const_deep(g.nodes[c].in[q]));
+        if (ok) f.act = c;
+      }
+      for (int q : {f.cast, f.mul, f.smul, f.add, f.act})
+        if (q >= 0) done.insert((size_t)q);
+      dynfuse[k] = f;
+    }
+  }
+
+  // a constant of one value, or of `channels` values lying along the channel axis of a rank-`rank` output
+  // (`axis` from the left: 1 of a ConvInteger's NCHW, the last of a MatMulInteger's) under ONNX broadcasting
+  static bool channel_const(const Value* v, int64_t channels, size_t rank, size_t axis, bool one_ok) {
+    if (!v || !v->is_const || v->c.is_int || v->c.f16 || v->c.f.empty()) return false;
+    const std::vector<int64_t>& d = v->c.dims;
+    if (d.size() > rank) return false;
+    const int64_t n = v->c.numel();
+    if (n == 1) return one_ok || channels == 1;
+    if (n != channels) return false;
+    for (size_t q = 0; q < d.size(); ++q)
+      if (d[q] != 1 && q + rank - d.size() != axis) return false;
+    return true;
+  }
+
+  struct Fused {  // the float epilogue of a fused chain
+    const float* xscale = nullptr;
+    std::vector<float> wscale, bias;
+    int act = ACT_NONE;
+    float lo = 0.f, hi = 0.f;
+    std::string out;
+  };
+
+  // the node heading a chain of find_dynq: 1 planned as one launch, 0 left to the nodes as they are, -1 failed
+  int try_plan_dynq(size_t ni) {
+    const DynFuse f = dynfuse[ni];
+    dynfuse.erase(ni);
+    const Node& nd = g.nodes[ni];
+    auto unfuse = [&]() -> int {
+      for (int q : {f.cast, f.mul, f.smul, f.add, f.act})
+        if (q >= 0) done.erase((size_t)q);
+      // (the scalar Mul placed ahead of this node: its launch now; behind it: when the walk reaches it)
+      return (size_t)f.smul < ni && !plan_node((size_t)f.smul) ? -1 : 0;
+    };
+    const bool mm = nd.op == "MatMulInteger";
+    Value* x = val(nd.in[0]);
+    Value* w = val(nd.in[1]);
+    if (!x || !w || !w->is_const || w->c.dims.size() != (mm ? 2u : 4u) || x->shape.size() < 2) return unfuse();  // (refused below, by name)
+    const int64_t M = mm ? w->c.dims[1] : w->c.dims[0];
+    const size_t rank = x->shape.size(), axis = mm ? rank - 1 : 1;
+    const Node& sm = g.nodes[f.smul];
+    const int pd = producer(nd.in[0]);
+    const std::string& xsn = g.nodes[pd].out[1];
+    Value* xs = val(xsn);
+    Value* ws = val(other_operand(sm, xsn));
+    if (!xs || xs->is_const || xs->qtype || xs->numel() != 1 || !channel_const(ws, M, rank, axis, true)) return unfuse();
+    Fused fu{};
+    fu.xscale = dptr(*xs);
+    fu.wscale.assign((size_t)M, 0.f);
+    for (int64_t m = 0; m < M; ++m) fu.wscale[m] = ws->c.f[ws->c.numel() == 1 ? 0 : m];
+    fu.out = g.nodes[f.mul].out[0];
+    if (f.add >= 0) {
+      Value* b = val(other_operand(g.nodes[f.add], fu.out));
+      if (!channel_const(b, M, rank, axis, false)) return unfuse();
+      fu.bias = b->c.f;
+      fu.out = g.nodes[f.add].out[0];
+    }
+    if (f.act >= 0) {
+      Epilogue ep{};
+      if (!act_of(g.nodes[f.act], &ep, (int)M)) return unfuse();
+      fu.act = ep.act; fu.lo = ep.a0; fu.hi = ep.a1;
+      fu.out = g.nodes[f.act].out[0];
+    }
+    return emit_integer(nd, &fu) ? 1 : -1;
+  }
+
+  bool plan_integer(size_t, const Node& nd, Ins&) { return emit_integer(nd, nullptr); }
+
+  // ConvInteger / MatMulInteger (the 1x1 convolution of N = rows, C = K, H = W = 1): k_iconv_tile where group is
+  // 1 and K < 2^15, else k_iconv_direct; fu: with the float epilogue, written as the chain's output
+  bool emit_integer(const Node& nd, const Fused* fu) {
+    const bool mm = nd.op == "MatMulInteger";
+    const std::string at = nd.op + " '" + nd.name + "': unsupported: ";
+    Value* in[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (size_t k = 0; k < 4 && k < nd.in.size(); ++k)
+      if (!nd.in[k].empty() && !(in[k] = val(nd.in[k])))
+        return fail("node '" + nd.name + "' (" + nd.op + "): input '" + nd.in[k] + "' is not defined");
+    Value *x = in[0], *w = in[1], *zx = in[2], *zw = in[3];
+    if (!x || x->is_const || (x->qtype != DT_UINT8 && x->qtype != DT_INT8))
+      return fail(at + "input 0 must be a quantised runtime tensor (uint8 / int8: DynamicQuantizeLinear, QuantizeLinear)");
+    if (!w || !w->is_const) return fail(at + "the weights (input 1) must be a constant");
+    if (!w->c.is_int || (w->c.dtype != DT_UINT8 && w->c.dtype != DT_INT8)) return fail(at + "uint8 / int8 weights only");
+    if (zw && !zw->is_const) return fail(at + "the weights' zero point (input 3) must be a constant");
+    if (zx && (zx->numel() != 1 || (zx->is_const ? !zx->c.is_int || zx->c.dtype != x->qtype : zx->qtype != x->qtype)))
+      return fail(at + "the input's zero point (input 2) must be one value of the input's type");
+    IConvParams p{};
+    std::vector<int64_t> oshape;
+    if (mm) {
+      const std::vector<int64_t>& as_ = x->shape;
+      if (w->c.dims.size() != 2) return fail(at + "a constant B of rank 2 only");
+      if (as_.size() < 2) return fail(at + "an A of rank >= 2 only");
+      if (as_.back() != w->c.dims[0]) return fail(nd.op + " '" + nd.name + "': inner dimensions differ");
+      p.C = (int)as_.back();
+      p.N = (int)(x->numel() / std::max<int64_t>(p.C, 1));
+      p.M = (int)w->c.dims[1];
+      p.H = p.W = p.Ho = p.Wo = p.kh = p.kw = p.sh = p.sw = p.dh = p.dw = p.G = 1;
+      p.Cg = p.C;
+      p.Mg = p.M;
+      oshape.assign(as_.begin(), as_.end() - 1);
+      oshape.push_back(p.M);
+    } else {
+      Node geo = nd;  // (inputs 2 and 3 are zero points, no bias: the attributes, list lengths and refusals are Conv's)
+      geo.in.resize(2);
+      ConvPlan c;
+      if (!conv_geometry(geo, &c)) return false;
+      const ConvParams& cp = c.p;
+      p.N = cp.N; p.C = cp.C; p.H = cp.H; p.W = cp.W; p.M = cp.M; p.Ho = cp.Ho; p.Wo = cp.Wo;
+      p.G = cp.G; p.Cg = cp.Cg; p.Mg = cp.Mg;
+      p.kh = cp.kh; p.kw = cp.kw; p.sh = cp.sh; p.sw = cp.sw; p.dh = cp.dh; p.dw = cp.dw; p.pt = cp.pt; p.pl = cp.pl;
+      oshape = c.oshape;
+    }
+    const int64_t K64 = (int64_t)p.Cg * p.kh * p.kw;
+    if (p.M < 1 || K64 < 1 || K64 >= (int64_t{1} << 30) || (int64_t)p.N * p.M * p.Ho * p.Wo >= (int64_t{1} << 30))
+      return fail(at + "2^30 elements or more");
+    p.K = (int)K64;
+    const int64_t nz = zw ? zw->c.numel() : 1;
+    if (zw && (!zw->c.is_int || zw->c.dtype != w->c.dtype || (nz != 1 && nz != p.M)))
+      return fail(at + "the weights' zero point (input 3) must be one value or one per output channel, of the weights' type");
+    // signed bytes: w' = Wq - 128 with zw' = zw - 128 (uint8), or as they are (int8)
+    const int off = w->c.dtype == DT_UINT8 ? 128 : 0;
+    std::vector<signed char> wi((size_t)p.M * p.K);
+    std::vector<int> wsum((size_t)p.M, 0), zwv((size_t)p.M, 0);
+    bool any_zw = false;
+    for (int m = 0; m < p.M; ++m) {
+      zwv[m] = (int)(zw ? zw->c.i[nz == 1 ? 0 : m] : 0) - off;
+      any_zw = any_zw || zwv[m] != 0;
+      for (int k = 0; k < p.K; ++k) {
+        const int64_t v = (mm ? w->c.i[(size_t)k * p.M + m] : w->c.i[(size_t)m * p.K + k]) - off;
+        wi[(size_t)m * p.K + k] = (signed char)v;
+        wsum[m] += (int)v;
+      }
+    }
+    const bool tile = p.G == 1 && p.K < (1 << 15);
+    if (tile) {
+      p.Kp = (p.K + kQK - 1) / kQK * kQK;
+      p.Mp = (p.M + kQBM - 1) / kQBM * kQBM;
+      std::vector<signed char> packed((size_t)p.Mp * p.Kp, 0);
+      for (int m = 0; m < p.M; ++m) std::copy(wi.begin() + (size_t)m * p.K, wi.begin() + (size_t)(m + 1) * p.K, packed.begin() + (size_t)m * p.Kp);
+      if (!(p.w = static_cast<const signed char*>(upload_bytes(packed.data(), packed.size())))) return false;
+      if (!(p.wsum = static_cast<const int*>(upload_bytes(wsum.data(), wsum.size() * 4)))) return false;
+      p.rows = p.H == 1 && p.W == 1 && p.kh == 1 && p.kw == 1 && p.pt == 0 && p.pl == 0;
+    } else if (!(p.w = static_cast<const signed char*>(upload_bytes(wi.data(), wi.size())))) {
+      return false;
+    }
+    if (any_zw && !(p.zw = static_cast<const int*>(upload_bytes(zwv.data(), zwv.size() * 4)))) return false;
+    p.xflip = x->qtype == DT_UINT8 ? 0x80 : 0;
+    if (zx && zx->is_const) {
+      const unsigned char b = (unsigned char)(int)zx->c.i[0];
+      if (!(p.zx = static_cast<const unsigned char*>(upload_bytes(&b, 1)))) return false;
+    } else if (zx) {
+      p.zx = qptr(*zx);
+    }
+    p.x = qptr(*x);
+    if (fu) {
+      p.xscale = fu->xscale;
+      if (!(p.wscale = upload_vec(fu->wscale))) return false;
+      if (!fu->bias.empty() && !(p.bias = upload_vec(fu->bias))) return false;
+      p.act = fu->act; p.lo = fu->lo; p.hi = fu->hi;
+      if (!(p.yf = make_out(fu->out, oshape))) return false;
+      s->dynq_nodes++;
+    } else if (!(p.yi = reinterpret_cast<int*>(make_q_out(nd.out[0], oshape, DT_INT32)))) {
+      return false;
+    }
+    if (tile) emit("vso::k_iconv_tile(vso::IConvParams)", p, launch_iconv_tile);
+    else emit("vso::k_iconv_direct(vso::IConvParams)", p, launch_iconv_direct);
+    return true;
+  }
+
   // ---- the walk ------------------------------------------------------------
   static std::vector<Operand> operands(const Ins& in) {
     std::vector<Operand> o;
@@ -3030,7 +3336,9 @@ struct Planner {
         {"Resize", &Planner::plan_resize}, {"Upsample", &Planner::plan_resize},
         {"Gemm", &Planner::plan_gemm}, {"MatMul", &Planner::plan_matmul},
         {"MatMulNBits", &Planner::plan_matmul_nbits},
-        {"QuantizeLinear", &Planner::plan_quantize}, {"DequantizeLinear", &Planner::plan_dequantize}};
+        {"QuantizeLinear", &Planner::plan_quantize}, {"DequantizeLinear", &Planner::plan_dequantize},
+        {"DynamicQuantizeLinear", &Planner::plan_dynamic_quantize},
+        {"ConvInteger", &Planner::plan_integer}, {"MatMulInteger", &Planner::plan_integer}};
     auto it = ops.find(op);
     return it == ops.end() ? nullptr : it->second;
   }
@@ -3044,6 +3352,10 @@ struct Planner {
     }
     if (qfuse.count(ni)) {  // the Conv / Add of a quantised pattern: one launch on the integers, or the nodes as they are
       const int r = try_plan_q(ni);
+      if (r != 0) return r > 0;
+    }
+    if (dynfuse.count(ni)) {  // a ConvInteger / MatMulInteger heading a chain: one launch with the float epilogue, or the nodes as they are
+      const int r = try_plan_dynq(ni);
       if (r != 0) return r > 0;
     }
     const Node& nd = g.nodes[ni];
@@ -3077,10 +3389,16 @@ struct Planner {
     }
     const PlanOp plan = plan_of(op);
     if (!plan) return fail("unsupported operator " + op + " (node '" + nd.name + "')");
-    if (op != "DequantizeLinear")  // (a quantised tensor's buffer is a quarter of the floats: no float kernel may read it)
-      for (const Value* v : in)
-        if (v && v->qtype)
-          return fail(op + " '" + nd.name + "': unsupported: a quantised tensor is read by DequantizeLinear only");
+    // (a quantised tensor's buffer is a quarter of the floats, an int32 one holds integers: no float kernel may read either)
+    const bool integer = op == "ConvInteger" || op == "MatMulInteger";
+    for (size_t k = 0; k < in.size(); ++k) {
+      const Value* v = in[k];
+      if (!v || !v->qtype) continue;
+      if (v->qtype == DT_INT32 ? !(op == "Cast" && k == 0) : !((op == "DequantizeLinear" && k == 0) || (integer && (k == 0 || k == 2))))
+        return fail(op + " '" + nd.name + "': unsupported: " +
+                    (v->qtype == DT_INT32 ? "an int32 tensor is read by Cast to FLOAT only"
+                                          : "a quantised tensor is read by DequantizeLinear, ConvInteger and MatMulInteger only"));
+    }
     return (this->*plan)(ni, nd, in);
   }
 
@@ -3105,6 +3423,7 @@ struct Planner {
     if (s->conv_precision != PREC_F32) find_up_fusions();
     if (head_enabled()) find_heads();
     if (qdq_enabled()) find_qdq();
+    if (dynq_enabled()) find_dynq();
     for (size_t k = 0; k < g.nodes.size(); ++k) {
       if (done.count(k)) continue;
       if (!plan_node(k)) return false;

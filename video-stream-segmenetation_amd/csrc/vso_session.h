@@ -20,7 +20,8 @@ struct Value {
   bool is_const = false;
   vso_onnx::Const c;  // when is_const
   int buf = -1;       // runtime tensor: device buffer id
-  int qtype = 0;      // runtime tensor: 0 float32, or DT_UINT8 / DT_INT8: quantised, one byte per element in `buf`
+  int qtype = 0;      // runtime tensor: 0 float32, or DT_UINT8 / DT_INT8: quantised, one byte per element in `buf`,
+                      // or DT_INT32 (a ConvInteger / MatMulInteger output): four bytes per element
   int64_t numel() const {
     int64_t n = 1;
     for (int64_t d : shape) n *= d;
@@ -57,6 +58,7 @@ struct vso_session {
   int attn_nodes = 0;      // attention patterns planned on k_attn (vso_attn_count)
   int head_nodes = 0;      // fused class heads planned on k_class_head (vso_head_count)
   int qconv_nodes = 0;     // fused quantised launches: k_qconv_tile + k_qconv_dw + k_qadd (vso_qconv_count)
+  int dynq_nodes = 0;      // ConvInteger / MatMulInteger chains planned as one launch with the float epilogue (vso_dynq_count)
   hipStream_t stream = nullptr;
   std::string err;
   std::vector<std::string> in_names, out_names;

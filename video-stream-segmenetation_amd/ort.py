@@ -11,7 +11,7 @@ becomes
 
 Tensors are float32 NCHW numpy arrays; an output the model declares int64,
 int32 or uint8 (ArgMax labels), or that is a quantised uint8 / int8 tensor
-(QuantizeLinear), comes back from run() in that dtype, as onnxruntime returns
+(QuantizeLinear, DynamicQuantizeLinear), comes back from run() in that dtype, as onnxruntime returns
 it — on the device it is float32 holding exact integers
 (vso_output_type), and run_device hands out those float32 buffers.  Fails loudly (VsoError) when the
 library or an operator is missing: there is no CPU fallback.
@@ -57,6 +57,7 @@ def lib():
             "vso_attn_count": ([P], I),
             "vso_head_count": ([P], I),
             "vso_qconv_count": ([P], I),
+            "vso_dynq_count": ([P], I),
             "vso_output_type": ([P, I], I),
             "vso_lane_count": ([P], I),
             "vso_destroy": ([P], None),
@@ -180,6 +181,10 @@ class InferenceSession:
     def qconv_nodes(self) -> int:
         """Quantised patterns planned as one launch on the integers each (k_qconv_tile, k_qconv_dw, k_qadd)."""
         return _check(lib().vso_qconv_count(self._h), self._h)
+
+    def dynq_nodes(self) -> int:
+        """ConvInteger / MatMulInteger chains planned as one launch ending in float32 (k_iconv_tile, k_iconv_direct)."""
+        return _check(lib().vso_dynq_count(self._h), self._h)
 
     def lanes(self) -> int:
         """Capture lanes of the session's graph (0 before its first run)."""
